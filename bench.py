@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — PPO experience+loss hot path throughput on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--cpu-seconds S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR]
+                  [--full [--cpu-seconds S]]
+
+A plain run does what the headline figure needs and no more: set up, W warm-up steps (+ the
+settle), K timed steps, the outputs if --dump-outputs is given, the result line.  --full adds
+the secondary measurements: the CPU baseline, and at C2 on one GPU the fp32-logits line and
+the from-hidden loss-side leg (each with runs of its own after the headline's).
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32; an array of more than DUMP_MAX_ELEMS elements as a fixed, seeded sample of that
+many).  Inputs are seeded, and with this option the hot path under test runs exactly W + K
+steps (the settle steps go to a twin), so two builds can be compared output for output.
 
 One "step" = one PPOHotPath.step over one shard of synthetic rollouts (see
 trlx-t5_amd/step.py): policy+reference log-softmax-gather (experience), fused KL reward
@@ -17,7 +28,7 @@ tokens = action tokens; no collective — the reference's ILQL loss is rank-loca
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with
   roofline      dominant kernel's algorithmic bytes / its average HIP-event time vs 8 TB/s
-  cpu_baseline  the oracle (op-for-op reference PyTorch path) on host cores, bounded sample
+  cpu_baseline  (--full) the oracle (op-for-op reference PyTorch path) on host cores, bounded sample
 """
 import argparse
 import json
@@ -52,17 +63,26 @@ def parse():
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=50)
     p.add_argument("--config", default="c2", choices=sorted(CONFIGS))
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements, each after the headline's timed steps: the CPU "
+                        "baseline (--cpu-seconds), and at C2 on one GPU the fp32-logits line and the from_hidden "
+                        "leg; off by default: a plain run times the N steps and prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one returned (PPO: loss, stats, dlogits, "
+                        "dvalues; ILQL: losses, dlogits, dq0, dq1, dvs) to DIR/<name>.npy as float32, large arrays "
+                        "as a fixed seeded sample; one GPU, no process group")
     p.add_argument("--cpu-seconds", type=float, default=8.0,
-                   help="CPU baseline budget per logits dtype (0 = skip); PPO times bf16 and fp32")
+                   help="--full: CPU baseline budget per logits dtype (0 = skip); PPO times bf16 and fp32")
     p.add_argument("--settle-ms", type=float, default=200.0,
                    help="after the W warm-up steps keep stepping until the GPU has been busy this long: an "
                         "idle MI355X runs this step up to ~20%% slow for its first ~20-40 ms of load "
                         "(profiles/r02_slowstart.log); reported as warmup_steps_run / warmup_ms (0 = off)")
     p.add_argument("--no-fp32-line", action="store_true",
-                   help="PPO C2 at N=1: skip the secondary fp32-logits measurement (reported under fp32_logits)")
+                   help="--full, PPO C2 at N=1: skip the secondary fp32-logits measurement (reported under "
+                        "fp32_logits)")
     p.add_argument("--no-timers", action="store_true", help="skip per-kernel HIP events")
     p.add_argument("--no-from-hidden", action="store_true",
-                   help="PPO C2 at N=1: skip the secondary §8f-2 loss-side measurement (reported under from_hidden: "
+                   help="--full, PPO C2 at N=1: skip the secondary §8f-2 loss-side measurement (reported under from_hidden: "
                         "the PPO update from hidden states, fused MFMA route vs the hipBLASLt logits route)")
     p.add_argument("--from-hidden-steps", type=int, default=10,
                    help="updates per route and round of the from_hidden measurement (3 interleaved rounds)")
@@ -538,7 +558,7 @@ def from_hidden_leg(torch, P, dev, name, steps, rounds=3):
 SETTLE_CHUNK = 8  # steps between the ranks' agreement on whether the settle is over (N > 1)
 
 
-def settle_and_warm(step, torch, args, dev, world=1, dist=None):
+def settle_and_warm(step, torch, args, dev, world=1, dist=None, settle_step=None):
     """The W warm-up steps, then (settle) more steps until the GPU has been kept busy for
     --settle-ms.  Measured cause (tools/slowstart_probe.py, profiles/r02_slowstart.log): after
     an idle period (process start, or 1 s of sleep) this step runs 10-20 % slow for its first
@@ -548,7 +568,10 @@ def settle_and_warm(step, torch, args, dev, world=1, dist=None):
     N > 1: every step carries collectives, so every rank must run the SAME number of settle
     steps (one extra step on one rank pairs its all-reduces with the next step's of the
     others and leaves its last one waiting forever): the ranks decide together, every
-    SETTLE_CHUNK steps, with an all-reduce of their "settled" flags (MIN: until all are)."""
+    SETTLE_CHUNK steps, with an all-reduce of their "settled" flags (MIN: until all are).
+    settle_step (--dump-outputs): the settle runs this step instead — the same work on a twin
+    hot path — so the number of steps `step`'s hot path has run does not depend on the clock."""
+    settle_step = settle_step or step
     from trlx_t5_amd.timing import LaunchEvent
     t0 = time.perf_counter()
     for _ in range(args.warmup):
@@ -570,7 +593,7 @@ def settle_and_warm(step, torch, args, dev, world=1, dist=None):
                         break
             elif (time.perf_counter() - t1) * 1e3 >= args.settle_ms:
                 break
-            step()
+            settle_step()
             ev = ring[extra % len(ring)]
             ev.record(s)
             extra += 1
@@ -584,7 +607,8 @@ def timed_run(step, hp, torch, dist, args, dev, world, names):
     """Exactly K steps between barrier + synchronize pairs; max over ranks.  Per-kernel HIP
     events (fence-free) on every TIMER_EVERY-th step, around the vocab-row launches only:
     an event between two kernels idles the queue briefly, so instrumenting every step
-    would tax `value`."""
+    would tax `value`.  Also returns what the last step returned to its caller."""
+    last = None
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -594,7 +618,7 @@ def timed_run(step, hp, torch, dist, args, dev, world, names):
     t0 = time.perf_counter()
     for i in range(args.steps):
         hp.timers = timers if (not args.no_timers and i % TIMER_EVERY == TIMER_EVERY - 1) else None
-        step()
+        last = step()
     hp.timers = None
     if hasattr(hp, "wait_stats"):
         hp.wait_stats()  # a deferred loss tail runs here, inside the timed region
@@ -614,7 +638,7 @@ def timed_run(step, hp, torch, dist, args, dev, world, names):
     for name, evs in timers.items():  # HIP events on the launch stream, timed region only
         kern_ms[name] = sum(a.elapsed_time(b) for a, b in evs) / len(evs)
         samples[name] = len(evs)
-    return elapsed, kern_ms, samples, per_rank
+    return elapsed, kern_ms, samples, per_rank, last
 
 
 def pmc_traffic(key, dom):
@@ -649,8 +673,42 @@ def roofline(kern_ms, samples, ab, tokens, doms, elapsed, steps, traffic_key):
             "step_frac": round(ab["step"] * tokens / (elapsed / steps) / 1e9 / HBM_PEAK_GBS, 4)}
 
 
-def ppo_setup(torch, P, args, B, T, V, dev, rank, masked, ldt, world=1, comm=None):
-    x = make_inputs(torch, B, T, V, dev, seed=1000 + rank, masked=masked, dtype=ldt)
+DUMP_MAX_ELEMS = 1 << 22  # per array: 4 Mi float32 = 16 MiB (ILQL's three [B, L, V] gradients: 48 MiB in all)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(torch, outdir, last, ilql):
+    """--dump-outputs: what the last timed step returned to its caller, as outdir/<name>.npy
+    in float32.  An array of more than DUMP_MAX_ELEMS elements is written as that many of its
+    elements in row-major order at indices drawn once from a generator seeded with DUMP_SEED
+    (so the same elements in every run and every build).  The pipelined PPO schedule returns
+    the outputs of the batch submitted one call earlier; loss / stats are final here, after
+    timed_run's wait_stats()."""
+    import numpy as np
+    if last is None:
+        raise SystemExit("--dump-outputs: the last step returned nothing (the pipelined schedule returns the previous "
+                         "batch's outputs: it needs two steps, warm-up included)")
+    if ilql:
+        losses, dlogits, dq, dvs = last
+        named = {"losses": losses, "dlogits": dlogits, **{f"dq{i}": q for i, q in enumerate(dq)}, "dvs": dvs}
+    else:
+        named = dict(zip(("loss", "stats", "dlogits", "dvalues"), last))
+    torch.cuda.synchronize()
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in named.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, flat.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            arr = flat[idx.to(flat.device)].float().cpu().numpy()
+        else:
+            arr = t.detach().float().cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), arr.astype(np.float32, copy=False))
+
+
+def ppo_setup(torch, P, args, B, T, V, dev, rank, masked, ldt, world=1, comm=None, x=None):
+    if x is None:  # (given: a second hot path over inputs already made)
+        x = make_inputs(torch, B, T, V, dev, seed=1000 + rank, masked=masked, dtype=ldt)
     cfg = P.PPOConfig()  # configs/ppo_config.yml method: adaptive KL (target 6, horizon 10000), clip 10
     ctl = None if args.host_state else P.PPOControlState.from_config(cfg, dev, n_steps=B)  # train.batch_size per process
     pipelined = args.schedule in ("pipelined", "auto")
@@ -669,6 +727,8 @@ def ppo_setup(torch, P, args, B, T, V, dev, rank, masked, ldt, world=1, comm=Non
 
 def main():
     args = parse()
+    if args.dump_outputs and not args.dry_run and (args.gpus != 1 or args.dist):
+        raise SystemExit("--dump-outputs writes one process's outputs: --gpus 1 without --dist")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], args.rank_timeout))
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
@@ -739,20 +799,29 @@ def main():
         # PMC bytes were collected at the config's rows per GPU
         traffic_key = None if args.global_batch else args.config + ("_fp32" if args.logits_dtype == "fp32" else "")
 
-    warm_steps, warm_ms = settle_and_warm(step, torch, args, dev, world, dist)
-    elapsed, kern_ms, samples, per_rank = timed_run(step, hp, torch, dist, args, dev, world, names)
+    # --dump-outputs: the PPO step carries state from step to step (RunningMoments, beta), and
+    # the settle runs for a time, not a count: it goes to a twin hot path on the same inputs
+    # (the ILQL step has no such state)
+    settle_step = None
+    if args.dump_outputs and not ilql and args.settle_ms > 0:
+        _, settle_step, _ = ppo_setup(torch, P, args, B, T, V, dev, rank, masked, ldt, world, comm, x=x)
+    warm_steps, warm_ms = settle_and_warm(step, torch, args, dev, world, dist, settle_step)
+    elapsed, kern_ms, samples, per_rank, last = timed_run(step, hp, torch, dist, args, dev, world, names)
     roof = roofline(kern_ms, samples, ab, tokens, doms, elapsed, args.steps, traffic_key)
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, last, ilql)
+    del last, settle_step
 
     # Secondary line (C2 at N=1): the same step with fp32 logits (the reference's GPT path,
     # ppo_models.py:225-289; BASELINE.md asks for both dtypes), same K / W / settle.
     fp32_line = None
-    if (not ilql and world == 1 and args.config == "c2" and args.logits_dtype == "bf16" and not args.no_fp32_line
-            and not args.global_batch):
+    if (args.full and not ilql and world == 1 and args.config == "c2" and args.logits_dtype == "bf16"
+            and not args.no_fp32_line and not args.global_batch):
         del hp, step, x
         torch.cuda.empty_cache()
         hp32, step32, x32 = ppo_setup(torch, P, args, B, T, V, dev, rank, masked, torch.float32, world, comm)
         w32, wms32 = settle_and_warm(step32, torch, args, dev)
-        el32, km32, sm32, _ = timed_run(step32, hp32, torch, dist, args, dev, world, names)
+        el32, km32, sm32, _, _ = timed_run(step32, hp32, torch, dist, args, dev, world, names)
         fp32_line = {"value": round(tokens * args.steps / el32, 1), "unit": "tokens/s",
                      "ms_per_step": round(el32 / args.steps * 1e3, 4), "warmup_steps_run": w32,
                      "warmup_ms": round(wms32, 1),
@@ -764,15 +833,15 @@ def main():
     # Secondary line (C2 at N=1): §8f-2's loss side from hidden states (the fused
     # route's speed-up over the hipBLASLt logits route, measured by the driver's run)
     from_hidden = None
-    if (not ilql and world == 1 and args.config == "c2" and args.logits_dtype == "bf16" and not args.no_from_hidden
-            and not args.global_batch):
+    if (args.full and not ilql and world == 1 and args.config == "c2" and args.logits_dtype == "bf16"
+            and not args.no_from_hidden and not args.global_batch):
         from_hidden = {name: from_hidden_leg(torch, P, dev, name, args.from_hidden_steps)
                        for name in FROM_HIDDEN_SHAPES}
 
     out = None
     if rank == 0:
         cpu = None
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             if ilql:
                 cpu = ilql_cpu_baseline(torch, T, V, args.cpu_seconds)
             else:  # both logits dtypes; `cpu_baseline` itself is the one matching this line

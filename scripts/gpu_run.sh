@@ -25,13 +25,13 @@ for step in "$@"; do
         sweep) run sweep 300 python tools/row_sweep.py ;;
         sweep_c4) B=128 T=128 V=32128 run sweep_c4 300 python tools/row_sweep.py ;;
         sweep_f32) DT=f32 run sweep_f32 300 python tools/row_sweep.py ;;
-        bench) run bench 400 python bench.py ;;
-        bench_c3) run bench_c3 300 python bench.py --config c3 --cpu-seconds 10 ;;
-        bench_c5) run bench_c5 300 python bench.py --config c5 --cpu-seconds 10 ;;
+        bench) run bench 400 python bench.py --full ;;
+        bench_c3) run bench_c3 300 python bench.py --config c3 --full --cpu-seconds 10 ;;
+        bench_c5) run bench_c5 300 python bench.py --config c5 --full --cpu-seconds 10 ;;
         profile_c5) run profile_c5 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_c5 \
                      -o run -- python bench.py --config c5 --cpu-seconds 0 ;;
         ilql) run ilql_tests 300 python -u -m pytest tests/test_gpu_ilql.py -x -v --timeout 120 --timeout-method thread -p no:cacheprovider ;;
-        bench_c4) run bench_c4 300 python bench.py --config c4 --cpu-seconds 10 ;;
+        bench_c4) run bench_c4 300 python bench.py --config c4 --full --cpu-seconds 10 ;;
         profile_nt) run profile_nt 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_nt \
                      -o run -- python bench.py --steps 20 --warmup 5 --cpu-seconds 0 --no-timers ;;
         bench_nt) run bench_nt 300 python bench.py --steps 20 --warmup 5 --cpu-seconds 0 --no-timers ;;
@@ -66,7 +66,7 @@ for step in "$@"; do
         stamps) LL_HS=1 LL_STAMPS=1 LL_TUNE=lmloss_fwd=4,lmloss_dw=3 run stamps 300 python tools/lmloss_ablate.py --libs stamp/lib_stamp.so ;;
         ablate) LL_HS=1 LL_STAMPS=1 LL_TUNE=lmloss_fwd=3,lmloss_dw=2 run ablate 300 python tools/lmloss_ablate.py \
                     --libs stamp/lib_stamp.so,stamp/lib_abl4.so,stamp/lib_abl1.so ;;
-        bench20) run bench20 400 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
+        bench20) run bench20 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full ;;
         *) echo "unknown step $step"; exit 2 ;;
     esac
 done

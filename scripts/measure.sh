@@ -21,7 +21,7 @@ B="python3 bench.py --cpu-seconds 0 --no-fp32-line"
 steps=${@:-bench c3 c4 c5 strong prof prof_c4 prof_c5 pmc}
 for st in $steps; do
     case $st in
-        bench) run ${TAG}_bench_c2 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 ;;
+        bench) run ${TAG}_bench_c2 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ;;
         c3) run ${TAG}_bench_c3 300 $B --config c3 --steps 200 --warmup 5 ;;
         c4) run ${TAG}_bench_c4 300 $B --config c4 --steps 200 --warmup 5 ;;
         c5) run ${TAG}_bench_c5 300 $B --config c5 --steps 100 --warmup 5 ;;

@@ -12,8 +12,8 @@ step() {  # name limit cmd...
     local rc=$?; echo "$n rc=$rc"; tail -c 1500 $O/$n.log | tail -2
     if [ $rc -ne 0 ]; then exit $rc; fi
 }
-step bench_c2 300 python bench.py --steps 20 --warmup 5
-step bench_c3 300 python bench.py --config c3 --cpu-seconds 10
+step bench_c2 300 python bench.py --steps 20 --warmup 5 --full
+step bench_c3 300 python bench.py --config c3 --full --cpu-seconds 10
 step lossside_c2 200 python tools/lossside_bench.py --config c2 --routes gemm,fused,fused_recompute --rounds 5 --iters 10
 step lossside_c3 200 python tools/lossside_bench.py --config c3 --routes gemm,fused,fused_recompute --rounds 5 --iters 10
 cd /tmp && export TMPDIR=/tmp

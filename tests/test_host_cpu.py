@@ -312,3 +312,13 @@ def test_bench_refuses_mislabelled_world():
     r = subprocess.run([__import__("sys").executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run"],
                        capture_output=True, text=True, env=env, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
+
+
+def test_bench_dump_outputs_needs_one_process(tmp_path):
+    """--dump-outputs writes one process's outputs: refused for --gpus N > 1 before any rank
+    starts (nothing is written)."""
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs",
+                        str(tmp_path / "out")], capture_output=True, text=True, env=_bench_env(), timeout=120)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr
+    assert not (tmp_path / "out").exists()

@@ -63,7 +63,7 @@ def main():
             x["lengths"], x["mask"] = pats[name]
             _lib.set_tuning(a.key, o)
             bench.settle_and_warm(step, torch, ns, dev)
-            el, km, _ = bench.timed_run(step, hp, torch, dist, ns, dev, 1, {"experience", "loss"})
+            el, km, *_ = bench.timed_run(step, hp, torch, dist, ns, dev, 1, {"experience", "loss"})
             res[key].append((el / a.steps * 1e3, km["experience"] * 1e3, km["loss"] * 1e3))
             print(f"round {rnd} {key:12s} step {res[key][-1][0]:.4f} ms  E {res[key][-1][1]:7.2f} us  "
                   f"L {res[key][-1][2]:7.2f} us", flush=True)
