@@ -424,7 +424,7 @@ int trlx_lmhead_logprobs_bwd(const void* hidden, int64_t ldh, const void* weight
 /* The same pair, extended (replaces the same reference lines as the pair above:
  * accelerate_ppo_model.py:96-118 through ppo_models.py:640 and modeling.py:37-41):
  *   saved: NULL = the recompute plan (as above), or a region of trlx_lmhead_savep_bytes(N, H, V)
- *          bytes (⌈V/64⌉·2⌈N/64⌉·4 KB + 128·N B: 0.62 GB at N = 6144, V = 50257 — the size of
+ *          bytes (2⌈V/128⌉·2⌈N/64⌉·4 KB + 32·N B: 0.62 GB at N = 6144, V = 50257 — the size of
  *          bf16 logits) the forward fills with its bf16 P tiles and per-(split, token) records
  *          and the caller keeps, unmodified, until the backward: the dW pass then reads P back
  *          (3 MFMA passes in all) instead of recomputing S (4);
@@ -432,8 +432,15 @@ int trlx_lmhead_logprobs_bwd(const void* hidden, int64_t ldh, const void* weight
  *          MFMA pass — their lp and lse are 0 and they get a zero dh and no share of dW (what the
  *          PPO loss's own mask gives them: ppo_models.py:150-199 multiplies every lp term by it).
  *          The backward takes the same mask (it rebuilds the same stable order).
- * The "lmloss_splits" tuning must not change between the two calls (the records follow the
- * forward's split plan).  lm_workspace as the pair above. */
+ * The forward-to-backward plan contract: the saved P tiles and records are laid out by the
+ * forward's split plan ("lmloss_splits": fixed count or auto) and split granule, and the
+ * backward must map them the same way.  The *_ex2 pair carries that plan itself: the forward
+ * writes a host-side token to *plan_out (the "lmloss_splits", "lmloss_dwp_form" and "lmloss_dw"
+ * values it read, once), the backward takes it by value and reads none of those knobs, so the
+ * tuning may change between the two calls (a backward with a token of a forward that kept P
+ * runs the saved-P dW pass in the forward's form; a value that is no token: TRLX_ERR_ARG).
+ * The *_ex pair has no token: its backward reads the knobs again, and the caller must hold
+ * those three unchanged from the forward to the backward.  lm_workspace as the pair above. */
 int64_t trlx_lmhead_savep_bytes(int64_t N, int64_t H, int64_t V);
 int trlx_lmhead_logprobs_fwd_ex(const void* hidden, int64_t ldh, const void* weight, int64_t ldw, int64_t N,
                                 int64_t H, int64_t V, const int64_t* labels, int64_t lb, const int64_t* mask,
@@ -444,6 +451,15 @@ int trlx_lmhead_logprobs_bwd_ex(const void* hidden, int64_t ldh, const void* wei
                                 const void* grad, int grad_dtype, const float* lse, const float* e, void* dhidden,
                                 int64_t lddh, int dh_dtype, void* dweight, int dw_dtype, int64_t lddw,
                                 void* lm_workspace, const void* saved, void* stream);
+int trlx_lmhead_logprobs_fwd_ex2(const void* hidden, int64_t ldh, const void* weight, int64_t ldw, int64_t N,
+                                 int64_t H, int64_t V, const int64_t* labels, int64_t lb, const int64_t* mask,
+                                 void* lp_out, int lp_dtype, float* lse_out, float* e_out, void* lm_workspace,
+                                 void* saved, int64_t* plan_out, void* stream);
+int trlx_lmhead_logprobs_bwd_ex2(const void* hidden, int64_t ldh, const void* weight, int64_t ldw, int64_t N,
+                                 int64_t H, int64_t V, const int64_t* labels, int64_t lb, const int64_t* mask,
+                                 const void* grad, int grad_dtype, const float* lse, const float* e, void* dhidden,
+                                 int64_t lddh, int dh_dtype, void* dweight, int dw_dtype, int64_t lddw,
+                                 void* lm_workspace, const void* saved, int64_t plan, void* stream);
 
 /* ---------------------------------------------------------------- §8f rank 3: ILQL sampling step
  * One decode step of CausalLMWithValueHeads.generate (ilql_models.py:296-316) per row b:

@@ -487,34 +487,46 @@ def test_lm_head_logprobs_auto_plan_falls_back_when_p_does_not_fit(monkeypatch):
 import lmloss_checks as C  # noqa: E402
 
 
-def _fwd_saved_bwd(h, w, y, gout, dh_dtype, dw_dtype, plan="recompute"):
+def _fwd_saved_bwd(h, w, y, gout, dh_dtype, dw_dtype, plan="recompute", lddh=None, lddw=None, grad_dtype=None,
+                   lp_dtype=None, mask=None, pad_fill=-7.25):
     """The drop-in pair through the C ABI on this thread (lp, lse, the saved E, dh, dW):
-    trlx_lmhead_logprobs_fwd_saved + _bwd (recompute plan) or _fwd_savep + _bwd_savep
-    (saved_p: the forward's P tiles kept in a region of trlx_lmhead_savep_bytes)."""
+    trlx_lmhead_logprobs_fwd_saved + _bwd (recompute plan) or _fwd_ex + _bwd_ex (saved_p: the
+    forward's P tiles kept in a region of trlx_lmhead_savep_bytes; also the recompute plan when
+    a mask is given, saved = NULL).  Optional corners of the ABI, the defaults being contiguous
+    fp32: h / w already on the device are passed as they are, with their own row strides (ldh,
+    ldw); lddh / lddw: dh / dW are written into [N, lddh] / [V, lddw] buffers pre-filled with
+    pad_fill and returned as their [:, :H] views (the padding: dh._base[:, H:]); grad_dtype /
+    lp_dtype: the dtype of the incoming gradient and of lp; mask: [N], tokens with 0 skipped."""
     N, H = h.shape
     V = w.shape[0]
     L = P._lib
-    hd, wd, yd, gd = h.to(DEV), w.to(DEV), y.to(DEV), gout.to(DEV).float()
+    hd, wd, yd = h.to(DEV), w.to(DEV), y.to(DEV)
+    gd = gout.to(DEV).to(grad_dtype or torch.float32)
+    md = None if mask is None else mask.to(DEV).to(torch.int64).contiguous()
     f32 = dict(dtype=torch.float32, device=DEV)
-    lp, lse, e = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty((N, H), **f32)
+    lp, lse, e = torch.empty(N, dtype=lp_dtype or torch.float32, device=DEV), torch.empty(N, **f32), \
+        torch.empty((N, H), **f32)
     ws = torch.empty(L.query("trlx_lmhead_loss_workspace_bytes", N, H, V), dtype=torch.uint8, device=DEV)
     s = torch.cuda.current_stream(DEV).cuda_stream
-    fwd = (hd.data_ptr(), H, wd.data_ptr(), H, N, H, V, yd.data_ptr(), 1, lp.data_ptr(), L.F32, lse.data_ptr(),
-           e.data_ptr(), ws.data_ptr())
+    fwd = (hd.data_ptr(), hd.stride(0), wd.data_ptr(), wd.stride(0), N, H, V, yd.data_ptr(), 1, lp.data_ptr(),
+           L.dtype_code(lp), lse.data_ptr(), e.data_ptr(), ws.data_ptr())
     saved = None
+    ex = plan == "saved_p" or md is not None
     if plan == "saved_p":
         saved = torch.empty(L.query("trlx_lmhead_savep_bytes", N, H, V), dtype=torch.uint8, device=DEV)
-        L.call("trlx_lmhead_logprobs_fwd_ex", *fwd[:9], None, *fwd[9:], saved.data_ptr(), s)
+    if ex:
+        L.call("trlx_lmhead_logprobs_fwd_ex", *fwd[:9], L.ptr(md), *fwd[9:], L.ptr(saved), s)
     else:
         L.call("trlx_lmhead_logprobs_fwd_saved", *fwd, s)
     del ws  # the forward's partials are not needed by the backward
-    dh = torch.empty((N, H), dtype=dh_dtype, device=DEV)
-    dw = torch.empty((V, H), dtype=dw_dtype, device=DEV)
+    dh = torch.full((N, lddh or H), pad_fill, dtype=dh_dtype, device=DEV)[:, :H]
+    dw = torch.full((V, lddw or H), pad_fill, dtype=dw_dtype, device=DEV)[:, :H]
     wsb = torch.empty(L.query("trlx_lmhead_loss_bwd_workspace_bytes", N, H, V), dtype=torch.uint8, device=DEV)
-    bwd = (hd.data_ptr(), H, wd.data_ptr(), H, N, H, V, yd.data_ptr(), 1, gd.data_ptr(), L.F32, lse.data_ptr(),
-           e.data_ptr(), dh.data_ptr(), H, L.dtype_code(dh), dw.data_ptr(), L.dtype_code(dw), H, wsb.data_ptr())
-    if saved is not None:
-        L.call("trlx_lmhead_logprobs_bwd_ex", *bwd[:9], None, *bwd[9:], saved.data_ptr(), s)
+    bwd = (hd.data_ptr(), hd.stride(0), wd.data_ptr(), wd.stride(0), N, H, V, yd.data_ptr(), 1, gd.data_ptr(),
+           L.dtype_code(gd), lse.data_ptr(), e.data_ptr(), dh.data_ptr(), dh.stride(0), L.dtype_code(dh),
+           dw.data_ptr(), L.dtype_code(dw), dw.stride(0), wsb.data_ptr())
+    if ex:
+        L.call("trlx_lmhead_logprobs_bwd_ex", *bwd[:9], L.ptr(md), *bwd[9:], L.ptr(saved), s)
     else:
         L.call("trlx_lmhead_logprobs_bwd", *bwd, s)
     torch.cuda.synchronize()

@@ -9,6 +9,8 @@ On flat and peaked operands, in fp64 on the CPU:
       - dW's −p·h term zeroed or scaled by 0.9 (a bad split partial / reduce / tail block),
       - E = Σ p·W zeroed or scaled by 1.1 / 0.8 (a bad O product or combine),
       - the last, partial 64-row vocab block of dW zeroed (50257 = 785·64 + 17 at GPT-2's V).
+      - the saved-P dW of a backward that maps the vocab blocks to another split count than
+        its forward's (the tuning changed in between: tests/test_gpu_lmhead_boundary.py).
 No GPU, no oracle: the checks and their limits are what is under test.
 """
 import pytest
@@ -119,3 +121,58 @@ def test_checks_fail_broken_kernels(kind, N, H, V, mutate, out_bf16):
     if not out_bf16 and mutate.startswith("e_"):
         want.add("dh_token_max")  # fp32 outputs: dh's own check sees E at any softmax
     assert want <= set(bad), f"{mutate} on {kind} V={V}: failed {sorted(bad)}, expected {sorted(want)}"
+
+
+def _split_of_rows(V, nsplit, gran=4):
+    """The split of every vocab row: ll_split_t0 / ll_split_of of csrc/lmhead_loss.hip (32-row
+    vocab tiles, whole granules of `gran` tiles a split)."""
+    nvt = (V + 31) // 32
+    ngr = (nvt + gran - 1) // gran
+    t0 = [min(nvt, gran * (s * ngr // nsplit)) for s in range(nsplit)]
+    tile = torch.arange(V) // 32
+    sp = torch.zeros(V, dtype=torch.long)
+    for k in range(1, nsplit):
+        sp[tile >= t0[k]] = k
+    return sp
+
+
+def _emulate_saved_p_splits(h, w, y, g, fwd_splits, bwd_splits):
+    """The saved-P dW over vocab splits, dW[v] = Σ_t P[t, v]·hq[split(v)][t]: the forward keeps
+    P = bf16(exp(S − m_s)) with split s's own offset m_s (label entries −(1 − p_y)/e'_s) and the
+    records e'_s = e^(m_s − lse) for s < fwd_splits; the backward scales hq[s] = bf16(−g·e'_s·h)
+    and maps each vocab row to a split with ITS split count.  A record slot the forward never
+    wrote holds the last written split's value (the kindest stale content: a plausible scale)."""
+    hf, wf = h.float(), w.float()
+    s = hf @ wf.t()
+    lse = torch.logsumexp(s, -1, keepdim=True)
+    n = torch.arange(len(y))
+    V = w.shape[0]
+    sp_f = _split_of_rows(V, fwd_splits)
+    m = torch.stack([s[:, sp_f == k].max(-1).values for k in range(fwd_splits)], 1)   # [N, fwd_splits]
+    erec = torch.exp(m - lse)
+    p_op = torch.exp(s - m[:, sp_f])
+    py = torch.exp(s[n, y] - lse[:, 0])
+    p_op[n, y] = -(1.0 - py) / erec[n, sp_f[y]]
+    sp_b = _split_of_rows(V, bwd_splits).clamp_max(fwd_splits - 1)
+    dw = torch.zeros(V, h.shape[1], dtype=torch.float64)
+    for k in range(int(sp_b.max()) + 1):
+        rows = sp_b == k
+        hq = -g[:, None] * erec[:, k:k + 1] * hf
+        dw[rows] = _bf(p_op[:, rows]).t() @ _bf(hq)
+    return dw.float().double()
+
+
+@pytest.mark.parametrize("kind,N,H,V", CASES[:2])
+def test_checks_fail_a_backward_on_the_wrong_split_plan(kind, N, H, V):
+    """The drop-in backward under a split count that is not its forward's (the forward ran with
+    3 splits, the backward maps the vocab blocks and reads the records as for 8): the records'
+    scales meet P tiles of another split's offset.  dw_errors passes the emulation on the
+    forward's own plan and fails the mismatched one — a test that changes the tuning between
+    the two halves and applies these checks can see the bug."""
+    h, w, y = _operands(kind, N, H, V, N + V)
+    g = torch.randn(N, generator=torch.Generator().manual_seed(1))
+    t = C.fp64_truth(h, w, y, g)
+    good = C.dw_errors(_emulate_saved_p_splits(h, w, y, g.float(), 3, 3), t["dw"], y)
+    C.assert_within(good, f"3-split forward and backward, {kind}")
+    bad = C.failures(C.dw_errors(_emulate_saved_p_splits(h, w, y, g.float(), 3, 8), t["dw"], y))
+    assert {"dw_nonlabel_rel", "dw_row_max"} <= set(bad), bad

@@ -149,6 +149,12 @@ SIGNATURES = {
     "trlx_lmhead_logprobs_bwd_ex": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64,
                                              _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_vp, _c_int,
                                              _c_i64, _c_vp, _c_vp, _c_vp]),
+    "trlx_lmhead_logprobs_fwd_ex2": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64,
+                                              _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp,
+                                              ctypes.POINTER(_c_i64), _c_vp]),
+    "trlx_lmhead_logprobs_bwd_ex2": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64,
+                                              _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_i64, _c_int, _c_vp, _c_int,
+                                              _c_i64, _c_vp, _c_vp, _c_i64, _c_vp]),
     "trlx_lmhead_set_variant": (_c_int, [_c_int]),
     "trlx_lmhead_logprobs": (_c_int, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp,
                                       _c_int, _c_vp, _c_vp, _c_vp]),

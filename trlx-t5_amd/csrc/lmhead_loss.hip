@@ -1604,6 +1604,31 @@ static LlDwForm ll_dw_form(int f, int64_t H) {
     return f == 1 ? LlDwForm{1, 1, 64} : LlDwForm{2, 2, 128};
 }
 
+// The tuning values that fix how the saved P tiles and the per-(split, token) records e' are laid
+// out (and so how a backward must read them): read once per entry call.  The drop-in forward
+// hands them to its backward as a host-side token (trlx_lmhead_logprobs_fwd_ex2 -> _bwd_ex2), so
+// a knob that changes between the two calls cannot pair one plan's records with another's map.
+struct LlPlan {
+    int splits;  // "lmloss_splits": 0 auto, 1..kLLMaxSplits fixed
+    int form;    // the saved-P dW form, resolved (1 or 2)
+    int dw;      // "lmloss_dw": 0 auto, 1 recompute, 4 saved P
+};
+constexpr int64_t kLLPlanMagic = int64_t(0x4C50) << 32;  // "LP"
+static LlPlan ll_plan_now() {
+    const int f = g_ll_form;
+    return LlPlan{int(g_ll_splits), f ? f : kLLDwpForm, int(g_ll_dw)};
+}
+static int64_t ll_plan_token(const LlPlan& p) {
+    return kLLPlanMagic | int64_t(p.splits) | int64_t(p.form) << 8 | int64_t(p.dw) << 16;
+}
+static bool ll_plan_parse(int64_t token, LlPlan* p) {
+    const LlPlan q{int(token & 0xff), int(token >> 8 & 0xff), int(token >> 16 & 0xff)};
+    const bool ok = ll_plan_token(q) == token && q.splits >= 0 && q.splits <= kLLMaxSplits &&
+                    (q.form == 1 || q.form == 2) && (q.dw == 0 || q.dw == 1 || q.dw == 4);
+    if (ok) *p = q;
+    return ok;
+}
+
 // dW grid plan: whole rounds of workgroups own a vocab block each; the blocks of the last,
 // partial round are split over the tokens so that round is (nearly) full instead of a tail of
 // a few long workgroups (C2: 786 blocks on 256 CUs = 3 rounds + 18 blocks, the 18 split 14 ways).
@@ -1628,7 +1653,10 @@ static LlDwPlan ll_dw_plan(int64_t V, int vpw = kLLTokBlock, int parts = 1) {
 // 32-token tiles of the saved-P layout: the forward's 64-token blocks, whole
 static int ll_pntt(int64_t N) { return int(2 * ((N + kLLTokBlock - 1) / kLLTokBlock)); }
 // the saved P tiles (⌈V/64⌉ x 2⌈N/64⌉ x 4 KB: 0.62 GB at C2) and the per-(split, token) records
-static size_t ll_pbuf_bytes(int64_t N, int64_t V) { return size_t((V + 63) / 64) * ll_pntt(N) * 4096; }
+// — the 64-row blocks counted in whole 128-row dW blocks: the RW 2 form's last workgroup addresses
+// both 64-row halves of its block, so with an odd ⌈V/64⌉ its upper waves' P resource starts one
+// tile row past the last (rows >= V: read, never stored) and must still lie inside the region
+static size_t ll_pbuf_bytes(int64_t N, int64_t V) { return size_t((V + 127) / 128) * 2 * ll_pntt(N) * 4096; }
 static size_t ll_hq_bytes(int64_t N, int64_t H) { return size_t(kLLMaxSplits) * N * H * 2; }
 static size_t ll_erec_bytes(int64_t N) { return size_t(kLLMaxSplits) * N * 4; }
 // the dwp kernel addresses hq rows through a 32-bit buffer resource (ll_check's bound)
@@ -1738,7 +1766,7 @@ static int ll_dw(const LmLossArgs& a, hipStream_t s) {
 static int ll_setup(LmLossArgs& a, const void* hidden, int64_t ldh, const void* weight, int64_t ldw, int64_t N,
                     int64_t H, int64_t V, const int64_t* labels, int64_t lb, const int64_t* compact_mask,
                     void* lm_ws, void* dweight, int dw_dtype, int64_t lddw, LlWs& w, hipStream_t s, bool savep,
-                    bool fwd, bool pbuf, bool hq) {
+                    bool fwd, bool pbuf, bool hq, const LlPlan& pl) {
     int rc = ll_check(hidden, ldh, weight, ldw, N, H, V);
     if (rc) return rc;
     TRLX_REQUIRE(labels && lm_ws, TRLX_ERR_ARG, "NULL labels / workspace");
@@ -1751,14 +1779,14 @@ static int ll_setup(LmLossArgs& a, const void* hidden, int64_t ldh, const void* 
     a.V = int(V);
     a.labels = labels;
     a.lb = lb;
-    a.nsplit = g_ll_splits ? g_ll_splits : kLLMaxSplits;
-    a.nsplit_fixed = g_ll_splits != 0;
+    a.nsplit = pl.splits ? pl.splits : kLLMaxSplits;
+    a.nsplit_fixed = pl.splits != 0;
     a.ncu = ll_ncu();
-    const LlDwForm fm = ll_dw_form(savep ? (g_ll_form ? int(g_ll_form) : kLLDwpForm) : 1, H);
+    const LlDwForm fm = ll_dw_form(savep ? pl.form : 1, H);
     a.dw_vpw = fm.vpw;
     a.dw_hsp = savep ? fm.hsp : 1;
-    // split granules of the dW vocab block (>= 4 tiles: the drop-in forward and backward agree
-    // whatever the plan; the tuning must not change between them)
+    // split granules of the dW vocab block (>= 4 tiles, whatever the plan); the split count and
+    // the form are the caller's LlPlan: the drop-in backward's is its forward's
     a.sgran = std::max(4, fm.vpw / kLLRows);
     const LlDwPlan dp = ll_dw_plan(V, fm.vpw, a.dw_hsp);
     a.dw_full = dp.full;
@@ -1857,7 +1885,7 @@ static int ll_ppo_loss(LmLossArgs& a, const void* hidden, int64_t ldh, const voi
                  (long long)lm_bytes, (long long)N, (long long)H, (long long)V);
     const bool savep = ll_savep_plan(N, H, V, lm_bytes);
     int rc = ll_setup(a, hidden, ldh, weight, ldw, N, H, V, labels, 1, mask, lm_workspace, dweight, dw_dtype, lddw, w,
-                      s, savep, true, savep, savep);
+                      s, savep, true, savep, savep, ll_plan_now());
     if (rc) return rc;
     Workspace ws;
     carve_ppo_workspace(workspace, B, T, &ws);
@@ -1947,14 +1975,18 @@ extern "C" int trlx_ppo_loss_from_hidden_split(
 // passes in all) instead of recomputing S (k_lmloss_dw, 4).
 static int ll_dropin_fwd(const void* hidden, int64_t ldh, const void* weight, int64_t ldw, int64_t N, int64_t H,
                          int64_t V, const int64_t* labels, int64_t lb, const int64_t* mask, void* lp_out, int lp_dtype,
-                         float* lse_out, float* e_out, void* lm_workspace, void* saved, hipStream_t s) {
+                         float* lse_out, float* e_out, void* lm_workspace, void* saved, int64_t* plan_out,
+                         hipStream_t s) {
+    // one read of the knobs for the whole call; the token tells the backward what was read
+    const LlPlan pl = ll_plan_now();
+    if (plan_out) *plan_out = ll_plan_token(pl);
     if (N == 0) return TRLX_OK;
     LmLossArgs a = {};
     LlWs w;
     TRLX_REQUIRE(lp_out && lse_out && e_out, TRLX_ERR_ARG, "NULL lp / lse / E output");
     TRLX_REQUIRE(lp_dtype == TRLX_F32 || lp_dtype == TRLX_BF16, TRLX_ERR_DTYPE, "lp dtype");
     int rc = ll_setup(a, hidden, ldh, weight, ldw, N, H, V, labels, lb, mask, lm_workspace, nullptr, TRLX_F32, H,
-                      w, s, saved != nullptr, true, false, false);
+                      w, s, saved != nullptr, true, false, false, pl);
     if (rc) return rc;
     if (saved) ll_saved_carve(saved, N, V, &a.pbuf, &a.erec);  // the forward stores P; the combine e' and the label patch
     a.mode = kLLFwd;
@@ -1972,7 +2004,12 @@ static int ll_dropin_bwd(const void* hidden, int64_t ldh, const void* weight, in
                          int64_t V, const int64_t* labels, int64_t lb, const int64_t* mask, const void* grad,
                          int grad_dtype, const float* lse, const float* e, void* dhidden, int64_t lddh, int dh_dtype,
                          void* dweight, int dw_dtype, int64_t lddw, void* lm_workspace, const void* saved,
-                         hipStream_t s) {
+                         const int64_t* plan, hipStream_t s) {
+    // the forward's plan (its token), or without one the knobs as they are now (the caller
+    // then answers for them being the forward's)
+    LlPlan pl = ll_plan_now();
+    TRLX_REQUIRE(!plan || ll_plan_parse(*plan, &pl), TRLX_ERR_ARG,
+                 "plan %lld is not a token of trlx_lmhead_logprobs_fwd_ex2", plan ? (long long)*plan : 0LL);
     if (N == 0) return TRLX_OK;
     LmLossArgs a = {};
     LlWs w;
@@ -1984,11 +2021,11 @@ static int ll_dropin_bwd(const void* hidden, int64_t ldh, const void* weight, in
     TRLX_REQUIRE(lddh % 4 == 0 && lddh >= H && lddw >= H, TRLX_ERR_STRIDE, "gradient row strides");
     // the saved-P dW pass where the forward kept P (and the scaled rows fit the 2-GB addressing);
     // else the recompute plan, which needs nothing from the forward but lse and E
-    const bool savep = saved != nullptr && dweight != nullptr && ll_hq_fits(N, H) && g_ll_dw != 1;
+    const bool savep = saved != nullptr && dweight != nullptr && ll_hq_fits(N, H) && pl.dw != 1;
     // the forward's compaction again (launch_order is a stable, deterministic order: the same
     // compact token indices as the forward's records)
     int rc = ll_setup(a, hidden, ldh, weight, ldw, N, H, V, labels, lb, mask, lm_workspace, dweight, dw_dtype, lddw,
-                      w, s, savep, false, false, true);
+                      w, s, savep, false, false, true, pl);
     if (rc) return rc;
     if (savep) {  // the forward's P and e' in; the scaled h rows (w.hq) out
         ll_saved_carve(const_cast<void*>(saved), N, V, &a.pbuf, &a.erec);
@@ -2014,7 +2051,7 @@ extern "C" int trlx_lmhead_logprobs_fwd_saved(const void* hidden, int64_t ldh, c
                                               void* lp_out, int lp_dtype, float* lse_out, float* e_out,
                                               void* lm_workspace, void* stream) {
     return ll_dropin_fwd(hidden, ldh, weight, ldw, N, H, V, labels, lb, nullptr, lp_out, lp_dtype, lse_out, e_out,
-                         lm_workspace, nullptr, (hipStream_t)stream);
+                         lm_workspace, nullptr, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int trlx_lmhead_logprobs_bwd(const void* hidden, int64_t ldh, const void* weight, int64_t ldw, int64_t N,
@@ -2023,7 +2060,8 @@ extern "C" int trlx_lmhead_logprobs_bwd(const void* hidden, int64_t ldh, const v
                                         int dh_dtype, void* dweight, int dw_dtype, int64_t lddw, void* lm_workspace,
                                         void* stream) {
     return ll_dropin_bwd(hidden, ldh, weight, ldw, N, H, V, labels, lb, nullptr, grad, grad_dtype, lse, e, dhidden,
-                         lddh, dh_dtype, dweight, dw_dtype, lddw, lm_workspace, nullptr, (hipStream_t)stream);
+                         lddh, dh_dtype, dweight, dw_dtype, lddw, lm_workspace, nullptr, nullptr,
+                         (hipStream_t)stream);
 }
 
 extern "C" int trlx_lmhead_logprobs_fwd_ex(const void* hidden, int64_t ldh, const void* weight, int64_t ldw,
@@ -2031,7 +2069,7 @@ extern "C" int trlx_lmhead_logprobs_fwd_ex(const void* hidden, int64_t ldh, cons
                                            const int64_t* mask, void* lp_out, int lp_dtype, float* lse_out,
                                            float* e_out, void* lm_workspace, void* saved, void* stream) {
     return ll_dropin_fwd(hidden, ldh, weight, ldw, N, H, V, labels, lb, mask, lp_out, lp_dtype, lse_out, e_out,
-                         lm_workspace, saved, (hipStream_t)stream);
+                         lm_workspace, saved, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int trlx_lmhead_logprobs_bwd_ex(const void* hidden, int64_t ldh, const void* weight, int64_t ldw,
@@ -2041,7 +2079,27 @@ extern "C" int trlx_lmhead_logprobs_bwd_ex(const void* hidden, int64_t ldh, cons
                                            int dw_dtype, int64_t lddw, void* lm_workspace, const void* saved,
                                            void* stream) {
     return ll_dropin_bwd(hidden, ldh, weight, ldw, N, H, V, labels, lb, mask, grad, grad_dtype, lse, e, dhidden, lddh,
-                         dh_dtype, dweight, dw_dtype, lddw, lm_workspace, saved, (hipStream_t)stream);
+                         dh_dtype, dweight, dw_dtype, lddw, lm_workspace, saved, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int trlx_lmhead_logprobs_fwd_ex2(const void* hidden, int64_t ldh, const void* weight, int64_t ldw,
+                                            int64_t N, int64_t H, int64_t V, const int64_t* labels, int64_t lb,
+                                            const int64_t* mask, void* lp_out, int lp_dtype, float* lse_out,
+                                            float* e_out, void* lm_workspace, void* saved, int64_t* plan_out,
+                                            void* stream) {
+    TRLX_REQUIRE(plan_out, TRLX_ERR_ARG, "NULL plan_out");
+    return ll_dropin_fwd(hidden, ldh, weight, ldw, N, H, V, labels, lb, mask, lp_out, lp_dtype, lse_out, e_out,
+                         lm_workspace, saved, plan_out, (hipStream_t)stream);
+}
+
+extern "C" int trlx_lmhead_logprobs_bwd_ex2(const void* hidden, int64_t ldh, const void* weight, int64_t ldw,
+                                            int64_t N, int64_t H, int64_t V, const int64_t* labels, int64_t lb,
+                                            const int64_t* mask, const void* grad, int grad_dtype, const float* lse,
+                                            const float* e, void* dhidden, int64_t lddh, int dh_dtype, void* dweight,
+                                            int dw_dtype, int64_t lddw, void* lm_workspace, const void* saved,
+                                            int64_t plan, void* stream) {
+    return ll_dropin_bwd(hidden, ldh, weight, ldw, N, H, V, labels, lb, mask, grad, grad_dtype, lse, e, dhidden, lddh,
+                         dh_dtype, dweight, dw_dtype, lddw, lm_workspace, saved, &plan, (hipStream_t)stream);
 }
 
 #if LL_STAMP

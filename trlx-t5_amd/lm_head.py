@@ -21,6 +21,8 @@ per token, and the backward forms dh_t = g_t·(W[y_t] − E_t) and dW = Σ_t g_t
   "auto"       saved_p when dW is needed and the P buffer can be allocated (a
                torch.cuda.OutOfMemoryError on it falls back to recompute), else recompute
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -70,21 +72,27 @@ class _LmHeadLogprobs(torch.autograd.Function):
         # the P tiles only serve the dW pass: a frozen lm_head keeps nothing of size N·V
         saved = _savep_buffer(N, H, V, dev, plan) if ctx.needs_input_grad[1] else None
         ws = torch.empty(_lib.query("trlx_lmhead_loss_workspace_bytes", N, H, V), dtype=torch.uint8, device=dev)
-        _lib.call("trlx_lmhead_logprobs_fwd_ex", h.data_ptr(), h.stride(0), w.data_ptr(), w.stride(0), N, H, V,
+        # the split plan the forward ran with (a host-side token): the backward takes it instead of
+        # reading the process-wide tuning again, which may have changed by then
+        plan_token = ctypes.c_int64(0)
+        _lib.call("trlx_lmhead_logprobs_fwd_ex2", h.data_ptr(), h.stride(0), w.data_ptr(), w.stride(0), N, H, V,
                   y.data_ptr(), 1, _lib.ptr(mask), lp.data_ptr(), _lib.dtype_code(lp), lse.data_ptr(), e.data_ptr(),
-                  ws.data_ptr(), _lib.ptr(saved), _lib.stream_of(h))
+                  ws.data_ptr(), _lib.ptr(saved), ctypes.byref(plan_token), _lib.stream_of(h))
         del ws  # the forward's partials: free once the combine has run (stream-ordered)
         # the P region rides save_for_backward, so autograd frees it with the graph's other saved
         # tensors once the backward has run (not when the last reference to lp goes); the
         # backward only reads it, so a retain_graph second backward sees the same bytes
-        ctx.save_for_backward(h, w, y, lse, e, saved)
-        ctx.mask = mask
+        # the mask too: P and the records are indexed by the compact order it gave the forward, so
+        # an in-place edit of a caller's own int64 mask before the backward must raise, as for any
+        # saved tensor
+        ctx.save_for_backward(h, w, y, lse, e, mask, saved)
+        ctx.plan_token = plan_token.value
         ctx.shapes = (hidden.shape, hidden.dtype, weight.shape, weight.dtype)
         return lp.view(labels.shape)
 
     @staticmethod
     def backward(ctx, grad_lp):
-        h, w, y, lse, e, saved_p = ctx.saved_tensors
+        h, w, y, lse, e, mask, saved_p = ctx.saved_tensors
         hshape, hdt, wshape, wdt = ctx.shapes
         N, H, V = h.shape[0], h.shape[1], w.shape[0]
         dev = h.device
@@ -101,11 +109,11 @@ class _LmHeadLogprobs(torch.autograd.Function):
         dw = torch.empty((V, H), dtype=wdt, device=dev) if need_w else None
         ws = torch.empty(_lib.query("trlx_lmhead_loss_bwd_workspace_bytes", N, H, V), dtype=torch.uint8, device=dev)
         saved = saved_p if need_w else None
-        _lib.call("trlx_lmhead_logprobs_bwd_ex", h.data_ptr(), h.stride(0), w.data_ptr(), w.stride(0), N, H, V,
-                  y.data_ptr(), 1, _lib.ptr(ctx.mask), g.data_ptr(), _lib.dtype_code(g), lse.data_ptr(), e.data_ptr(),
+        _lib.call("trlx_lmhead_logprobs_bwd_ex2", h.data_ptr(), h.stride(0), w.data_ptr(), w.stride(0), N, H, V,
+                  y.data_ptr(), 1, _lib.ptr(mask), g.data_ptr(), _lib.dtype_code(g), lse.data_ptr(), e.data_ptr(),
                   _lib.ptr(dh), H if dh is None else dh.stride(0), _lib.dtype_code(dh if dh is not None else dw),
                   _lib.ptr(dw), _lib.dtype_code(dw if dw is not None else dh), H if dw is None else dw.stride(0),
-                  ws.data_ptr(), _lib.ptr(saved), _lib.stream_of(h))
+                  ws.data_ptr(), _lib.ptr(saved), ctx.plan_token, _lib.stream_of(h))
         return (dh.view(hshape) if need_h else None), (dw.view(wshape) if need_w else None), None, None, None, None
 
 
@@ -119,15 +127,20 @@ def lm_head_logprobs(hidden: torch.Tensor, weight: torch.Tensor, labels: torch.T
     GRAD_HIDDEN_SIZES the backward runs lmhead_loss.hip's dh / dW passes (no [.., V] logits;
     `plan`: the dW pass from the forward's saved bf16 P or recomputed, see the module doc);
     other H take hipBLASLt bf16 logits + logprobs_from_logits (the reference's structure).
-    mask (optional, labels' shape, any integer / bool dtype): tokens with mask == 0 get lp = 0
-    and zero gradient, and the fused path compacts them out of its MFMA passes — for a consumer
-    that multiplies lp by the same mask (PPOConfig.loss: ppo_models.py:150-199), where their lp
-    never matters."""
+    mask (optional, labels' shape, bool or any integer / floating dtype): a token is live where
+    mask != 0 (a fractional weight such as 0.5 keeps it) and skipped where mask == 0 — skipped
+    tokens get lp = 0 and zero gradient, and the fused path compacts them out of its MFMA passes —
+    for a consumer that multiplies lp by the same mask (PPOConfig.loss: ppo_models.py:150-199),
+    where their lp never matters.  The mask is part of what the backward needs: an int64 mask on
+    the device is kept by reference, and editing it in place before backward() raises autograd's
+    in-place error; any other mask is converted, so the call keeps a private copy."""
     if plan not in PLANS:
         raise ValueError(f"plan must be one of {PLANS}, not {plan!r}")
     if mask is not None:
         if tuple(mask.shape) != tuple(labels.shape):
             raise ValueError(f"mask must have labels' shape {tuple(labels.shape)}, got {tuple(mask.shape)}")
+        if mask.dtype != torch.int64:  # live = mask != 0, not the truncation of a float weight
+            mask = mask != 0
         mask = mask.to(device=labels.device, dtype=torch.int64).reshape(-1).contiguous()
     _lib.require_cuda(hidden, weight, labels)
     if hidden.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16:

@@ -931,7 +931,11 @@ class PPOHotPath:
         the PREVIOUS batch's (loss, stats, dhidden, dweight, dvalues) or None on the first call
         (valid until the next call); pipeline_flush() runs the last pending loss.  The GAE keeps
         its own launch: the loss side is ~2 ms of MFMA work, against which a 7-us launch is
-        noise, and no launch of it can host the rollout waves."""
+        noise, and no launch of it can host the rollout waves.  The pending batch's new_hidden
+        and new_weight are held by reference until its loss runs: an in-place edit of either in
+        between is refused at the top of the next call (or of pipeline_flush), before anything
+        is launched or swapped — the pending batch stays; pipeline_discard() drops it."""
+        self._pending_operands_unmodified("pipeline_step_from_hidden")
         self._check_hidden(hidden, weight, ref_hidden, ref_weight)
         w_new = weight if new_weight is None else new_weight
         # the loss side's checks now, before any launch of this batch (a failure inside the next
@@ -943,18 +947,13 @@ class PPOHotPath:
             self._experience_lmhead(hidden, weight, ref_hidden, ref_weight, labels, lengths, s, route)
 
         def loss(p, fold):
-            # batch k's loss runs in call k+1: its lm_head weight must still be the one it was
-            # submitted with (an in-place optimizer.step in between would pair hidden(k) with W(k+1))
-            if p["new_weight"]._version != p["weight_version"]:
-                raise RuntimeError("pipeline_step_from_hidden: new_weight was modified in place between the call "
-                                   "that submitted the batch and the one running its loss; step the optimizer "
-                                   "after pipeline_flush(), or pass a copy")
             return self.policy_loss_from_hidden(p["new_hidden"], p["new_weight"], p["labels"], p["values"],
                                                 p["old_values"], mask=p["mask"], grad_dtype=p["grad_dtype"],
                                                 route=p["loss_route"])
 
         return self._pipeline(experience, loss, dict(new_hidden=new_hidden, new_weight=w_new, grad_dtype=grad_dtype,
-                                                     loss_route=loss_route, weight_version=w_new._version),
+                                                     loss_route=loss_route, weight_version=w_new._version,
+                                                     hidden_version=new_hidden._version),
                               labels, old_values, values, scores, lengths, mask, group, fold=False)
 
     def _pipeline(self, experience, loss, payload, labels, old_values, values, scores, lengths, mask, group, fold):
@@ -1002,12 +1001,23 @@ class PPOHotPath:
                              mask=mask)
         return out
 
-    def pipeline_flush(self):
-        """Run the pending loss of the last pipeline_step(_from_hidden) batch; returns its outputs
-        (or None)."""
-        prev, self._pending = self._pending, None
-        if prev is None:
-            return None
+    def _pending_operands_unmodified(self, what):
+        """Batch k's loss runs in call k+1 (or in pipeline_flush) on the new_hidden / new_weight
+        it was submitted with, held by reference: an in-place edit in between (an optimizer.step)
+        would pair hidden(k) with W(k+1).  Checked before the call launches or swaps anything,
+        so a refusal leaves the pending batch and every buffer as they were."""
+        p = self._pending
+        if p is None or "weight_version" not in p:
+            return
+        for name, ver in (("new_weight", "weight_version"), ("new_hidden", "hidden_version")):
+            if p[name]._version != p[ver]:
+                raise RuntimeError(f"{what}: the pending batch's {name} was modified in place between the call "
+                                   f"that submitted it and the one running its loss; step the optimizer after "
+                                   f"pipeline_flush(), or pass a copy (pipeline_discard() drops the pending batch)")
+
+    def _retire_pending(self, prev):
+        """The pending batch's buffers selected, its all-reduce joined and, under the lag
+        schedule, its score moments merged: what precedes its loss when no next batch follows."""
         self._use_split(True, prev["buf"])
         self.lp_old, self.ref_lp = self._lp_bufs[prev["buf"]]
         self._resolve_allreduce()  # nothing left to hide it behind
@@ -1016,7 +1026,27 @@ class PPOHotPath:
             _lib.call("trlx_score_moments_merge", st, st, self._mom_bufs[prev["buf"]].data_ptr(),
                       torch.cuda.current_stream(self.device).cuda_stream)
             self._lag = False
+
+    def pipeline_flush(self):
+        """Run the pending loss of the last pipeline_step(_from_hidden) batch; returns its outputs
+        (or None)."""
+        self._pending_operands_unmodified("pipeline_flush")
+        prev, self._pending = self._pending, None
+        if prev is None:
+            return None
+        self._retire_pending(prev)
         return prev["loss"](prev, None)
+
+    def pipeline_discard(self):
+        """Drop the pending batch without running its loss — the way out after an in-place edit
+        of its new_hidden / new_weight was refused: its experience outputs (lp_old, ref_lp,
+        rewards, ...) stay readable as after pipeline_flush(), and the next
+        pipeline_step(_from_hidden) starts a new pipeline.  Returns whether a batch was pending."""
+        prev, self._pending = self._pending, None
+        if prev is None:
+            return False
+        self._retire_pending(prev)
+        return True
 
     def step(self, logits, ref_logits, new_logits, labels, old_values, values, scores,
              lengths: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, group=None,
