@@ -476,6 +476,35 @@ int trlx_ilql_sample(const void* logits, int64_t ld_logits, const void* tq0, int
                      int64_t V, float beta, int top_k, float temperature, const float* u,
                      int64_t* out_ids, int64_t* finished, int64_t eos, void* stream);
 
+/* ---------------------------------------------------------------- PPO rollout sampling step
+ * One decode step of HF generate's sample path (transformers 4.21; ppo_orchestrator.py:76 with
+ * PPOConfig.gen_kwargs) per row b, x = logits[b] in fp32:
+ *   x[eos] = -inf while cur_len < min_length (eos given);
+ *   top-k: keep x >= the k-th largest x, k = min(max(top_k, min_tokens_to_keep), V), ties at
+ *   the threshold kept, top_k = 0 off;
+ *   top-p (only when top_p < 1): w = exp((x - max x) / temperature) over the top-k survivors,
+ *   W = sum w; x is kept iff the mass of the survivors strictly above it is <= top_p * W (the
+ *   token that crosses top_p stays) or it is among the min_tokens_to_keep largest; every tie
+ *   at the nucleus boundary is kept (HF keeps the one its sort placed first);
+ *   out_ids[b] = the inverse CDF of w over the kept at u[b], vocab-index order (u from the
+ *   caller's generator replaces torch.multinomial's draw);
+ *   unfinished[b] == 0: out_ids[b] = pad and the row does no other work; else
+ *   unfinished[b] &= out_ids[b] != eos.
+ * out_logprobs[b] = log_softmax(logits[b])[out_ids[b]] on the unmodified row (no eos
+ * suppression, no temperature); out_min_kept[b] = the smallest kept x, exactly;
+ * out_kept_count[b] = the number of kept tokens.  A finished row writes 0 to those three; so
+ * does a row with no finite logit left, which returns pad (HF raises there); pad = -1 writes
+ * token 0 in both cases.
+ * logits: [B, V] of dtype (TRLX_F32 / TRLX_BF16), row stride ld_logits, unit column stride;
+ * eos_token_id / pad_token_id in [0, V) or -1 for none; unfinished: int64 [B] in/out or NULL.
+ * Requires temperature > 0, top_p > 0, top_k >= 0, min_tokens_to_keep >= 1 (TRLX_ERR_ARG);
+ * B = 0 is a no-op.  Stream-ordered: no host synchronisation, no allocation. */
+int trlx_ppo_sample(const void* logits, int64_t ld_logits, int dtype, int64_t B, int64_t V,
+                    float temperature, int top_k, float top_p, int min_tokens_to_keep,
+                    int64_t cur_len, int64_t min_length, int64_t eos_token_id, int64_t pad_token_id,
+                    const float* u, int64_t* out_ids, float* out_logprobs, float* out_min_kept,
+                    int32_t* out_kept_count, int64_t* unfinished, void* stream);
+
 /* ---------------------------------------------------------------- §8f: device-resident rollout store
  * Row copy between padded columnar [rows, W] buffers — replaces the reference's
  * `.cpu()` of the experience tensors, per-sample PPORLElement lists and the pad_sequence

@@ -3,13 +3,16 @@
 Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
   logprobs_from_logits, whiten, get_global_statistics, RunningMoments, flatten_dict
       trlx/utils/modeling.py
-  PPOConfig (.get_advantages_and_returns, .loss, .loss_from_logits),
+  PPOConfig (.get_advantages_and_returns, .loss, .loss_from_logits, .sample_step),
   AdaptiveKLController, FixedKLController
       trlx/model/nn/ppo_models.py
   kl_penalty_rewards, prepare_scores
       trlx/orchestrator/ppo_orchestrator.py:96-112,163-167
   ILQLConfig (.loss), ILQLBatch, ilql_sample_step (one decode step of generate)
       trlx/model/nn/ilql_models.py:52-116,296-316, trlx/data/ilql_types.py
+  ppo_sample_step — one rollout token of generate(**gen_kwargs): min length, temperature,
+      top-k, top-p, the draw, unfinished / pad, and the token's policy log-prob
+      trlx/orchestrator/ppo_orchestrator.py:76 (HF generate's sample path)
   lm_head_logprobs — fused lm_head GEMM (MFMA) + logprobs, logits never in HBM
   PPORolloutStorage, PPORLElement, PPORLBatch
       trlx/pipeline/ppo_pipeline.py, trlx/data/ppo_types.py (device-resident store)
@@ -27,6 +30,7 @@ from .ppo import (STATS_KEYS, AdaptiveKLController, FixedKLController, PPOConfig
 from .lm_head import lm_head_logprobs
 from .rollout_store import PPORLBatch, PPORLElement, PPORolloutStorage
 from .ilql import ILQL_LOSS_KEYS, ILQLBatch, ILQLConfig, ILQLHotPath, ilql_sample_step
+from .sampling import ppo_sample_step
 from .control import PPOControlState
 from .step import PPOHotPath
 from .comm import RcclComm
@@ -36,7 +40,8 @@ __all__ = [
     "logprobs_from_logits", "whiten", "get_global_statistics", "RunningMoments", "flatten_dict", "moments",
     "grad_buffer_like", "PPOConfig", "AdaptiveKLController", "FixedKLController", "kl_penalty_rewards",
     "prepare_scores", "stats_dict", "STATS_KEYS", "PPOHotPath", "load_library",
-    "ILQLConfig", "ILQLBatch", "ILQLHotPath", "ILQL_LOSS_KEYS", "ilql_sample_step", "PPORolloutStorage",
+    "ILQLConfig", "ILQLBatch", "ILQLHotPath", "ILQL_LOSS_KEYS", "ilql_sample_step", "ppo_sample_step",
+    "PPORolloutStorage",
     "PPORLElement", "PPORLBatch", "lm_head_logprobs", "PPOControlState",
     "RcclComm", "shift_tokens_right", "get_model_inputs",
 ]

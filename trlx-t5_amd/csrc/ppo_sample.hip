@@ -1,0 +1,576 @@
+// Vocab-axis sampling step of PPO rollout generation, one workgroup per row: the logits
+// processors and the draw of HF generate's sample path (transformers 4.21, as called by
+// ppo_orchestrator.py:76 / ppo_models.py:620-622 with PPOConfig.gen_kwargs), per row b:
+//
+//   x      = logits[b, :] in fp32;  x[eos] = -inf while cur_len < min_length
+//   keep   = x >= k-th largest x                       (top-k; ties at the threshold kept)
+//   w      = exp((x - max x) / T) over the kept,  W = sum w
+//   keep  &= mass{x' > x} <= top_p * W  or  x among the min_tokens_to_keep largest
+//            (top-p, the 4.21 rule: the token that crosses top_p stays; every tie at the
+//            nucleus boundary is kept, where HF keeps whichever its sort placed first)
+//   token  = inverse CDF of w over the kept at u[b], vocab-index order
+//   token  = unfinished ? token : pad;  unfinished &= token != eos
+//   logprob = log_softmax(logits[b, :])[token]          (the unmodified row)
+//
+// Filtering is defined on the order of x (division by T > 0 is monotone).  The row is held
+// in VGPRs as in ilql_sample.hip (16-B non-temporal buffer loads on the rows' 256-B line
+// shift).  Nothing is sorted: the k-th largest value and the nucleus threshold are each the
+// result of a search over order-preserving uint32 keys.  Fast path: a candidate list in
+// LDS (the values above a lower bound of the n-th largest, n = k or a seed of 128 for
+// top-p alone) is ranked by one thread per candidate.  Rows that defeat it (ties, k above
+// the thread count, a nucleus wider than the list) take 32-step block-wide bisections: on
+// counts for top-k, on mass for top-p.  Every block reduction runs in a fixed order.
+#include "common.h"
+
+namespace trlx {
+
+struct PpoSampleArgs {
+    const void* logits;  // [B, V] rows of ld_logits
+    int64_t ld_logits;
+    int64_t V;
+    float scale;         // log2(e) / temperature
+    float top_p;
+    int top_k;           // 0 = off, else already clamped to [min_keep, V]
+    int min_keep;        // min_tokens_to_keep, <= V
+    int suppress_eos;    // cur_len < min_length and eos given
+    int64_t eos, pad;    // -1 = none
+    const float* u;      // [B] uniforms in [0, 1)
+    int64_t* out_ids;    // [B]
+    float* out_lp;       // [B] log_softmax(logits)[id]
+    float* out_min;      // [B] smallest kept logit
+    int* out_cnt;        // [B] number of kept tokens
+    int64_t* unfinished; // [B] in/out (0/1), NULL = all live
+};
+
+// order-preserving float -> uint32 (a larger float has a larger key) and back
+__device__ __forceinline__ uint32_t fkey(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float fkey_inv(uint32_t k) {  // NaN for keys no float maps to
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+constexpr int kPsCandCap = 512;   // candidate list in LDS, one per thread at most
+constexpr int kPsSeed = 128;      // list size aimed at when top-p runs without top-k
+
+template <class DT, int NV, int NT>
+__global__ __launch_bounds__(NT) void k_ppo_sample(PpoSampleArgs a) {
+    constexpr int kWaves = NT / kWave;
+    typedef typename DT::elem_t E;
+    constexpr int EPV = DT::kEPV;
+    constexpr int NSEG = NV + 2;  // index-order segments: head elements, vector steps, tail
+    static_assert(kPsCandCap <= NT, "one candidate per thread");
+    __shared__ float sh_red[kWaves];
+    __shared__ double sh_sum[kWaves];
+    __shared__ float sh_red3[kWaves];
+    __shared__ int cnt[2][kWaves];           // bisection counts / masses (double-buffered)
+    __shared__ float mass[2][kWaves];
+    __shared__ float seg_tot[NSEG][kWaves];
+    __shared__ float seg_pre[NSEG + 1];
+    __shared__ int s_pick[3];                // segment, winning thread, token
+    __shared__ float s_rem, s_lp;
+    __shared__ int w_cnt[kWaves];            // kept count / smallest kept logit per wave
+    __shared__ float w_min[kWaves];
+    __shared__ float t_max[NT];              // per-thread maximum
+    __shared__ __align__(16) float c_val[kPsCandCap + 4];  // candidates: every x >= t0
+    __shared__ __align__(16) float c_w[kPsCandCap + 4];    // their weights
+    __shared__ int c_n, s_bad;
+    __shared__ uint32_t s_minkey;
+    __shared__ float s_thr;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int b = blockIdx.x;
+    const int64_t V = a.V;
+    const int64_t padtok = a.pad < 0 ? 0 : a.pad;
+    auto finish = [&](int64_t tok, float lp, float mn, int n) {  // one thread
+        a.out_ids[b] = tok;
+        a.out_lp[b] = lp;
+        a.out_min[b] = mn;
+        a.out_cnt[b] = n;
+    };
+    if (a.unfinished && a.unfinished[b] == 0) {  // a finished row emits pad and stays finished
+        if (tid == 0) finish(padtok, 0.f, 0.f, 0);
+        return;
+    }
+
+    const E* x = reinterpret_cast<const E*>(a.logits) + b * a.ld_logits;
+    const RowSplit<DT> s(x, V);
+    const int nvec = int(s.nvec);
+    const int shift = line_shift(x + s.head);
+    const int voff = (tid - shift) * 16;
+    const __amdgpu_buffer_rsrc_t rin = make_rsrc(x + s.head, uint32_t(nvec) * 16u);
+    auto valid = [&](int k) { return unsigned(tid - shift + k * NT) < unsigned(nvec); };
+    // recomputed at every use (laundered): CSE would keep NV 64-bit indices live across the kernel
+    auto index_of = [&](int k, int e) {
+        return s.head + int64_t(launder_int(tid - shift) + k * NT) * EPV + e;
+    };
+
+    // ---- logits row -> registers (out-of-row entries -inf); <= 1 edge element per thread
+    float f[NV][EPV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const vec4u v = __builtin_amdgcn_raw_buffer_load_b128(rin, launder_int(voff) + k * NT * 16, 0, kAuxNT);
+        DT::unpack(v, f[k]);
+    }
+    int64_t je = -1;  // head element -> threads [0, head); tail -> the last `tail` threads
+    if (tid < s.head) je = tid;
+    else if (tid >= NT - s.tail) je = s.tail0 + (tid - (NT - s.tail));
+    float fe = je >= 0 ? DT::load1(x, je) : -INFINITY;
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+#pragma unroll
+        for (int e = 0; e < EPV; ++e)
+            if (!valid(k)) f[k][e] = -INFINITY;
+
+    // ---- log_softmax statistics of the unmodified row: exponentials relative to the wave
+    // maximum, then one exchange of (wave max, wave sum) pairs — one barrier
+    float m = fe;
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) m = fmaxf(m, f[k][e]);
+    m = wave_max(m);
+    const float mo = m == -INFINITY ? 0.f : m * kLog2e;
+    // (summed in fp64: when one token holds nearly all the mass the sum is 1 + a small rest,
+    // and the rest is the token's log-prob — fp32 partial sums would round it away)
+    double sum = exp2_fast(__builtin_fmaf(fe, kLog2e, -mo));
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) sum += double(exp2_fast(__builtin_fmaf(f[k][e], kLog2e, -mo)));
+        __builtin_amdgcn_sched_barrier(0);  // one step's exponentials in flight, not the row's
+    }
+    sum = wave_sum_d(sum);
+    if (lane == 0) {
+        sh_red[wv] = m;
+        sh_sum[wv] = sum;
+    }
+    __syncthreads();
+    m = sh_red[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) m = fmaxf(m, sh_red[w]);
+    sum = 0.0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w)
+        if (sh_red[w] != -INFINITY) sum += sh_sum[w] * double(exp2_fast((sh_red[w] - m) * kLog2e));
+    // log_softmax(x)[j] = (x_j - m) - log(sum): the difference first, so a token that holds
+    // nearly all the mass keeps a log-prob near 0 to fp32 relative precision
+    const float row_max = m, log_sum = float(log(sum));
+
+    // ---- min length: the thread that holds x[eos] drops it; the row maximum again
+    float xmax = m;
+    if (a.suppress_eos) {  // block-uniform
+        if (je == a.eos) fe = -INFINITY;
+        int ks = -1, es = -1;
+        if (a.eos >= s.head && a.eos < s.tail0) {
+            const int64_t q = a.eos - s.head;
+            const int slot = int(q / EPV) + shift;  // vector i sits in thread (i + shift) % NT, step (i + shift) / NT
+            if (slot % NT == tid) {
+                ks = slot / NT;
+                es = int(q % EPV);
+            }
+        }
+        float mx = fe;
+#pragma unroll
+        for (int k = 0; k < NV; ++k)
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) {
+                if (k == ks && e == es) f[k][e] = -INFINITY;
+                mx = fmaxf(mx, f[k][e]);
+            }
+        xmax = block_max(mx, sh_red3);
+    }
+    if (xmax == -INFINITY) {  // no finite logit left (HF's multinomial would raise): pad, nothing kept
+        if (tid == 0) {
+            finish(padtok, 0.f, 0.f, 0);
+            if (a.unfinished && a.eos >= 0) a.unfinished[b] = padtok != a.eos ? 1 : 0;
+        }
+        return;
+    }
+
+    // (from here on a slot outside the row or suppressed holds -inf, which no count or
+    // weight below can pick: no per-slot validity test is needed)
+    const float scale = a.scale;
+    auto weight_at = [&](float v, float xm) { return exp2_fast((v - xm) * scale); };  // exp((x - max) / T); 0 for -inf
+    auto weight = [&](float v) { return weight_at(v, xmax); };
+    // block-wide #(x >= cf) and mass{x >= lo}: per-thread partial, wave reduction, one LDS
+    // exchange summed in wave order by every thread (double-buffered: one barrier per call)
+    int par = 0;
+    auto count_ge = [&](float cf) {
+        int c = fe >= cf ? 1 : 0;
+#pragma unroll
+        for (int k = 0; k < NV; ++k)
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) c += f[k][e] >= cf ? 1 : 0;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, kWave);
+        if (lane == 0) cnt[par][wv] = c;
+        __syncthreads();
+        int tot = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) tot += cnt[par][w];
+        par ^= 1;
+        return tot;
+    };
+    auto mass_ge = [&](float lo) {
+        // (laundered maximum: inside a bisection loop the weights are loop-invariant, and
+        // hoisting them would hold the row twice in VGPRs)
+        float xm = xmax;
+        asm volatile("" : "+v"(xm));
+        float t = fe >= lo ? weight_at(fe, xm) : 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) t += f[k][e] >= lo ? weight_at(f[k][e], xm) : 0.f;
+            __builtin_amdgcn_sched_barrier(0);  // one step's exponentials in flight, not the row's
+        }
+        t = wave_sum(t);
+        if (lane == 0) mass[par][wv] = t;
+        __syncthreads();
+        float tot = 0.f;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) tot += mass[par][w];
+        par ^= 1;
+        return tot;
+    };
+    // the n-th largest x: bisection on the keys, MSB first — the largest key K with
+    // #(key >= K) >= n IS the n-th largest key.  The candidate is turned into a float, not
+    // every x into a key; float >= is monotone in the key, and candidates in the NaN key
+    // ranges (skipped) would count 0.  Fewer than n finite values: -inf, all of them kept.
+    auto nth_largest = [&](int n) {
+        uint32_t K = 0;
+#pragma unroll 1
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = K | (1u << bit);
+            const float cf = fkey_inv(cand);
+            if (cf != cf) continue;
+            if (count_ge(cf) >= n) K = cand;
+        }
+        return K > fkey(-INFINITY) ? fkey_inv(K) : -INFINITY;
+    };
+
+    const int top_k = a.top_k;
+    const bool nucleus = a.top_p < 1.f;
+    float thr = -INFINITY;  // keep x >= thr (and finite)
+    bool done = !(top_k > 0 && int64_t(top_k) < V) && !nucleus;  // nothing to filter
+    float w_all = 0.f;
+    if (!done && top_k == 0) w_all = mass_ge(-INFINITY);  // top-p alone: W over the whole row
+
+    // ---- candidate list.  t0 = the n-th largest of the per-thread maxima is a lower bound of
+    // the n-th largest x (n threads each own an x >= t0), so the values >= t0 — a few times n
+    // on real rows — hold the n largest.  With top-k (n = k) that is every survivor, and the
+    // nucleus is a subset of them.  With top-p alone (n = a seed) the list is an upper set
+    // of the row: the mass above a candidate is exact, and the nucleus lies inside the list
+    // iff the list's smallest value is not kept; otherwise the block-wide search runs.
+    int n0 = top_k > 0 ? top_k : (kPsSeed > a.min_keep ? kPsSeed : a.min_keep);
+    if (!done && n0 <= NT && int64_t(n0) < V) {
+        float mx = fe;
+#pragma unroll
+        for (int k = 0; k < NV; ++k)
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) mx = fmaxf(mx, f[k][e]);
+        t_max[tid] = mx;
+        if (tid == 0) {
+            c_n = 0;
+            s_bad = 0;
+            s_minkey = 0xffffffffu;
+        }
+        __syncthreads();
+        if (wv == 0) {
+            constexpr int R = NT / kWave;
+            float tv[R];
+#pragma unroll
+            for (int i = 0; i < R; ++i) tv[i] = t_max[lane + i * kWave];
+            // the top 16 key bits (sign, exponent, 7 mantissa bits) are enough for a lower
+            // bound: K <= the exact key, a few more candidates at most
+            uint32_t K = 0;
+            for (int bit = 31; bit >= 16; --bit) {
+                const uint32_t cand = K | (1u << bit);
+                const float cf = fkey_inv(cand);
+                int c = 0;
+#pragma unroll
+                for (int i = 0; i < R; ++i) c += __popcll(__ballot(tv[i] >= cf));
+                if (c >= n0) K = cand;
+            }
+            if (lane == 0) s_thr = K > fkey(-INFINITY) ? fkey_inv(K) : -INFINITY;
+        }
+        __syncthreads();
+        const float t0 = s_thr;
+        if (t0 != -INFINITY) {
+            auto append = [&](bool p, float v) {
+                const uint64_t mk = __ballot(p);
+                if (mk == 0) return;
+                const int leader = __ffsll((unsigned long long)mk) - 1;
+                int base = 0;
+                if (lane == leader) base = atomicAdd(&c_n, __popcll(mk));
+                base = __shfl(base, leader, kWave);
+                const int pos = base + __builtin_amdgcn_mbcnt_hi(uint32_t(mk >> 32),
+                                                                 __builtin_amdgcn_mbcnt_lo(uint32_t(mk), 0));
+                if (p && pos < kPsCandCap) c_val[pos] = v;
+            };
+            append(fe >= t0, fe);
+#pragma unroll
+            for (int k = 0; k < NV; ++k)
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) append(f[k][e] >= t0, f[k][e]);
+        }
+        __syncthreads();
+        const int n = c_n;
+        if (t0 != -INFINITY && n <= kPsCandCap) {  // block-uniform
+            if (tid < 4) {  // pad to whole float4s: -inf and zero weights never count
+                c_val[n + tid] = -INFINITY;
+                c_w[n + tid] = 0.f;
+            }
+            __syncthreads();
+            // every thread ranks at most one candidate against the whole list (LDS broadcast
+            // reads): the k-th largest is the value with #(>) < k <= #(>=) — exact, with ties
+            const bool own = tid < n;
+            const float vt = own ? c_val[tid] : -INFINITY;
+            int gt = 0, ge = 0;
+            for (int q = 0; q < n; q += 4) {
+                const float4 vq = *reinterpret_cast<const float4*>(&c_val[q]);
+                gt += (vq.x > vt) + (vq.y > vt) + (vq.z > vt) + (vq.w > vt);
+                ge += (vq.x >= vt) + (vq.y >= vt) + (vq.z >= vt) + (vq.w >= vt);
+            }
+            float thr_k = -INFINITY;
+            if (top_k > 0) {
+                if (own && gt < top_k && top_k <= ge) s_thr = vt;  // every writer holds the same value
+                __syncthreads();
+                thr_k = s_thr;
+            }
+            const bool surv = own && vt >= thr_k;
+            if (own) c_w[tid] = surv ? weight(vt) : 0.f;
+            __syncthreads();
+            bool kept = surv;
+            if (nucleus) {
+                float above = 0.f, tot = 0.f;  // mass of the survivors strictly above vt; all survivors
+                for (int q = 0; q < n; q += 4) {
+                    const float4 vq = *reinterpret_cast<const float4*>(&c_val[q]);
+                    const float4 wq = *reinterpret_cast<const float4*>(&c_w[q]);
+                    tot += wq.x + wq.y + wq.z + wq.w;
+                    above += (vq.x > vt ? wq.x : 0.f) + (vq.y > vt ? wq.y : 0.f) + (vq.z > vt ? wq.z : 0.f) +
+                             (vq.w > vt ? wq.w : 0.f);
+                }
+                const float W = top_k > 0 ? tot : w_all;
+                kept = surv && (above <= a.top_p * W || gt < a.min_keep);
+                if (top_k == 0 && kept && ge == n) s_bad = 1;  // the list's smallest value is kept
+            }
+            if (kept) atomicMin(&s_minkey, fkey(vt));
+            __syncthreads();
+            if (!s_bad) {
+                thr = fkey_inv(s_minkey);
+                done = true;
+            }
+        }
+    }
+    if (!done) {
+        // ---- block-wide searches over the whole row
+        const float thr_k = (top_k > 0 && int64_t(top_k) < V) ? nth_largest(top_k) : -INFINITY;
+        thr = thr_k;
+        if (nucleus) {
+            // the smallest row value whose strictly-greater mass is <= top_p * W is the
+            // largest key K with mass{key >= K} > top_p * W (mass{key >= K + 1} is then
+            // <= top_p * W, so K itself carries mass: it is a row value)
+            const float pw = a.top_p * (top_k == 0 ? w_all : mass_ge(thr_k));
+            uint32_t K = 0;
+#pragma unroll 1
+            for (int bit = 31; bit >= 0; --bit) {
+                const uint32_t cand = K | (1u << bit);
+                const float cf = fkey_inv(cand);
+                if (cf != cf) continue;
+                if (mass_ge(fmaxf(cf, thr_k)) > pw) K = cand;
+            }
+            float thr_p = K > fkey(-INFINITY) ? fkey_inv(K) : -INFINITY;
+            if (a.min_keep > 1) thr_p = fminf(thr_p, nth_largest(a.min_keep));
+            thr = fmaxf(thr_p, thr_k);
+        }
+    }
+
+    // ---- weights of the kept entries, their count and smallest value
+    auto kept = [&](float v) { return v >= thr && v != -INFINITY; };
+    const float ew = kept(fe) ? weight(fe) : 0.f;
+    const int eseg = je < s.head ? 0 : NSEG - 1;  // the edge element's segment
+    int nk = kept(fe) ? 1 : 0;
+    float mn = kept(fe) ? fe : INFINITY;
+    // the registers now hold the unnormalised probabilities; per-wave segment totals go
+    // straight to LDS (no per-thread segment array: it would spill at 1024 threads)
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        float t = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) {
+            const bool kp = kept(f[k][e]);
+            nk += kp ? 1 : 0;
+            mn = kp ? fminf(mn, f[k][e]) : mn;
+            const float w = kp ? weight(f[k][e]) : 0.f;
+            f[k][e] = w;
+            t += w;
+        }
+        t = wave_sum(t);
+        if (lane == 0) seg_tot[1 + k][wv] = t;
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    {
+        const float t0 = wave_sum(eseg == 0 ? ew : 0.f), t1 = wave_sum(eseg == 0 ? 0.f : ew);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) nk += __shfl_xor(nk, off, kWave);
+        mn = -wave_max(-mn);
+        if (lane == 0) {
+            seg_tot[0][wv] = t0;
+            seg_tot[NSEG - 1][wv] = t1;
+            w_cnt[wv] = nk;
+            w_min[wv] = mn;
+        }
+    }
+
+    // ---- inverse CDF at u: segment totals (fixed order) -> segment -> thread -> element
+    __syncthreads();
+    if (tid == 0) {
+        float acc = 0.f;
+        for (int g = 0; g < NSEG; ++g) {
+            seg_pre[g] = acc;
+            for (int w = 0; w < kWaves; ++w) acc += seg_tot[g][w];
+        }
+        seg_pre[NSEG] = acc;
+        const float target = a.u[b] * acc;
+        int gsel = -1;
+        for (int g = 0; g < NSEG; ++g)
+            if (gsel < 0 && seg_pre[g + 1] > target) gsel = g;
+        for (int g = NSEG - 1; gsel < 0 && g >= 0; --g)  // rounding at the top: last non-empty
+            if (seg_pre[g + 1] > seg_pre[g]) gsel = g;
+        s_pick[0] = gsel;
+        s_pick[1] = -1;
+        s_pick[2] = -1;
+        s_lp = 0.f;
+        s_rem = gsel < 0 ? 0.f : target - seg_pre[gsel];
+    }
+    __syncthreads();
+    const int gsel = s_pick[0];
+    const float rem = s_rem;
+    float mine = 0.f, lo = 0.f;
+    if (gsel >= 0) {
+        if (gsel == 0 || gsel == NSEG - 1) {
+            mine = (je >= 0 && eseg == gsel) ? ew : 0.f;
+        } else {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                // (opaque zero: the same sums exist in the pass above, and reusing them would
+                // keep NV more registers live across it)
+                float t = 0.f;
+                asm volatile("" : "+v"(t));
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) t += f[k][e];
+                mine = k + 1 == gsel ? t : mine;
+            }
+        }
+        float incl = mine;  // exclusive prefix of this thread's share inside the segment
+#pragma unroll
+        for (int off = 1; off < kWave; off <<= 1) {
+            const float y = __shfl_up(incl, off, kWave);
+            if (lane >= off) incl += y;
+        }
+        float woff = 0.f;
+        for (int w = 0; w < wv; ++w) woff += seg_tot[gsel][w];
+        lo = woff + incl - mine;
+        // the last thread (index order) whose share starts at or below the target
+        if (mine > 0.f && lo <= rem) atomicMax(&s_pick[1], tid);
+    }
+    __syncthreads();
+    if (gsel >= 0 && tid == s_pick[1]) {
+        int64_t pick = -1;
+        if (gsel == 0 || gsel == NSEG - 1) {
+            pick = je;
+        } else {
+            float run = lo;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                if (k + 1 != gsel) continue;
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) {
+                    if (f[k][e] > 0.f && (pick < 0 || run <= rem)) {
+                        pick = index_of(k, e);
+                        run += f[k][e];
+                        if (run > rem) run = INFINITY;  // found: later elements keep the pick
+                    }
+                }
+            }
+        }
+        s_pick[2] = int(pick);
+        // the row's registers hold weights by now: the drawn logit comes from memory again
+        if (pick >= 0) s_lp = (DT::load1(x, pick) - row_max) - log_sum;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int n = 0;
+        float mnk = INFINITY;
+        for (int w = 0; w < kWaves; ++w) {
+            n += w_cnt[w];
+            mnk = fminf(mnk, w_min[w]);
+        }
+        const bool got = s_pick[2] >= 0;
+        const int64_t tok = got ? s_pick[2] : padtok;
+        finish(tok, got ? s_lp : 0.f, got ? mnk : 0.f, got ? n : 0);
+        if (a.unfinished && a.eos >= 0) a.unfinished[b] = tok != a.eos ? 1 : 0;
+    }
+}
+
+}  // namespace trlx
+
+using namespace trlx;
+
+extern "C" int trlx_ppo_sample(const void* logits, int64_t ld_logits, int dtype, int64_t B, int64_t V,
+                               float temperature, int top_k, float top_p, int min_tokens_to_keep,
+                               int64_t cur_len, int64_t min_length, int64_t eos_token_id, int64_t pad_token_id,
+                               const float* u, int64_t* out_ids, float* out_logprobs, float* out_min_kept,
+                               int32_t* out_kept_count, int64_t* unfinished, void* stream) {
+    TRLX_REQUIRE(B == 0 || (logits && u && out_ids && out_logprobs && out_min_kept && out_kept_count), TRLX_ERR_ARG,
+                 "NULL argument to trlx_ppo_sample");
+    TRLX_REQUIRE(dtype == TRLX_F32 || dtype == TRLX_BF16, TRLX_ERR_DTYPE, "dtype %d", dtype);
+    TRLX_REQUIRE(B >= 0 && V > 0, TRLX_ERR_SHAPE, "bad shape");
+    TRLX_REQUIRE(temperature > 0.f && top_p > 0.f && top_k >= 0 && min_tokens_to_keep >= 1, TRLX_ERR_ARG,
+                 "bad sampling arguments (temperature > 0, top_p > 0, top_k >= 0, min_tokens_to_keep >= 1)");
+    TRLX_REQUIRE(eos_token_id >= -1 && eos_token_id < V && pad_token_id >= -1 && pad_token_id < V, TRLX_ERR_ARG,
+                 "eos / pad token outside [0, V) (-1 = none)");
+    TRLX_REQUIRE(B < (int64_t(1) << 31) && V * 16 < (int64_t(1) << 32), TRLX_ERR_SHAPE, "too large");
+    if (B == 0) return TRLX_OK;
+    PpoSampleArgs a = {};
+    a.logits = logits;
+    a.ld_logits = ld_logits;
+    a.V = V;
+    a.scale = kLog2e / temperature;
+    a.top_p = top_p;
+    a.min_keep = int(min_tokens_to_keep < V ? min_tokens_to_keep : V);
+    a.top_k = top_k == 0 ? 0 : int(top_k < a.min_keep ? a.min_keep : (top_k < V ? top_k : V));
+    a.suppress_eos = eos_token_id >= 0 && cur_len < min_length;
+    a.eos = eos_token_id;
+    a.pad = pad_token_id;
+    a.u = u;
+    a.out_ids = out_ids;
+    a.out_lp = out_logprobs;
+    a.out_min = out_min_kept;
+    a.out_cnt = out_kept_count;
+    a.unfinished = unfinished;
+    const int epv = dtype == TRLX_BF16 ? 8 : 4;
+    auto need = [&](int nt) { return (V / epv + 1 + (kLineVecs - 1) + nt - 1) / nt; };  // vectors per thread
+    // (the table of trlx_ilql_sample without its 128-VGPR rows — 16 x 8 bf16, 32 x 4 fp32 — which
+    // cannot hold the row beside this kernel's state without scratch: rows end at ~53k entries)
+#define TRLX_PSMP(DTT, N, NT)                                                                            \
+    if (need(NT) <= N) {                                                                                 \
+        hipLaunchKernelGGL((k_ppo_sample<DTT, N, NT>), dim3(unsigned(B)), dim3(NT), 0, (hipStream_t)stream, a); \
+        return check_launch("k_ppo_sample");                                                             \
+    }
+    if (dtype == TRLX_BF16) {
+        TRLX_PSMP(BF16T, 1, 1024)
+        TRLX_PSMP(BF16T, 4, 1024)
+        TRLX_PSMP(BF16T, 8, 512)
+        TRLX_PSMP(BF16T, 13, 512)
+    } else {
+        TRLX_PSMP(F32T, 1, 1024)
+        TRLX_PSMP(F32T, 4, 1024)
+        TRLX_PSMP(F32T, 8, 1024)
+        TRLX_PSMP(F32T, 16, 512)
+        TRLX_PSMP(F32T, 26, 512)
+    }
+#undef TRLX_PSMP
+    TRLX_REQUIRE(false, TRLX_ERR_SHAPE, "vocab %lld too long for the sampling kernel", (long long)V);
+}

@@ -269,6 +269,22 @@ class PPOConfig:
     def from_dict(cls, config: Dict[str, Any]):
         return cls(**config)
 
+    # -------------------------------------------------------------- rollout sampling
+    def sample_step(self, logits, cur_len, unfinished=None, **overrides):
+        """One rollout token from logits [B, V] with this config's gen_kwargs — the per-token
+        sampling chain of `generate(**gen_kwargs)` (ppo_orchestrator.py:76) as one launch; see
+        sampling.ppo_sample_step.  Reads temperature, top_k, top_p, min_length, eos_token_id and
+        pad_token_id; `do_sample: False` (greedy) maps to top_k = 1.  `overrides` are passed on
+        (u=, out=, generator=, or any of the keys above).  Returns (ids [B, 1], logprobs [B])."""
+        from .sampling import ppo_sample_step
+        gk = self.gen_kwargs
+        kw = {k: gk[k] for k in ("temperature", "top_k", "top_p", "min_length", "eos_token_id", "pad_token_id")
+              if gk.get(k) is not None}
+        if not gk.get("do_sample", True):
+            kw.update(top_k=1, top_p=1.0)
+        kw.update(overrides)
+        return ppo_sample_step(logits, cur_len=cur_len, unfinished=unfinished, **kw)
+
     # -------------------------------------------------------------- A5
     def gae_raw(self, values: torch.Tensor, rewards: torch.Tensor, response_length: int,
                 lengths: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
