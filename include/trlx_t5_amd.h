@@ -469,7 +469,9 @@ int trlx_lmhead_logprobs_bwd_ex2(const void* hidden, int64_t ldh, const void* we
  *   order; u from the caller's generator replaces torch.multinomial's draw);
  *   out = finished ? eos : out; finished = out == eos.
  * logits / tq rows: [B, V] of dtype with row strides ld_*; tq1 may be NULL (one head);
- * logit_mask: NULL or uint8 [*, V] rows of ld_mask; finished: int64 [B] in/out or NULL. */
+ * logit_mask: NULL or uint8 [*, V] rows of ld_mask; finished: int64 [B] in/out or NULL.
+ * A row in which nothing is kept (no finite logit) returns token 0.  B == 0 launches nothing
+ * (the row pointers may then be NULL). */
 int trlx_ilql_sample(const void* logits, int64_t ld_logits, const void* tq0, int64_t ld_tq0,
                      const void* tq1, int64_t ld_tq1, int dtype, const float* vs,
                      const uint8_t* logit_mask, int64_t ld_mask, const int64_t* prev_ids, int64_t B,

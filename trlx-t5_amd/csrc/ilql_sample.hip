@@ -468,7 +468,9 @@ __global__ __launch_bounds__(NT) void k_ilql_sample(SampleArgs a) {
     __syncthreads();
     SMP_STAMP(6);
     if (tid == 0) {
-        const int64_t tok = s_pick[2] < 0 ? 0 : s_pick[2];  // nothing kept: torch.multinomial would raise
+        // nothing kept (torch.multinomial would raise): token 0.  A row without a finite logit ends
+        // here too: its lse is -inf, every score -inf - -inf = NaN, which no comparison above selects
+        const int64_t tok = s_pick[2] < 0 ? 0 : s_pick[2];
         a.out_ids[b] = tok;  // (finished rows returned eos at the top)
         if (a.finished) a.finished[b] = tok == a.eos ? 1 : 0;
     }
@@ -483,7 +485,8 @@ extern "C" int trlx_ilql_sample(const void* logits, int64_t ld_logits, const voi
                                 const uint8_t* logit_mask, int64_t ld_mask, const int64_t* prev_ids, int64_t B,
                                 int64_t V, float beta, int top_k, float temperature, const float* u,
                                 int64_t* out_ids, int64_t* finished, int64_t eos, void* stream) {
-    TRLX_REQUIRE(logits && tq0 && vs && u && out_ids, TRLX_ERR_ARG, "NULL argument to trlx_ilql_sample");
+    // an empty batch's tensors have no storage: NULL is what B == 0 passes
+    TRLX_REQUIRE(B == 0 || (logits && tq0 && vs && u && out_ids), TRLX_ERR_ARG, "NULL argument to trlx_ilql_sample");
     TRLX_REQUIRE(!logit_mask || prev_ids, TRLX_ERR_ARG, "logit_mask needs prev_ids");
     TRLX_REQUIRE(dtype == TRLX_F32 || dtype == TRLX_BF16, TRLX_ERR_DTYPE, "dtype %d", dtype);
     TRLX_REQUIRE(B >= 0 && V > 0 && top_k > 0 && temperature > 0.f, TRLX_ERR_SHAPE, "bad sampling arguments");
