@@ -496,7 +496,9 @@ int trlx_ilql_sample(const void* logits, int64_t ld_logits, const void* tq0, int
  * suppression, no temperature); out_min_kept[b] = the smallest kept x, exactly;
  * out_kept_count[b] = the number of kept tokens.  A finished row writes 0 to those three; so
  * does a row with no finite logit left, which returns pad (HF raises there); pad = -1 writes
- * token 0 in both cases.
+ * token 0 in both cases.  The row without a finite logit updates unfinished[b] like any live
+ * row, from the token it returns: a pad that equals eos finishes it (HF: a sequence ends at
+ * eos), any other pad leaves it live; eos = -1 leaves unfinished untouched for every row.
  * logits: [B, V] of dtype (TRLX_F32 / TRLX_BF16), row stride ld_logits, unit column stride;
  * eos_token_id / pad_token_id in [0, V) or -1 for none; unfinished: int64 [B] in/out or NULL.
  * Requires temperature > 0, top_p > 0, top_k >= 0, min_tokens_to_keep >= 1 (TRLX_ERR_ARG);

@@ -13,56 +13,9 @@ import pytest
 import torch
 
 import trlx_t5_amd as P
+from ppo_sample_checks import DEV, NEG, TOL, check_draw_and_logprob, oracle_keep, run, suppress
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-NEG = float("-inf")
-TOL = 1e-5
-
-
-# ------------------------------------------------------------------ fp64 oracle
-def oracle_keep(x, T, top_k, top_p, min_keep=1):
-    """x: fp64 [B, V] (eos already suppressed).  Returns (keep bool [B, V], w fp64 [B, V]):
-    the kept set and exp(s - max s), s = x / T, for every finite entry."""
-    B, V = x.shape
-    keep = torch.isfinite(x)
-    if top_k > 0:
-        k = min(max(int(top_k), min_keep), V)
-        kth = torch.topk(x, k, -1).values[:, -1:]
-        keep = keep & (x >= kth)
-    s = x / T
-    smax = torch.where(keep, s, torch.full_like(s, NEG)).max(-1, keepdim=True).values
-    w = torch.where(torch.isfinite(x), torch.exp(s - smax), torch.zeros_like(s))
-    if top_p < 1.0:
-        ws = torch.where(keep, w, torch.zeros_like(w))
-        W = ws.sum(-1, keepdim=True)
-        xs, order = torch.sort(torch.where(keep, x, torch.full_like(x, NEG)), -1, descending=True)
-        wso = ws.gather(1, order)
-        before = torch.cumsum(wso, -1) - wso            # mass ahead of each entry in sorted order
-        first = torch.searchsorted(-xs, -xs, right=False)  # first entry of each run of ties = #(strictly greater)
-        above = before.gather(1, first)                 # mass of the survivors strictly greater
-        ok = (above <= top_p * W) | (first < min_keep)
-        keep = keep & torch.zeros_like(keep).scatter(1, order, ok)
-    return keep, w
-
-
-def suppress(x, eos):
-    x = x.double().clone()
-    if eos is not None:
-        x[:, eos] = NEG
-    return x
-
-
-# ------------------------------------------------------------------ the kernel
-def run(logits, u, **kw):
-    B = logits.shape[0]
-    lg = logits.to(DEV)
-    out = (torch.empty(B, dtype=torch.int64, device=DEV), torch.empty(B, dtype=torch.float32, device=DEV),
-           torch.empty(B, dtype=torch.float32, device=DEV), torch.empty(B, dtype=torch.int32, device=DEV))
-    ids, lp = P.ppo_sample_step(lg, u=u.to(DEV, torch.float32), out=out, **kw)
-    torch.cuda.synchronize()
-    assert ids.data_ptr() == out[0].data_ptr() and lp.data_ptr() == out[1].data_ptr()
-    return ids.cpu().reshape(B), lp.cpu(), out[2].cpu(), out[3].cpu()
 
 
 def make(V, dtype, seed, B=16, sigma=3.0, quant=None):
@@ -75,22 +28,6 @@ def make(V, dtype, seed, B=16, sigma=3.0, quant=None):
     u = torch.rand(B, generator=g)
     u[0], u[1] = 0.0, 0.999999
     return x.to(dtype), u
-
-
-def check_draw_and_logprob(logits, x, kept, w, ids, lp, u):
-    """Token inside the kept set; its CDF interval over that set (index order) holds u within
-    TOL; logprob = fp64 log_softmax of the unmodified row at the token."""
-    B = x.shape[0]
-    rows = torch.arange(B)
-    assert bool(kept[rows, ids].all()), "token outside the kept set"
-    pk = torch.where(kept, w, torch.zeros_like(w))
-    cdf = torch.cumsum(pk / pk.sum(-1, keepdim=True), -1)
-    hi = cdf[rows, ids]
-    lo = hi - (pk / pk.sum(-1, keepdim=True))[rows, ids]
-    ud = u.double()
-    assert bool(((lo - TOL <= ud) & (ud <= hi + TOL)).all()), (lo, ud, hi)
-    want = torch.log_softmax(logits.double(), -1)[rows, ids]
-    torch.testing.assert_close(lp.double(), want, rtol=1e-5, atol=1e-6)
 
 
 # ------------------------------------------------------------------ top-k: exact kept set

@@ -15,11 +15,12 @@
 // Filtering is defined on the order of x (division by T > 0 is monotone).  The row is held
 // in VGPRs as in ilql_sample.hip (16-B non-temporal buffer loads on the rows' 256-B line
 // shift).  Nothing is sorted: the k-th largest value and the nucleus threshold are each the
-// result of a search over order-preserving uint32 keys.  Fast path: a candidate list in
-// LDS (the values above a lower bound of the n-th largest, n = k or a seed of 128 for
-// top-p alone) is ranked by one thread per candidate.  Rows that defeat it (ties, k above
-// the thread count, a nucleus wider than the list) take 32-step block-wide bisections: on
-// counts for top-k, on mass for top-p.  Every block reduction runs in a fixed order.
+// result of a search over order-preserving uint32 keys.  Fast path: a candidate list in LDS
+// (the values above a lower bound of the n-th largest, n = k or a seed of 128 for top-p
+// alone) is ranked by one thread per candidate.  Rows that defeat it (ties, k above the
+// thread count, a nucleus wider than the list) take 32-step block-wide bisections: on counts
+// for top-k, on mass for top-p.  Block reductions run in a fixed order; the list's masses are
+// summed in the order the waves filled it, and feed comparisons with top_p * W only.
 #include "common.h"
 
 namespace trlx {
@@ -142,8 +143,13 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(PpoSampleArgs a) {
     }
     sum = wave_sum_d(sum);
     if (lane == 0) {
+        // mo is rounded, so every term above carries the factor 2^(m * log2e - mo) (off 1 by
+        // up to 7e-7), the maximum's own term included — and that one must count as exactly 1
+        // for log(sum) to keep the small rest.  d is that term bit for bit: divide it out
+        // (1 / d = 1 - e + e^2 to fp64 for e = d - 1)
+        const double e = double(exp2_fast(__builtin_fmaf(m, kLog2e, -mo))) - 1.0;
         sh_red[wv] = m;
-        sh_sum[wv] = sum;
+        sh_sum[wv] = sum * (1.0 - e + e * e);
     }
     __syncthreads();
     m = sh_red[0];
