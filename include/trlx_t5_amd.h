@@ -274,7 +274,8 @@ int trlx_ppo_loss_finalize(const double* partials, int64_t nblk, int64_t n,
  *   q_i row (b,a)       : CE against the action a* = input_ids[b, 1+actions_ixs[b,a]]
  *                         weighted by dones[b,a] (CQL, :87-96) + the TD term
  *                         ((Q_i[a*] - (r + gamma*vs[b,a+1]*dones[b,a+1]))*dones[b,a])^2 (:63-74)
- *   target-Q rows are only gathered at a* (min over heads) for the expectile V loss (:76-83).
+ *   target-Q rows are only gathered at a* (min over heads) for the expectile V loss (:76-83);
+ *   with tq_gathered = 1 the caller passes the values at a* themselves.
  * Three launches: prep (n_nonterminal = max(1, sum dones[:, :-1]) and sum attention[:, 1:]),
  * rows (one workgroup per vocab row), finalize (fixed-order fp64 sums -> losses[5] =
  * {loss, loss_q, loss_v, loss_cql, loss_awac}); prep and finalize run a few workgroups whose
@@ -290,7 +291,7 @@ typedef struct {
     int64_t logits_sb, logits_st;
     const void* q[2];                 /* [B,A,V] Q heads (q[1] unused when nq == 1) */
     int64_t q_sb[2], q_st[2];
-    const void* tq[2];                /* [B,A,V] target Q heads (gathered only) */
+    const void* tq[2];                /* [B,A,V] target Q heads (gathered only); see tq_gathered */
     int64_t tq_sb[2], tq_st[2];
     const int64_t* input_ids;         /* [B,L] */
     const int64_t* attention_mask;    /* [B,L] */
@@ -309,6 +310,11 @@ typedef struct {
     float* losses;                    /* [5] fp32 */
     void* workspace;                  /* trlx_ilql_workspace_bytes(B, L, A, nq) bytes, zero-filled
                                          once before first use (prep / finalize re-arm their tickets) */
+    int tq_gathered;                  /* 0: tq[i] are [B,A,V] rows of `dtype`, gathered at a* here.
+                                         1: tq[i] are fp32 [B,A] values already taken at a*
+                                         (trlx_ilql_tq_at_actions): element (b,a) at
+                                         tq[i] + b*tq_sb[i] + a*tq_st[i]; `dtype` does not describe
+                                         them; an a* outside [0, V) still makes the value NaN */
 } trlx_ilql_args;
 
 int64_t trlx_ilql_workspace_bytes(int64_t B, int64_t L, int64_t A, int nq);
@@ -316,6 +322,49 @@ int trlx_ilql_prep(const trlx_ilql_args* args, void* stream);
 int trlx_ilql_rows(const trlx_ilql_args* args, void* stream);
 int trlx_ilql_finalize(const trlx_ilql_args* args, void* stream);
 int trlx_ilql_loss_fused(const trlx_ilql_args* args, void* stream);   /* the three in order */
+
+/* ---------------------------------------------------------------- ILQL heads
+ * The target-Q heads at the action tokens only — replaces the second Linear of
+ * `target_qs = tuple(q_head(actions_hs) for q_head in self.target_q_heads)`
+ * (ilql_models.py:31-34,156) for the loss, which reads tq_i[b, a, a*] alone
+ * (a* = input_ids[b, 1 + actions_ixs[b, a]], computed here exactly as the loss rows do):
+ *   out[i][b, a] = sum_k z[i][b, a, k] * w2[i][a*, k] + b2[i][a*]
+ * z[i]: the head's post-ReLU hidden activations [B, A, K], element (b, a, k) at
+ * z[i] + b*z_sb[i] + a*z_st[i] + k; w2[i]: [V, K] (nn.Linear layout), rows of w2_ld[i]
+ * elements; b2[i]: [V] or NULL; all of `dtype` (TRLX_F32 / TRLX_BF16).  out[i]: fp32 [B, A],
+ * contiguous.  One launch for nh = 1 or 2 heads, one wave per (token, head).  fp32
+ * accumulation in an order fixed by (K, dtype) alone: bit-reproducible, independent of B, A,
+ * the grid and the rows' alignment (16-B loads when K is a multiple of the vector width and
+ * both rows are 16-B aligned, element loads into the same chains otherwise).  Any K >= 1.
+ * An a* outside [0, V) (or actions_ixs outside [0, L-1)) gives NaN and reads nothing. */
+typedef struct {
+    int dtype;                        /* TRLX_F32 / TRLX_BF16: z, w2, b2 */
+    int nh;                           /* 1 or 2 heads */
+    int64_t B, L, A, K, V;
+    const void* z[2];
+    int64_t z_sb[2], z_st[2];
+    const void* w2[2];
+    int64_t w2_ld[2];
+    const void* b2[2];                /* or NULL */
+    const int64_t* input_ids;         /* [B,L] */
+    const int64_t* actions_ixs;       /* [B,A] */
+    float* out[2];                    /* [B,A] fp32 */
+} trlx_ilql_tq_args;
+int trlx_ilql_tq_at_actions(const trlx_ilql_tq_args* args, void* stream);
+
+/* Polyak sync of the target heads — replaces ILQLHeads._sync_target_q_heads
+ * (ilql_models.py:161-168): for each of `count` tensors of one dtype (TRLX_F32 / TRLX_BF16)
+ *   target[i][k] = (alpha * src[i][k]) + (1 - alpha) * target[i][k],   k < numel[i]
+ * rounded as torch's three elementwise ops: alpha and 1.0 - alpha (formed in double) are
+ * each rounded to fp32, every product is rounded separately (no fma), and for bf16 each
+ * product and the sum are rounded to bf16.  The (src, target, numel) triples travel to the
+ * kernel by value, TRLX_POLYAK_MAX_TENSORS per launch; a longer list is split into several
+ * launches.  The host arrays are read during the call only.  Zero-length tensors are
+ * skipped; any element alignment and any tail length; a source that overlaps its target is
+ * refused with TRLX_ERR_ARG (before anything is launched). */
+#define TRLX_POLYAK_MAX_TENSORS 16
+int trlx_polyak_update(const void* const* src, void* const* target, const int64_t* numel, int64_t count,
+                       int dtype, double alpha, void* stream);
 
 /* ---------------------------------------------------------------- §8f rank 2: fused lm_head + logprobs
  * lp[n] = h[n]·W[y_n] − logsumexp_v h[n]·W[v] without materialising the [N, V] logits —

@@ -10,6 +10,9 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
       trlx/orchestrator/ppo_orchestrator.py:96-112,163-167
   ILQLConfig (.loss), ILQLBatch, ilql_sample_step (one decode step of generate)
       trlx/model/nn/ilql_models.py:52-116,296-316, trlx/data/ilql_types.py
+  ILQLHeads (.forward, .forward_for_loss, .sync_target_q_heads), ilql_target_q_at_actions,
+  polyak_update — the heads module: target Q at the action tokens only, fused Polyak sync
+      trlx/model/nn/ilql_models.py:119-181
   ppo_sample_step — one rollout token of generate(**gen_kwargs): min length, temperature,
       top-k, top-p, the draw, unfinished / pad, and the token's policy log-prob
       trlx/orchestrator/ppo_orchestrator.py:76 (HF generate's sample path)
@@ -30,6 +33,7 @@ from .ppo import (STATS_KEYS, AdaptiveKLController, FixedKLController, PPOConfig
 from .lm_head import lm_head_logprobs
 from .rollout_store import PPORLBatch, PPORLElement, PPORolloutStorage
 from .ilql import ILQL_LOSS_KEYS, ILQLBatch, ILQLConfig, ILQLHotPath, ilql_sample_step
+from .ilql_heads import ILQLHeads, ilql_target_q_at_actions, make_head, polyak_update
 from .sampling import ppo_sample_step
 from .control import PPOControlState
 from .step import PPOHotPath
@@ -41,7 +45,7 @@ __all__ = [
     "grad_buffer_like", "PPOConfig", "AdaptiveKLController", "FixedKLController", "kl_penalty_rewards",
     "prepare_scores", "stats_dict", "STATS_KEYS", "PPOHotPath", "load_library",
     "ILQLConfig", "ILQLBatch", "ILQLHotPath", "ILQL_LOSS_KEYS", "ilql_sample_step", "ppo_sample_step",
-    "PPORolloutStorage",
+    "ILQLHeads", "ilql_target_q_at_actions", "polyak_update", "make_head", "PPORolloutStorage",
     "PPORLElement", "PPORLBatch", "lm_head_logprobs", "PPOControlState",
     "RcclComm", "shift_tokens_right", "get_model_inputs",
 ]

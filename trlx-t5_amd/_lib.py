@@ -41,10 +41,27 @@ class IlqlArgs(ctypes.Structure):
         ("dlogits", _c_vp), ("dlogits_sb", _c_i64), ("dlogits_st", _c_i64),
         ("dq", _c_vp * 2), ("dq_sb", _c_i64 * 2), ("dq_st", _c_i64 * 2),
         ("dvs", _c_vp), ("losses", _c_vp), ("workspace", _c_vp),
+        ("tq_gathered", _c_int),
     ]
 
 
+class IlqlTqArgs(ctypes.Structure):
+    """Mirror of trlx_ilql_tq_args (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("dtype", _c_int), ("nh", _c_int),
+        ("B", _c_i64), ("L", _c_i64), ("A", _c_i64), ("K", _c_i64), ("V", _c_i64),
+        ("z", _c_vp * 2), ("z_sb", _c_i64 * 2), ("z_st", _c_i64 * 2),
+        ("w2", _c_vp * 2), ("w2_ld", _c_i64 * 2),
+        ("b2", _c_vp * 2),
+        ("input_ids", _c_vp), ("actions_ixs", _c_vp),
+        ("out", _c_vp * 2),
+    ]
+
+
+POLYAK_MAX_TENSORS = 16
+
 _ilql_p = ctypes.POINTER(IlqlArgs)
+_ilql_tq_p = ctypes.POINTER(IlqlTqArgs)
 
 CTL_SLOTS = 16
 (CTL_MEAN, CTL_VAR, CTL_STD, CTL_COUNT, CTL_REF_MEAN, CTL_REF_STD, CTL_REF_SET, CTL_KL_COEF, CTL_BATCH_MEAN,
@@ -204,6 +221,9 @@ SIGNATURES = {
     "trlx_ilql_rows": (_c_int, [_ilql_p, _c_vp]),
     "trlx_ilql_finalize": (_c_int, [_ilql_p, _c_vp]),
     "trlx_ilql_loss_fused": (_c_int, [_ilql_p, _c_vp]),
+    "trlx_ilql_tq_at_actions": (_c_int, [_ilql_tq_p, _c_vp]),
+    "trlx_polyak_update": (_c_int, [ctypes.POINTER(_c_vp), ctypes.POINTER(_c_vp), ctypes.POINTER(_c_i64), _c_i64,
+                                    _c_int, _c_d, _c_vp]),
 }
 
 _lib = None

@@ -337,12 +337,15 @@ __global__ __launch_bounds__(NL ? 512 : kMaxThreads, NL ? 4 : 1) void k_ilql_row
         if (id.head == 0) {  // expectile V loss + d loss / d vs for state (b, t)
             const int64_t* ai = a.actions_ixs;
             (void)ai;
-            float tQ = y_ok ? DT::load1(static_cast<const E*>(a.tq[0]) + id.b * a.tq_sb[0] + id.t * a.tq_st[0], y)
-                            : NAN;
+            // tq_gathered: fp32 [B, A] values already taken at a* (trlx_ilql_tq_at_actions)
+            const auto tq_at = [&](int h) -> float {
+                const int64_t off = id.b * a.tq_sb[h] + id.t * a.tq_st[h];
+                return a.tq_gathered ? static_cast<const float*>(a.tq[h])[off]
+                                     : DT::load1(static_cast<const E*>(a.tq[h]) + off, y);
+            };
+            float tQ = y_ok ? tq_at(0) : NAN;
             if (a.nq > 1) {
-                const float t1 = y_ok ? DT::load1(static_cast<const E*>(a.tq[1]) + id.b * a.tq_sb[1] +
-                                                      id.t * a.tq_st[1], y)
-                                      : NAN;
+                const float t1 = y_ok ? tq_at(1) : NAN;
                 tQ = (tQ != tQ || t1 != t1) ? NAN : fminf(tQ, t1);  // torch.minimum propagates NaN
             }
             const float V = ld_any(a.vs, a.vs_dtype, id.b * S + id.t);
@@ -448,6 +451,8 @@ static int ilql_check(const trlx_ilql_args* p) {
     const trlx_ilql_args& a = *p;
     TRLX_REQUIRE(a.dtype == TRLX_F32 || a.dtype == TRLX_BF16, TRLX_ERR_DTYPE, "ILQL rows dtype %d", a.dtype);
     TRLX_REQUIRE(a.nq == 1 || a.nq == 2, TRLX_ERR_ARG, "nq must be 1 or 2 (got %d)", a.nq);
+    TRLX_REQUIRE(a.tq_gathered == 0 || a.tq_gathered == 1, TRLX_ERR_ARG, "tq_gathered must be 0 or 1 (got %d)",
+                 a.tq_gathered);
     TRLX_REQUIRE(a.B > 0 && a.L >= 1 && a.A >= 1 && a.V > 0, TRLX_ERR_SHAPE,
                  "bad ILQL shape B=%lld L=%lld A=%lld V=%lld", (long long)a.B, (long long)a.L, (long long)a.A,
                  (long long)a.V);

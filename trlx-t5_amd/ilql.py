@@ -52,6 +52,25 @@ def _strides(x):
     return x.stride(0), x.stride(1)
 
 
+def _tq_gathered(target_qs, B, A, V):
+    """The form of the target-Q entries: False = [B, A, V] rows (gathered at the action tokens
+    by the loss), True = [B, A] (or [B, A, 1]) values already taken there
+    (ilql_target_q_at_actions, ILQLHeads.forward_for_loss).  Mixing the two raises."""
+    forms = set()
+    for i, t in enumerate(target_qs):
+        shape = tuple(t.shape)
+        if shape == (B, A) or (shape == (B, A, 1) and V != 1):
+            forms.add(True)
+        elif shape == (B, A, V):
+            forms.add(False)
+        else:
+            raise ValueError(f"target_qs[{i}] must have shape {(B, A, V)} (rows) or {(B, A)} (values at the "
+                             f"action tokens), got {shape}")
+    if len(forms) != 1:
+        raise ValueError("target_qs mixes [B, A, V] rows and [B, A] values at the action tokens")
+    return forms.pop()
+
+
 class _ILQLLoss(torch.autograd.Function):
     """Forward = trlx_ilql_loss_fused (gradients computed eagerly, closed form); backward
     scales the stored gradients in place by grad_output."""
@@ -65,8 +84,12 @@ class _ILQLLoss(torch.autograd.Function):
         S = A + 1
         lg = _row_view(logits, "logits", (B, L, V))
         qs = [_row_view(q, f"qs[{i}]", (B, A, V)) for i, q in enumerate((q0, q1)[:nq])]
-        tqs = [_row_view(q, f"target_qs[{i}]", (B, A, V)) for i, q in enumerate((tq0, tq1)[:nq])]
-        for t in qs + tqs:
+        gathered = _tq_gathered((tq0, tq1)[:nq], B, A, V)
+        if gathered:  # fp32 values at the action tokens, read with their own strides
+            tqs = [q.reshape(B, A).to(torch.float32) for q in (tq0, tq1)[:nq]]
+        else:
+            tqs = [_row_view(q, f"target_qs[{i}]", (B, A, V)) for i, q in enumerate((tq0, tq1)[:nq])]
+        for t in qs + ([] if gathered else tqs):
             if t.dtype != lg.dtype:
                 raise TypeError("logits, qs and target_qs must share one dtype")
         vflat = vs.reshape(B, S) if vs.numel() == B * S else None
@@ -95,6 +118,7 @@ class _ILQLLoss(torch.autograd.Function):
 
         a = _lib.IlqlArgs()
         a.dtype, a.nq, a.B, a.L, a.A, a.V = _lib.dtype_code(lg), nq, B, L, A, V
+        a.tq_gathered = int(gathered)
         a.logits = lg.data_ptr()
         a.logits_sb, a.logits_st = _strides(lg)
         a.dlogits = dlg.data_ptr()
@@ -156,11 +180,19 @@ class ILQLConfig:
     def from_dict(cls, config: dict):
         return cls(**config)
 
+    def heads(self, hidden_size: int, vocab_size: int):
+        """ILQLConfig.heads (ilql_models.py:49-50)."""
+        from .ilql_heads import ILQLHeads
+        return ILQLHeads(self, hidden_size, vocab_size)
+
     def loss(self, outputs: Any, labels: ILQLBatch):
         """ILQLConfig.loss (ilql_models.py:52-116): outputs = (logits, (qs, target_qs, vs)).
 
         Returns (loss, stats) with the reference's stats keys; stats values are 0-d device
         tensors ("losses/loss" is the loss itself).  Gradients reach logits, qs and vs.
+        target_qs: [B, A, V] rows as the reference builds them, or — every entry — [B, A]
+        (or [B, A, 1]) values already taken at the action tokens
+        (ILQLHeads.forward_for_loss / ilql_target_q_at_actions); mixing the two raises.
         Deviation: with one action per row (A == 1) and B > 1 the reference's
         `vs[:, :-1].squeeze()` drops the action axis and broadcasts [B,1] against [B]
         into a [B,B] loss; that degenerate shape raises ValueError here."""
@@ -213,6 +245,8 @@ class ILQLHotPath:
         self.timers.setdefault(name, []).append([e0, e1])
 
     def step(self, logits, qs, target_qs, vs, batch: ILQLBatch):
+        """target_qs: [B, L-1, V] rows of the logits dtype, or — every entry — fp32 [B, L-1]
+        (or [B, L-1, 1]) values at the action tokens (ilql_target_q_at_actions)."""
         B, L, V, A, nq = self.B, self.L, self.V, self.A, self.nq
         if tuple(logits.shape) != (B, L, V) or logits.dtype != self.dtype or logits.stride(-1) != 1:
             raise ValueError("logits do not match the hot path shape / dtype")
@@ -220,9 +254,14 @@ class ILQLHotPath:
         if len(qs) != nq or len(target_qs) != nq:
             raise ValueError(f"the hot path was built for {nq} Q head(s) (two_qs={self.cfg.two_qs}); got "
                              f"{len(qs)} Q and {len(target_qs)} target-Q heads")
-        for q in qs + target_qs:
+        gathered = _tq_gathered(target_qs, B, A, V)
+        for q in qs + ([] if gathered else target_qs):
             if tuple(q.shape) != (B, A, V) or q.dtype != self.dtype or q.stride(-1) != 1:
                 raise ValueError("Q heads must be [B, L-1, V] of the logits dtype")
+        if gathered:
+            if any(t.dtype != torch.float32 for t in target_qs):
+                raise ValueError("target-Q values at the action tokens must be fp32 [B, L-1]")
+            target_qs = [t.squeeze(-1) if t.dim() == 3 else t for t in target_qs]
         _lib.require_cuda(logits, vs, batch.rewards, *qs, *target_qs)
         for name, t, shape in (("vs", vs, (B, A + 1)), ("batch.rewards", batch.rewards, (B, A))):
             ok_shape = tuple(t.shape) in (shape, shape + (1,))
@@ -238,6 +277,7 @@ class ILQLHotPath:
             self.dq = [grad_buffer_like(q) for q in qs[:nq]]
         a = _lib.IlqlArgs()
         a.dtype, a.nq, a.B, a.L, a.A, a.V = _lib.dtype_code(logits), nq, B, L, A, V
+        a.tq_gathered = int(gathered)
         a.logits, (a.logits_sb, a.logits_st) = logits.data_ptr(), _strides(logits)
         a.dlogits, (a.dlogits_sb, a.dlogits_st) = self.dlogits.data_ptr(), _strides(self.dlogits)
         for i in range(nq):
