@@ -581,6 +581,46 @@ int trlx_rows_copy(int nfields, const void* const* src, void* const* dst, const 
 int trlx_shift_tokens_right(const int64_t* ids, int64_t B, int64_t T, int64_t ld, int64_t pad_token_id,
                             int64_t decoder_start_token_id, int64_t* out, int64_t out_ld, void* stream);
 
+/* ---------------------------------------------------------------- §8f: device-resident ILQL rollout store
+ * The offline dataset of ILQLRolloutStorage (trlx/pipeline/offline_pipeline.py:57-85) as six
+ * flat device buffers in three offset families, each with an int64 prefix-sum vector of
+ * N + 1 entries (sample i of family X spans [off_X[i], off_X[i+1]), len_X(i) its length):
+ *   off_L: input_ids, attention_mask     off_S: states_ixs, dones     off_A: actions_ixs, rewards
+ * rewards is fp32, the other five fields are int64.
+ *
+ * trlx_ilql_collate builds one training batch in one launch — replaces the pad_sequence
+ * collate_fn (offline_pipeline.py:88-108) and to_device(batch) (accelerate_ilql_model.py:58-68).
+ * For each field f of family X, j < n and c < W_X:
+ *   out_f[j * ld_f + c] = c < len_X(idx[j]) ? f[off_X[idx[j]] + c] : 0
+ * idx: device int64 [n] sample numbers, any order, repeats allowed; an entry outside [0, N)
+ * gives a row of pads and reads nothing.  Columns >= W_X are never written (a longer sample is
+ * truncated, row strides ld_f >= W_X in elements), length 0 gives a row of pads, an output of
+ * width 0 may be NULL, n = 0 is a no-op. */
+int trlx_ilql_collate(const int64_t* input_ids, const int64_t* attention_mask, const float* rewards,
+                      const int64_t* states_ixs, const int64_t* actions_ixs, const int64_t* dones,
+                      const int64_t* off_L, const int64_t* off_S, const int64_t* off_A, int64_t N,
+                      const int64_t* idx, int64_t n, int64_t WL, int64_t WS, int64_t WA,
+                      int64_t* out_input_ids, int64_t ld_input_ids, int64_t* out_attention_mask,
+                      int64_t ld_attention_mask, float* out_rewards, int64_t ld_rewards,
+                      int64_t* out_states_ixs, int64_t ld_states_ixs, int64_t* out_actions_ixs,
+                      int64_t ld_actions_ixs, int64_t* out_dones, int64_t ld_dones, void* stream);
+
+/* The device half of OfflineOrchestrator.make_experience (offline_orchestrator.py:39-70): the
+ * five derived flat fields of all N samples in one launch.  Sample i with prompt_len[i] = p:
+ *   attention_mask = 1 (len_L)          states_ixs = p-1, p, ... (len_S)     actions_ixs = p-1, p, ... (len_A)
+ *   dones = 1 ... 1 0 (len_S)           out_rewards = 0 ... 0 G_i (len_A)
+ *   G_i = (rewards[i] - mean) / (std + 1e-30), unbiased std, evaluated in fp64 and rounded to fp32
+ * mean / std come from stats[4] = {sum, sumsq, count, .} of the raw rewards
+ * (trlx_moments_partial / trlx_moments_finalize), read on the device; count 1 gives NaN as
+ * torch's std() does.  The caller makes the offsets consistent (len_S = len_L - p + 1,
+ * len_A = len_L - p, 1 <= p < len_L); total_X = off_X[N] is the length of family X's buffers,
+ * past which nothing is written whatever the offsets hold.  N = 0 is a no-op. */
+int trlx_ilql_build_fields(const int64_t* off_L, const int64_t* off_S, const int64_t* off_A,
+                           const int64_t* prompt_len, const float* rewards, const double* stats, int64_t N,
+                           int64_t total_L, int64_t total_S, int64_t total_A, int64_t* attention_mask,
+                           int64_t* states_ixs, int64_t* actions_ixs, int64_t* dones, float* out_rewards,
+                           void* stream);
+
 /* ---------------------------------------------------------------- §8f rank 4: device-resident controller state
  * The PPO loop's host scalars — RunningMoments of the scores (trlx/utils/modeling.py:72-104),
  * the orchestrator's ref_mean/ref_std + score scale/clip (ppo_orchestrator.py:48-49,96-112)

@@ -19,6 +19,9 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
   lm_head_logprobs — fused lm_head GEMM (MFMA) + logprobs, logits never in HBM
   PPORolloutStorage, PPORLElement, PPORLBatch
       trlx/pipeline/ppo_pipeline.py, trlx/data/ppo_types.py (device-resident store)
+  ILQLRolloutStorage (.from_samples = make_experience, .collate, .create_loader), ILQLElement
+      trlx/pipeline/offline_pipeline.py, trlx/orchestrator/offline_orchestrator.py:17-74,
+      trlx/data/ilql_types.py (device-resident ragged store, one-launch padded collate)
   PPOHotPath — the fused device-resident experience+loss step (bench / DP shard)
   PPOControlState — RunningMoments / score scale+clip / KL controller state in HBM
 
@@ -34,6 +37,7 @@ from .lm_head import lm_head_logprobs
 from .rollout_store import PPORLBatch, PPORLElement, PPORolloutStorage
 from .ilql import ILQL_LOSS_KEYS, ILQLBatch, ILQLConfig, ILQLHotPath, ilql_sample_step
 from .ilql_heads import ILQLHeads, ilql_target_q_at_actions, make_head, polyak_update
+from .ilql_store import ILQLElement, ILQLRolloutStorage
 from .sampling import ppo_sample_step
 from .control import PPOControlState
 from .step import PPOHotPath
@@ -46,6 +50,7 @@ __all__ = [
     "prepare_scores", "stats_dict", "STATS_KEYS", "PPOHotPath", "load_library",
     "ILQLConfig", "ILQLBatch", "ILQLHotPath", "ILQL_LOSS_KEYS", "ilql_sample_step", "ppo_sample_step",
     "ILQLHeads", "ilql_target_q_at_actions", "polyak_update", "make_head", "PPORolloutStorage",
+    "ILQLRolloutStorage", "ILQLElement",
     "PPORLElement", "PPORLBatch", "lm_head_logprobs", "PPOControlState",
     "RcclComm", "shift_tokens_right", "get_model_inputs",
 ]

@@ -184,6 +184,9 @@ SIGNATURES = {
     "trlx_rows_copy": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                 _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_shift_tokens_right": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp]),
+    "trlx_ilql_collate": (_c_int, [_c_vp] * 9 + [_c_i64, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64]
+                          + [_c_vp, _c_i64] * 6 + [_c_vp]),
+    "trlx_ilql_build_fields": (_c_int, [_c_vp] * 6 + [_c_i64] * 4 + [_c_vp] * 6),
     "trlx_ctl_init": (_c_int, [_c_vp, _c_d, _c_d, _c_d, _c_int, _c_vp]),
     "trlx_score_moments": (_c_int, [_c_vp, _c_int, _c_i64, _c_vp, _c_vp]),
     "trlx_score_moments_signal": (_c_int, [_c_vp, _c_int, _c_i64, _c_vp, _c_vp, _c_vp]),

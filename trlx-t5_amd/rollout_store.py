@@ -197,9 +197,11 @@ class PPORolloutStorage:
 
 
 class RolloutLoader:
-    """Iterable of device PPORLBatch objects over a PPORolloutStorage snapshot."""
+    """Iterable of device batches over a snapshot of a store with __len__, .device and
+    .collate(idx, rows): PPORLBatch objects of a PPORolloutStorage, ILQLBatch objects of an
+    ILQLRolloutStorage (ilql_store.py)."""
 
-    def __init__(self, store: PPORolloutStorage, batch_size: int, shuffle: bool,
+    def __init__(self, store, batch_size: int, shuffle: bool,
                  generator: Optional[torch.Generator], drop_last: bool):
         self.store, self.batch_size, self.shuffle = store, int(batch_size), bool(shuffle)
         self.generator, self.drop_last = generator, drop_last
