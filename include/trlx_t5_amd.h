@@ -71,6 +71,8 @@ const char* trlx_last_error(void);
  *   "row_order"         resident rows: 0 (default) = step-major vectors, 1 = wave-major
  *   "split_lds"         long rows (fp32 V > 32 k, bf16 V > 32 k): 0 = split VGPR + LDS residency
  *                       for the loss / backward (default), 1 = off, 2 = also for the forward
+ *   "ilql_split"        ILQL fp32 rows in split residency (8192 < V/4 + 16 <= 12800; off with split_lds = 1):
+ *                       VGPR + LDS vector steps 0 = 20 + 5 (default), 1 = 22 + 3, 2 = 21 + 4, 3 = 19 + 6
  *   "split_mid"         mid-length bf16 rows (16k < V <= 32k) in the loss / backward: 0 auto (= 3),
  *                       1 = all in VGPRs, 2 = 5 VGPR + 3 LDS vector steps, 3 = 6 + 2 (8 waves/SIMD)
  *   "ragged_order"      ragged experience rows with an order scratch: 0 = valid rows first (default),

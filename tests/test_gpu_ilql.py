@@ -13,54 +13,14 @@ import torch
 
 import trlx_t5_amd as P
 from golden_util import T
-from oracle import ppo_oracle as orc
+from ilql_loss_checks import DEV, KEYS, check, make_case, run_gpu, run_oracle
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-KEYS = ("loss", "loss_q", "loss_v", "loss_cql", "loss_awac")
 
 
 def batch_from(z, k):
     return P.ILQLBatch(**{n: T(z[f"{k}/{n}"]) for n in
                           ("input_ids", "attention_mask", "rewards", "states_ixs", "actions_ixs", "dones")})
-
-
-def run_gpu(cfg, logits, qs, tqs, vs, batch, grad_scale=1.0):
-    lg = logits.to(DEV).requires_grad_(True)
-    q = [x.to(DEV).requires_grad_(True) for x in qs]
-    tq = [x.to(DEV) for x in tqs]
-    v = vs.to(DEV).requires_grad_(True)
-    b = P.ILQLBatch(*(getattr(batch, f).to(DEV) for f in ("input_ids", "attention_mask", "rewards", "states_ixs",
-                                                         "actions_ixs", "dones")))
-    loss, stats = cfg.loss((lg, (q, tq, v)), b)
-    assert list(stats) == [f"losses/{k}" for k in ("loss_q", "loss_v", "loss_cql", "loss_awac", "loss")]
-    (loss * grad_scale).backward()
-    torch.cuda.synchronize()
-    return (loss.detach().cpu(), {k: stats[f"losses/{k}"].detach().cpu() for k in KEYS}, lg.grad.cpu(),
-            [x.grad.cpu() for x in q], v.grad.cpu())
-
-
-def run_oracle(logits, qs, tqs, vs, batch, grad_scale=1.0, **kw):
-    lg = logits.float().requires_grad_(True)
-    q = [x.float().requires_grad_(True) for x in qs]
-    v = vs.float().requires_grad_(True)
-    loss, stats = orc.ilql_loss(lg, q, [x.float() for x in tqs], v, batch.input_ids, batch.attention_mask,
-                                batch.rewards, batch.actions_ixs, batch.dones, **kw)
-    (loss * grad_scale).backward()
-    return (loss.detach(), {k: stats[f"losses/{k}"].detach() for k in KEYS}, lg.grad, [x.grad for x in q],
-            v.grad)
-
-
-def check(got, want, grad_rtol=1e-5, grad_atol=1e-6):
-    gl, gs, gdl, gdq, gdv = got
-    wl, ws, wdl, wdq, wdv = want
-    torch.testing.assert_close(gl, wl.float(), rtol=1e-5, atol=1e-6)
-    for k in KEYS:
-        torch.testing.assert_close(gs[k], ws[k].float(), rtol=1e-5, atol=1e-6, msg=k)
-    torch.testing.assert_close(gdl.float(), wdl, rtol=grad_rtol, atol=grad_atol)
-    for a, b in zip(gdq, wdq):
-        torch.testing.assert_close(a.float(), b, rtol=grad_rtol, atol=grad_atol)
-    torch.testing.assert_close(gdv.float(), wdv, rtol=1e-5, atol=1e-6)
 
 
 @pytest.mark.parametrize("k", ["c0", "c1"])
@@ -107,33 +67,6 @@ def test_ilql_golden_wide(golden):
     np.testing.assert_allclose(float(dl.double().abs().sum()), float(z[f"{k}/dlogits_abs_sum"]), rtol=1e-5)
     np.testing.assert_allclose(float(dq[0].double().abs().sum()), float(z[f"{k}/dq0_abs_sum"]), rtol=1e-5)
     torch.testing.assert_close(dv, T(z[f"{k}/dvs"]), rtol=1e-5, atol=1e-6)
-
-
-def make_case(B, L, V, seed, dtype=torch.float32, prompt=1, ragged=True, nq=2, peaked=False):
-    """Synthetic ILQL batch in the offline orchestrator's layout (offline_orchestrator.py:
-    28-73): actions_ixs = arange(prompt-1, L-1), states one longer, dones 1 but the last."""
-    g = torch.Generator().manual_seed(seed)
-    A = L - prompt
-    ids = torch.randint(0, V, (B, L), generator=g)
-    ids[0, -1] = V - 1
-    ids[-1, 1] = 0
-    attn = torch.ones(B, L, dtype=torch.long)
-    dones = torch.ones(B, A + 1, dtype=torch.long)
-    dones[:, -1] = 0
-    if ragged and B > 1:  # padded rows (pad_sequence zeros) of different lengths
-        for r in range(1, B, 2):
-            cut = 1 + (r * 7) % (L - 1)
-            attn[r, cut:] = 0
-            dones[r, max(0, cut - prompt):] = 0
-    aix = torch.arange(prompt - 1, L - 1).repeat(B, 1)
-    six = torch.arange(prompt - 1, L).repeat(B, 1)
-    rewards = torch.randn(B, A, generator=g)
-    sc = 4.0 if peaked else 1.0
-    logits = (torch.randn(B, L, V, generator=g) * sc).to(dtype)
-    qs = [(torch.randn(B, A, V, generator=g) * sc).to(dtype) for _ in range(nq)]
-    tqs = [(torch.randn(B, A, V, generator=g) * sc).to(dtype) for _ in range(nq)]
-    vs = torch.randn(B, A + 1, 1, generator=g)
-    return logits, qs, tqs, vs, P.ILQLBatch(ids, attn, rewards, six, aix, dones)
 
 
 @pytest.mark.parametrize("B,L,V,prompt,nq,peaked", [

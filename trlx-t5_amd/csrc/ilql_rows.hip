@@ -282,10 +282,16 @@ __global__ __launch_bounds__(NL ? 512 : kMaxThreads, NL ? 4 : 1) void k_ilql_row
     sum = block_sum(sum, sh_sum);
 #pragma unroll
     for (int k = 0; k < NV; ++k) launder(v[k]);
-    const float lse = m + logf(sum);
+    // The exponent offset ml2e = -m·log2e is rounded: every term above carries 2^d, d the exact
+    // residual m·log2e + ml2e (fma).  Undone once per row, as k_vocab_rows does: at |m| ~ 100 it is
+    // ~4e-6 of the lse, which a one-element row (ce = 0) or a Q head of that scale shows.
+    const float dm = isfinite(m) ? fmaf(m, kLog2e, ml2e) : 0.0f;
+    const float lse = m + (logf(sum) - dm * kLn2);
 
     // (the reductions' barriers order thread 0's s_sc writes before these reads)
-    const float g = s_sc[0];
+    // A row whose token could not be gathered (y outside [0, V)) has NaN records; its whole
+    // gradient row is NaN too, not the softmax half alone.
+    const float g = y_ok ? s_sc[0] : NAN;
     float dQ = 0.0f, d = 0.0f;
     if (id.head >= 0) {  // TD term: ((Q - Qt)·w)², its gradient lands on the action element
         const float w = s_sc[1];
@@ -293,11 +299,14 @@ __global__ __launch_bounds__(NL ? 512 : kMaxThreads, NL ? 4 : 1) void k_ilql_row
         dQ = mul_rn(mul_rn(s_sc[3], mul_rn(2.0f, d)), w);
     }
     const float lse_l2e = -lse * kLog2e;
-    const float gy = add_rn(g * (1.0f - exp2_fast(fmaf(xy, kLog2e, lse_l2e))), dQ);
-    if (je >= 0) DT::store1(dx, je, je == y ? gy : -g * exp2_fast(fmaf(ex, kLog2e, lse_l2e)));
+    // likewise 2^(x·log2e + lse_l2e) = softmax(x) · 2^d2; the row factor 2^-d2 rides on g
+    const float corr = isfinite(lse) ? exp2_fast(-fmaf(lse, kLog2e, lse_l2e)) : 1.0f;
+    const float ng = -g * corr;
+    const float gy = add_rn(g * (1.0f - corr * exp2_fast(fmaf(xy, kLog2e, lse_l2e))), dQ);
+    if (je >= 0) DT::store1(dx, je, je == y ? gy : ng * exp2_fast(fmaf(ex, kLog2e, lse_l2e)));
     const __amdgpu_buffer_rsrc_t rout = make_rsrc(dx + s.head, uint32_t(nvec) * 16u);
     const int iy = y_ok && y >= s.head && y < s.tail0 ? int((y - s.head) / EPV) : -1;
-    const f32x2 c2 = f2_splat(lse_l2e), ng2 = f2_splat(-g);
+    const f32x2 c2 = f2_splat(lse_l2e), ng2 = f2_splat(ng);
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         const int i = tid - shift + k * nthr;  // lanes outside the body: range-checked away
