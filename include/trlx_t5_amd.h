@@ -560,6 +560,36 @@ int trlx_ppo_sample(const void* logits, int64_t ld_logits, int dtype, int64_t B,
                     const float* u, int64_t* out_ids, float* out_logprobs, float* out_min_kept,
                     int32_t* out_kept_count, int64_t* unfinished, void* stream);
 
+/* The recording step: trlx_ppo_sample (the same arguments, the same policy-row path: token,
+ * out_logprobs, out_min_kept and out_kept_count are bit-identical) that also scores the token
+ * under the reference model's row of the same step and writes column t of the rollout's
+ * [B, T] buffers, so no teacher-forced second pass over [B, T, V] logits is needed
+ * (ppo_orchestrator.py:116-161):
+ *   ref_logits: [B, V] rows of ref_dtype (must equal dtype), row stride ld_ref, streamed once
+ *   and reduced to (max, sum exp) in fp32 in a fixed order;
+ *   tokens[b, t] = out_ids[b];  logprobs[b, t] = out_logprobs[b];
+ *   ref_logprobs[b, t] = log_softmax(ref_logits[b])[out_ids[b]];
+ *   values[b, t] = step_values[b] (values_dtype TRLX_F32 / TRLX_BF16; both NULL = none);
+ *   lengths[b] = t + 1 where a live row returns eos (NULL = not kept; a row that stays live
+ *   leaves its entry untouched: the caller initialises lengths to T).
+ * Finished rows (unfinished[b] == 0): score_finished = 0 writes pad, 0, 0 and value 0 and reads
+ * neither row (the ragged convention of the experience kernels); score_finished = 1 writes pad
+ * and the log-softmax of both rows at pad (also to out_logprobs[b]) and the value as given —
+ * what a teacher-forced pass with an all-ones mask stores after eos — with no selection and no
+ * draw; the row stays finished either way.  A live row with no finite policy logit records pad, 0, 0.
+ * Record buffers: row strides in elements, each >= T; 0 <= t < T.  Launch table and vocab
+ * limit as trlx_ppo_sample. */
+int trlx_ppo_sample_record(const void* logits, int64_t ld_logits, int dtype, int64_t B, int64_t V,
+                           float temperature, int top_k, float top_p, int min_tokens_to_keep,
+                           int64_t cur_len, int64_t min_length, int64_t eos_token_id, int64_t pad_token_id,
+                           const float* u, int64_t* out_ids, float* out_logprobs, float* out_min_kept,
+                           int32_t* out_kept_count, int64_t* unfinished, const void* ref_logits,
+                           int64_t ld_ref, int ref_dtype, int64_t t, int64_t T, int64_t* tokens,
+                           int64_t ld_tokens, float* logprobs, int64_t ld_logprobs, float* ref_logprobs,
+                           int64_t ld_ref_logprobs, float* values, int64_t ld_values,
+                           const void* step_values, int values_dtype, int64_t* lengths,
+                           int score_finished, void* stream);
+
 /* ---------------------------------------------------------------- §8f: device-resident rollout store
  * Row copy between padded columnar [rows, W] buffers — replaces the reference's
  * `.cpu()` of the experience tensors, per-sample PPORLElement lists and the pad_sequence

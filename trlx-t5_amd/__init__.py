@@ -16,6 +16,10 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
   ppo_sample_step — one rollout token of generate(**gen_kwargs): min length, temperature,
       top-k, top-p, the draw, unfinished / pad, and the token's policy log-prob
       trlx/orchestrator/ppo_orchestrator.py:76 (HF generate's sample path)
+  PPORolloutRecorder + ppo_sample_step(ref_logits=, recorder=) — the decode loop records
+      tokens, policy and reference log-probs and values per step; with
+      PPOHotPath.experience_from_logprobs the teacher-forced second pass over [B, T, V] logits
+      goes away      trlx/orchestrator/ppo_orchestrator.py:116-167
   lm_head_logprobs — fused lm_head GEMM (MFMA) + logprobs, logits never in HBM
   PPORolloutStorage, PPORLElement, PPORLBatch
       trlx/pipeline/ppo_pipeline.py, trlx/data/ppo_types.py (device-resident store)
@@ -34,7 +38,7 @@ from .modeling import (RunningMoments, flatten_dict, get_global_statistics, grad
 from .ppo import (STATS_KEYS, AdaptiveKLController, FixedKLController, PPOConfig, kl_penalty_rewards,
                   prepare_scores, stats_dict)
 from .lm_head import lm_head_logprobs
-from .rollout_store import PPORLBatch, PPORLElement, PPORolloutStorage
+from .rollout_store import PPORLBatch, PPORLElement, PPORolloutRecorder, PPORolloutStorage
 from .ilql import ILQL_LOSS_KEYS, ILQLBatch, ILQLConfig, ILQLHotPath, ilql_sample_step
 from .ilql_heads import ILQLHeads, ilql_target_q_at_actions, make_head, polyak_update
 from .ilql_store import ILQLElement, ILQLRolloutStorage
@@ -50,6 +54,7 @@ __all__ = [
     "prepare_scores", "stats_dict", "STATS_KEYS", "PPOHotPath", "load_library",
     "ILQLConfig", "ILQLBatch", "ILQLHotPath", "ILQL_LOSS_KEYS", "ilql_sample_step", "ppo_sample_step",
     "ILQLHeads", "ilql_target_q_at_actions", "polyak_update", "make_head", "PPORolloutStorage",
+    "PPORolloutRecorder",
     "ILQLRolloutStorage", "ILQLElement",
     "PPORLElement", "PPORLBatch", "lm_head_logprobs", "PPOControlState",
     "RcclComm", "shift_tokens_right", "get_model_inputs",

@@ -181,6 +181,10 @@ SIGNATURES = {
                                   _c_i64, _c_i64, _c_f, _c_int, _c_f, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp]),
     "trlx_ppo_sample": (_c_int, [_c_vp, _c_i64, _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_f, _c_int, _c_i64, _c_i64,
                                  _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp]),
+    "trlx_ppo_sample_record": (_c_int, [_c_vp, _c_i64, _c_int, _c_i64, _c_i64, _c_f, _c_int, _c_f, _c_int, _c_i64,
+                                        _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                        _c_vp, _c_i64, _c_int, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp,
+                                        _c_i64, _c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_int, _c_vp]),
     "trlx_rows_copy": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                 _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_shift_tokens_right": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp]),

@@ -23,6 +23,8 @@
 // summed in the order the waves filled it, and feed comparisons with top_p * W only.
 #include "common.h"
 
+#include <type_traits>
+
 namespace trlx {
 
 struct PpoSampleArgs {
@@ -43,6 +45,26 @@ struct PpoSampleArgs {
     int64_t* unfinished; // [B] in/out (0/1), NULL = all live
 };
 
+// The recording step (trlx_ppo_sample_record): the reference model's row of the same step and
+// column t of the rollout's [B, T] buffers (row strides in elements).
+struct PpoRecordArgs {
+    const void* ref_logits;  // [B, V] rows of ld_ref, the dtype of the policy rows
+    int64_t ld_ref;
+    int64_t t;               // the column written
+    int64_t* tokens;         // [B, T] int64
+    int64_t ld_tokens;
+    float* lp;               // [B, T] policy log-prob of the token
+    int64_t ld_lp;
+    float* ref_lp;           // [B, T] reference log-prob of the token
+    int64_t ld_ref_lp;
+    float* values;           // [B, T] or NULL
+    int64_t ld_values;
+    const void* v;           // [B] this step's values (v_dtype), NULL with values
+    int v_dtype;
+    int score_finished;      // finished rows: log-softmax of both rows at pad (else 0 and no read)
+    int64_t* lengths;        // [B] or NULL: t + 1 where a live row returns eos
+};
+
 // order-preserving float -> uint32 (a larger float has a larger key) and back
 __device__ __forceinline__ uint32_t fkey(float f) {
     const uint32_t u = __float_as_uint(f);
@@ -55,8 +77,27 @@ __device__ __forceinline__ float fkey_inv(uint32_t k) {  // NaN for keys no floa
 constexpr int kPsCandCap = 512;   // candidate list in LDS, one per thread at most
 constexpr int kPsSeed = 128;      // list size aimed at when top-p runs without top-k
 
-template <class DT, int NV, int NT>
-__global__ __launch_bounds__(NT) void k_ppo_sample(PpoSampleArgs a) {
+struct PpoSampleRecArgs {
+    PpoSampleArgs s;
+    PpoRecordArgs r;
+};
+__device__ __forceinline__ const PpoSampleArgs& sample_args(const PpoSampleArgs& a) { return a; }
+__device__ __forceinline__ const PpoSampleArgs& sample_args(const PpoSampleRecArgs& a) { return a.s; }
+__device__ __forceinline__ PpoRecordArgs record_args(const PpoSampleArgs&) { return PpoRecordArgs{}; }
+__device__ __forceinline__ PpoRecordArgs record_args(const PpoSampleRecArgs& a) { return a.r; }
+
+// One row's step.  REC: the recording step — the reference row is reduced to per-wave
+// (max, sum exp) pairs first, parked in LDS (nothing of it stays in registers while the
+// policy row is held), and the thread that finds the token reads x_ref[token] beside x[token].
+// The lambdas that the larger body would otherwise leave as calls are always_inline: a call
+// takes the row's registers by reference, which puts the row in scratch.
+// (One kernel template, not a shared device function called by two kernels: through such a
+// wrapper hipcc 7.2 schedules the plain step differently — 89 -> 128 VGPRs + 52 B scratch at
+// bf16 4 x 1024.  REC = false compiles to the kernel this file had before the recording step.)
+template <class DT, int NV, int NT, bool REC = false>
+__global__ __launch_bounds__(NT) void k_ppo_sample(std::conditional_t<REC, PpoSampleRecArgs, PpoSampleArgs> args) {
+    const PpoSampleArgs& a = sample_args(args);
+    const PpoRecordArgs r = record_args(args);
     constexpr int kWaves = NT / kWave;
     typedef typename DT::elem_t E;
     constexpr int EPV = DT::kEPV;
@@ -89,10 +130,87 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(PpoSampleArgs a) {
         a.out_min[b] = mn;
         a.out_cnt[b] = n;
     };
-    if (a.unfinished && a.unfinished[b] == 0) {  // a finished row emits pad and stays finished
+    // column t of the rollout's buffers (one thread); scored: the row was read, else 0 / 0 / 0
+    auto record = [&](int64_t tok, float lp, float rlp, bool scored, bool live) __attribute__((always_inline)) {
+        r.tokens[b * r.ld_tokens + r.t] = tok;
+        r.lp[b * r.ld_lp + r.t] = lp;
+        r.ref_lp[b * r.ld_ref_lp + r.t] = rlp;
+        if (r.values) r.values[b * r.ld_values + r.t] = scored ? ld_any(r.v, r.v_dtype, b) : 0.f;
+        if (live && r.lengths && a.eos >= 0 && tok == a.eos) r.lengths[b] = r.t + 1;
+    };
+    [[maybe_unused]] bool pad_scored = false;  // the recording step's finished row that still scores pad
+    if constexpr (REC) {
+        const bool finished = a.unfinished && a.unfinished[b] == 0;
+        pad_scored = finished && r.score_finished;
+        if (finished && !pad_scored) {  // pad, 0, 0; neither row is read
+            if (tid == 0) {
+                finish(padtok, 0.f, 0.f, 0);
+                record(padtok, 0.f, 0.f, false, false);
+            }
+            return;
+        }
+    } else if (a.unfinished && a.unfinished[b] == 0) {  // a finished row emits pad and stays finished
         if (tid == 0) finish(padtok, 0.f, 0.f, 0);
         return;
     }
+
+    // ---- recording step: the reference row, streamed once on its own head / body / tail split
+    // and line shift: per-thread online (max, sum exp) in fp32 over the steps in order, then the
+    // wave's pair in LDS.  The pairs are combined in wave order by ref_logprob(), after the
+    // barrier that the policy row's statistics take below.
+    __shared__ float r_max[REC ? kWaves : 1], r_sum[REC ? kWaves : 1], s_rlp;
+    const E* xr = nullptr;
+    if constexpr (REC) {
+        xr = reinterpret_cast<const E*>(r.ref_logits) + b * r.ld_ref;
+        const RowSplit<DT> sr(xr, V);
+        const int nvr = int(sr.nvec);
+        const int shr = line_shift(xr + sr.head);
+        const __amdgpu_buffer_rsrc_t rr = make_rsrc(xr + sr.head, uint32_t(nvr) * 16u);
+        vec4u raw[NV];
+#pragma unroll
+        for (int k = 0; k < NV; ++k)
+            raw[k] = __builtin_amdgcn_raw_buffer_load_b128(rr, (tid - shr) * 16 + k * NT * 16, 0, kAuxNT);
+        int64_t jr = -1;
+        if (tid < sr.head) jr = tid;
+        else if (tid >= NT - sr.tail) jr = sr.tail0 + (tid - (NT - sr.tail));
+        float rm = jr >= 0 ? DT::load1(xr, jr) : -INFINITY;
+        float rs = rm == -INFINITY ? 0.f : 1.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            if (unsigned(tid - shr + k * NT) >= unsigned(nvr)) continue;  // outside the row: reads 0
+            float g[EPV];
+            DT::unpack(raw[k], g);
+            float vm = g[0];
+#pragma unroll
+            for (int e = 1; e < EPV; ++e) vm = fmaxf(vm, g[e]);
+            if (vm > rm) {  // rescale what is summed so far (0 while rm = -inf)
+                rs *= exp2_fast((rm - vm) * kLog2e);
+                rm = vm;
+            }
+            if (rm != -INFINITY) {
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) rs += exp2_fast((g[e] - rm) * kLog2e);
+            }
+        }
+        const float wm = wave_max(rm);
+        rs = rm == -INFINITY ? 0.f : rs * exp2_fast((rm - wm) * kLog2e);
+        rs = wave_sum(rs);
+        if (lane == 0) {
+            r_max[wv] = wm;
+            r_sum[wv] = rs;
+        }
+    }
+    // log_softmax(x_ref)[tok] (one thread, after a barrier): the difference first, as for the policy row
+    auto ref_logprob = [&](int64_t tok) __attribute__((always_inline)) {
+        float m = r_max[0];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) m = fmaxf(m, r_max[w]);
+        float sum = 0.f;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w)
+            if (r_max[w] != -INFINITY) sum += r_sum[w] * exp2_fast((r_max[w] - m) * kLog2e);
+        return (DT::load1(xr, tok) - m) - logf(sum);
+    };
 
     const E* x = reinterpret_cast<const E*>(a.logits) + b * a.ld_logits;
     const RowSplit<DT> s(x, V);
@@ -162,6 +280,16 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(PpoSampleArgs a) {
     // log_softmax(x)[j] = (x_j - m) - log(sum): the difference first, so a token that holds
     // nearly all the mass keeps a log-prob near 0 to fp32 relative precision
     const float row_max = m, log_sum = float(log(sum));
+    if constexpr (REC) {
+        if (pad_scored) {  // block-uniform: no selection, no draw, the row stays finished
+            if (tid == 0) {
+                const float lp = (DT::load1(x, padtok) - row_max) - log_sum;
+                finish(padtok, lp, 0.f, 0);
+                record(padtok, lp, ref_logprob(padtok), true, false);
+            }
+            return;
+        }
+    }
 
     // ---- min length: the thread that holds x[eos] drops it; the row maximum again
     float xmax = m;
@@ -189,6 +317,7 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(PpoSampleArgs a) {
     if (xmax == -INFINITY) {  // no finite logit left (HF's multinomial would raise): pad, nothing kept
         if (tid == 0) {
             finish(padtok, 0.f, 0.f, 0);
+            if constexpr (REC) record(padtok, 0.f, 0.f, true, true);
             if (a.unfinished && a.eos >= 0) a.unfinished[b] = padtok != a.eos ? 1 : 0;
         }
         return;
@@ -243,7 +372,7 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(PpoSampleArgs a) {
     // #(key >= K) >= n IS the n-th largest key.  The candidate is turned into a float, not
     // every x into a key; float >= is monotone in the key, and candidates in the NaN key
     // ranges (skipped) would count 0.  Fewer than n finite values: -inf, all of them kept.
-    auto nth_largest = [&](int n) {
+    auto nth_largest = [&](int n) __attribute__((always_inline)) {
         uint32_t K = 0;
 #pragma unroll 1
         for (int bit = 31; bit >= 0; --bit) {
@@ -504,6 +633,7 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(PpoSampleArgs a) {
         s_pick[2] = int(pick);
         // the row's registers hold weights by now: the drawn logit comes from memory again
         if (pick >= 0) s_lp = (DT::load1(x, pick) - row_max) - log_sum;
+        if constexpr (REC) s_rlp = pick >= 0 ? ref_logprob(pick) : 0.f;
     }
     __syncthreads();
     if (tid == 0) {
@@ -516,6 +646,7 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(PpoSampleArgs a) {
         const bool got = s_pick[2] >= 0;
         const int64_t tok = got ? s_pick[2] : padtok;
         finish(tok, got ? s_lp : 0.f, got ? mnk : 0.f, got ? n : 0);
+        if constexpr (REC) record(tok, got ? s_lp : 0.f, got ? s_rlp : 0.f, true, true);
         if (a.unfinished && a.eos >= 0) a.unfinished[b] = tok != a.eos ? 1 : 0;
     }
 }
@@ -524,13 +655,14 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(PpoSampleArgs a) {
 
 using namespace trlx;
 
-extern "C" int trlx_ppo_sample(const void* logits, int64_t ld_logits, int dtype, int64_t B, int64_t V,
-                               float temperature, int top_k, float top_p, int min_tokens_to_keep,
-                               int64_t cur_len, int64_t min_length, int64_t eos_token_id, int64_t pad_token_id,
-                               const float* u, int64_t* out_ids, float* out_logprobs, float* out_min_kept,
-                               int32_t* out_kept_count, int64_t* unfinished, void* stream) {
+// Both entries: the arguments they share, one launch table.  rec = NULL: the plain step.
+static int ppo_sample_launch(const char* who, const void* logits, int64_t ld_logits, int dtype, int64_t B, int64_t V,
+                             float temperature, int top_k, float top_p, int min_tokens_to_keep, int64_t cur_len,
+                             int64_t min_length, int64_t eos_token_id, int64_t pad_token_id, const float* u,
+                             int64_t* out_ids, float* out_logprobs, float* out_min_kept, int32_t* out_kept_count,
+                             int64_t* unfinished, const PpoRecordArgs* rec, void* stream) {
     TRLX_REQUIRE(B == 0 || (logits && u && out_ids && out_logprobs && out_min_kept && out_kept_count), TRLX_ERR_ARG,
-                 "NULL argument to trlx_ppo_sample");
+                 "NULL argument to %s", who);
     TRLX_REQUIRE(dtype == TRLX_F32 || dtype == TRLX_BF16, TRLX_ERR_DTYPE, "dtype %d", dtype);
     TRLX_REQUIRE(B >= 0 && V > 0, TRLX_ERR_SHAPE, "bad shape");
     TRLX_REQUIRE(temperature > 0.f && top_p > 0.f && top_k >= 0 && min_tokens_to_keep >= 1, TRLX_ERR_ARG,
@@ -560,10 +692,15 @@ extern "C" int trlx_ppo_sample(const void* logits, int64_t ld_logits, int dtype,
     auto need = [&](int nt) { return (V / epv + 1 + (kLineVecs - 1) + nt - 1) / nt; };  // vectors per thread
     // (the table of trlx_ilql_sample without its 128-VGPR rows — 16 x 8 bf16, 32 x 4 fp32 — which
     // cannot hold the row beside this kernel's state without scratch: rows end at ~53k entries)
-#define TRLX_PSMP(DTT, N, NT)                                                                            \
-    if (need(NT) <= N) {                                                                                 \
+#define TRLX_PSMP(DTT, N, NT)                                                                                  \
+    if (need(NT) <= N) {                                                                                       \
+        if (rec) {                                                                                             \
+            hipLaunchKernelGGL((k_ppo_sample<DTT, N, NT, true>), dim3(unsigned(B)), dim3(NT), 0,               \
+                               (hipStream_t)stream, PpoSampleRecArgs{a, *rec});                                \
+            return check_launch("k_ppo_sample<record>");                                                       \
+        }                                                                                                      \
         hipLaunchKernelGGL((k_ppo_sample<DTT, N, NT>), dim3(unsigned(B)), dim3(NT), 0, (hipStream_t)stream, a); \
-        return check_launch("k_ppo_sample");                                                             \
+        return check_launch("k_ppo_sample");                                                                   \
     }
     if (dtype == TRLX_BF16) {
         TRLX_PSMP(BF16T, 1, 1024)
@@ -579,4 +716,59 @@ extern "C" int trlx_ppo_sample(const void* logits, int64_t ld_logits, int dtype,
     }
 #undef TRLX_PSMP
     TRLX_REQUIRE(false, TRLX_ERR_SHAPE, "vocab %lld too long for the sampling kernel", (long long)V);
+}
+
+extern "C" int trlx_ppo_sample(const void* logits, int64_t ld_logits, int dtype, int64_t B, int64_t V,
+                               float temperature, int top_k, float top_p, int min_tokens_to_keep,
+                               int64_t cur_len, int64_t min_length, int64_t eos_token_id, int64_t pad_token_id,
+                               const float* u, int64_t* out_ids, float* out_logprobs, float* out_min_kept,
+                               int32_t* out_kept_count, int64_t* unfinished, void* stream) {
+    return ppo_sample_launch("trlx_ppo_sample", logits, ld_logits, dtype, B, V, temperature, top_k, top_p,
+                             min_tokens_to_keep, cur_len, min_length, eos_token_id, pad_token_id, u, out_ids,
+                             out_logprobs, out_min_kept, out_kept_count, unfinished, nullptr, stream);
+}
+
+extern "C" int trlx_ppo_sample_record(const void* logits, int64_t ld_logits, int dtype, int64_t B, int64_t V,
+                                      float temperature, int top_k, float top_p, int min_tokens_to_keep,
+                                      int64_t cur_len, int64_t min_length, int64_t eos_token_id,
+                                      int64_t pad_token_id, const float* u, int64_t* out_ids, float* out_logprobs,
+                                      float* out_min_kept, int32_t* out_kept_count, int64_t* unfinished,
+                                      const void* ref_logits, int64_t ld_ref, int ref_dtype, int64_t t, int64_t T,
+                                      int64_t* tokens, int64_t ld_tokens, float* logprobs, int64_t ld_logprobs,
+                                      float* ref_logprobs, int64_t ld_ref_logprobs, float* values, int64_t ld_values,
+                                      const void* step_values, int values_dtype, int64_t* lengths,
+                                      int score_finished, void* stream) {
+    TRLX_REQUIRE(B == 0 || (ref_logits && tokens && logprobs && ref_logprobs), TRLX_ERR_ARG,
+                 "NULL argument to trlx_ppo_sample_record (ref_logits, tokens, logprobs, ref_logprobs)");
+    TRLX_REQUIRE(ref_dtype == dtype, TRLX_ERR_DTYPE, "reference rows of dtype %d, policy rows of dtype %d", ref_dtype,
+                 dtype);
+    TRLX_REQUIRE(T > 0 && t >= 0 && t < T, TRLX_ERR_SHAPE, "column t = %lld outside [0, T = %lld)", (long long)t,
+                 (long long)T);
+    TRLX_REQUIRE(ld_tokens >= T && ld_logprobs >= T && ld_ref_logprobs >= T && (!values || ld_values >= T),
+                 TRLX_ERR_SHAPE, "a record buffer's row stride is below T = %lld", (long long)T);
+    TRLX_REQUIRE(B <= 1 || V <= 0 || (ld_logits >= V && ld_ref >= V), TRLX_ERR_SHAPE,
+                 "row strides %lld / %lld below V = %lld", (long long)ld_logits, (long long)ld_ref, (long long)V);
+    TRLX_REQUIRE((values == nullptr) == (step_values == nullptr), TRLX_ERR_ARG,
+                 "values (the [B, T] buffer) and step_values (this step's [B]) go together");
+    TRLX_REQUIRE(!values || values_dtype == TRLX_F32 || values_dtype == TRLX_BF16, TRLX_ERR_DTYPE,
+                 "step_values dtype %d", values_dtype);
+    PpoRecordArgs r = {};
+    r.ref_logits = ref_logits;
+    r.ld_ref = ld_ref;
+    r.t = t;
+    r.tokens = tokens;
+    r.ld_tokens = ld_tokens;
+    r.lp = logprobs;
+    r.ld_lp = ld_logprobs;
+    r.ref_lp = ref_logprobs;
+    r.ld_ref_lp = ld_ref_logprobs;
+    r.values = values;
+    r.ld_values = ld_values;
+    r.v = step_values;
+    r.v_dtype = values_dtype;
+    r.score_finished = score_finished != 0;
+    r.lengths = lengths;
+    return ppo_sample_launch("trlx_ppo_sample_record", logits, ld_logits, dtype, B, V, temperature, top_k, top_p,
+                             min_tokens_to_keep, cur_len, min_length, eos_token_id, pad_token_id, u, out_ids,
+                             out_logprobs, out_min_kept, out_kept_count, unfinished, &r, stream);
 }

@@ -275,7 +275,8 @@ class PPOConfig:
         sampling chain of `generate(**gen_kwargs)` (ppo_orchestrator.py:76) as one launch; see
         sampling.ppo_sample_step.  Reads temperature, top_k, top_p, min_length, eos_token_id and
         pad_token_id; `do_sample: False` (greedy) maps to top_k = 1.  `overrides` are passed on
-        (u=, out=, generator=, or any of the keys above).  Returns (ids [B, 1], logprobs [B])."""
+        (u=, out=, generator=, the recording step's ref_logits=, recorder=, values=,
+        score_finished=, or any of the keys above).  Returns (ids [B, 1], logprobs [B])."""
         from .sampling import ppo_sample_step
         gk = self.gen_kwargs
         kw = {k: gk[k] for k in ("temperature", "top_k", "top_p", "min_length", "eos_token_id", "pad_token_id")

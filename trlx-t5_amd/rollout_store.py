@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["PPORLElement", "PPORLBatch", "PPORolloutStorage", "RolloutLoader"]
+__all__ = ["PPORLElement", "PPORLBatch", "PPORolloutStorage", "PPORolloutRecorder", "RolloutLoader"]
 
 
 @dataclass
@@ -194,6 +194,92 @@ class PPORolloutStorage:
         """Batches of the stored rollouts (ppo_pipeline.py:34-68 / torch DataLoader order:
         sequential, or a torch.randperm permutation when shuffle)."""
         return RolloutLoader(self, batch_size, shuffle, generator, drop_last)
+
+
+class PPORolloutRecorder:
+    """The columnar [B, T] buffers of one rollout chunk, filled one column per decode step by the
+    recording sampling step (sampling.ppo_sample_step(..., ref_logits=, recorder=), one launch of
+    trlx_ppo_sample_record): what ppo_orchestrator.py:76-167 obtains from generate() plus a
+    second, teacher-forced pass of the policy and the reference model over [B, T, V] logits.
+
+      tokens [B, T] int64 (pad)        logprobs / ref_logprobs [B, T] fp32 (0)
+      values [B, T] fp32 (0)           lengths [B] int64 (T)      unfinished [B] int64 (1)
+      t: the next column
+
+    Allocated once; a step allocates nothing here.  hot_path: a PPOHotPath of the same B and T —
+    logprobs / ref_logprobs are then its own lp_old / ref_lp, so
+    PPOHotPath.experience_from_logprobs() reads them with no copy.  reset() re-arms the
+    recorder for the next chunk; push_to() hands the chunk to a PPORolloutStorage."""
+
+    def __init__(self, B: int, T: int, device, pad_token_id: int, eos_token_id: Optional[int], hot_path=None):
+        self.B, self.T = int(B), int(T)
+        if self.B < 1 or self.T < 1:
+            raise ValueError("PPORolloutRecorder needs B >= 1 and T >= 1")
+        self.device = torch.device(device)
+        if pad_token_id is None:
+            raise ValueError("PPORolloutRecorder needs pad_token_id (the token of a finished row)")
+        self.pad_token_id = int(pad_token_id)
+        self.eos_token_id = None if eos_token_id is None else int(eos_token_id)
+        dev = self.device
+        if hot_path is not None:
+            if (hot_path.B, hot_path.T) != (self.B, self.T) or hot_path.device != dev:
+                raise ValueError(f"hot path ({hot_path.B},{hot_path.T}) on {hot_path.device} does not match the "
+                                 f"recorder ({self.B},{self.T}) on {dev}")
+            self.logprobs, self.ref_logprobs = hot_path.lp_old, hot_path.ref_lp
+        else:
+            self.logprobs = torch.empty((self.B, self.T), dtype=torch.float32, device=dev)
+            self.ref_logprobs = torch.empty((self.B, self.T), dtype=torch.float32, device=dev)
+        self.hot_path = hot_path
+        self.tokens = torch.empty((self.B, self.T), dtype=torch.int64, device=dev)
+        self.values = torch.empty((self.B, self.T), dtype=torch.float32, device=dev)
+        self.lengths = torch.empty(self.B, dtype=torch.int64, device=dev)
+        self.unfinished = torch.empty(self.B, dtype=torch.int64, device=dev)
+        self.t = 0
+        self.reset()
+
+    def reset(self):
+        """Re-arm for the next chunk: column 0, every row live, the buffers' initial contents."""
+        self.tokens.fill_(self.pad_token_id)
+        self.logprobs.zero_()
+        self.ref_logprobs.zero_()
+        self.values.zero_()
+        self.lengths.fill_(self.T)
+        self.unfinished.fill_(1)
+        self.t = 0
+
+    def _step_inputs(self, logits, ref_logits, values, pad_token_id, eos_token_id, unfinished):
+        """The recording step's argument checks (all before any launch) -> (pad, eos, unfinished)."""
+        B, V = logits.shape
+        if B != self.B:
+            raise ValueError(f"logits have {B} rows, the recorder {self.B}")
+        if self.t >= self.T:
+            raise ValueError(f"the recorder is full (t = {self.t} = T): reset() starts the next chunk")
+        if logits.device != self.device:
+            raise ValueError(f"logits on {logits.device}, the recorder on {self.device}")
+        if not isinstance(ref_logits, torch.Tensor) or tuple(ref_logits.shape) != (B, V) or \
+                ref_logits.dtype != logits.dtype or ref_logits.device != logits.device:
+            raise ValueError(f"ref_logits must be [{B}, {V}] {logits.dtype} on {logits.device} like logits")
+        if values is not None and (tuple(values.shape) != (B,) or not values.is_contiguous() or
+                                   values.device != self.device or
+                                   values.dtype not in (torch.float32, torch.bfloat16)):
+            raise ValueError(f"values must be a contiguous fp32 / bf16 [{B}] tensor on {self.device}")
+        if pad_token_id is not None and int(pad_token_id) != self.pad_token_id:
+            raise ValueError(f"pad_token_id {pad_token_id} is not the recorder's ({self.pad_token_id})")
+        if eos_token_id is not None and self.eos_token_id is not None and int(eos_token_id) != self.eos_token_id:
+            raise ValueError(f"eos_token_id {eos_token_id} is not the recorder's ({self.eos_token_id})")
+        eos = self.eos_token_id if eos_token_id is None else int(eos_token_id)
+        return self.pad_token_id, eos, (self.unfinished if unfinished is None else unfinished)
+
+    def push_to(self, store: "PPORolloutStorage", query_tensors, rewards):
+        """One PPORolloutStorage.push_batch of the first t columns: queries [B, Wq], rewards
+        [B, >= t] (PPOHotPath.rewards), responses / logprobs / values from the recorder."""
+        t = self.t
+        if t < 1:
+            raise ValueError("nothing recorded yet")
+        if rewards.dim() != 2 or rewards.shape[0] != self.B or rewards.shape[1] < t:
+            raise ValueError(f"rewards must be [{self.B}, >= {t}], got {tuple(rewards.shape)}")
+        store.push_batch(query_tensors, self.tokens[:, :t], self.logprobs[:, :t], self.values[:, :t],
+                         rewards[:, :t])
 
 
 class RolloutLoader:

@@ -315,6 +315,34 @@ class PPOHotPath:
         self._experience_tail(s, labels, old_values, scores, lengths, mask, group, g_mom, work)
         return self.lp_old, self.ref_lp
 
+    def experience_from_logprobs(self, labels, old_values, scores, logprobs=None, ref_logprobs=None, lengths=None,
+                                 mask=None, group=None):
+        """K1 without the logits rows: the serial experience() from per-token log-probs that
+        the decode loop already recorded (sampling.ppo_sample_step with a PPORolloutRecorder) —
+        the same preconditions, _begin_step and GAE tail, no pass over [B, T, V] logits.
+        logprobs / ref_logprobs: fp32 [B, T] on this device, copied into lp_old / ref_lp unless
+        they are those buffers already (a recorder built with hot_path=self) or None (lp_old /
+        ref_lp are used as they stand).  With the same lp_old / ref_lp the results equal
+        experience()'s bit for bit.  Serial schedule only: pipeline_step's two-launch shape folds
+        each tail into an experience or loss rows launch, and this route has no experience rows
+        launch to fold into."""
+        self._no_pipeline_pending("experience_from_logprobs")
+        B, T = self.B, self.T
+        for t, own, name in ((logprobs, self.lp_old, "logprobs"), (ref_logprobs, self.ref_lp, "ref_logprobs")):
+            if t is not None and (tuple(t.shape) != (B, T) or t.dtype != torch.float32 or t.device != self.device):
+                raise ValueError(f"{name} must be fp32 [{B}, {T}] on {self.device}, got {tuple(t.shape)}/{t.dtype} "
+                                 f"on {t.device}")
+        labels, lengths, mask, old_values, scores = self._rollout_inputs(labels, lengths, mask, old_values, scores)
+        s = torch.cuda.current_stream(self.device)
+        self._launch_pending_tail(s)  # a deferred loss tail has no rows launch to ride here
+        self._use_split(self.split_beta, 0)
+        g_mom, work = self._begin_step(scores, group, s)
+        for t, own in ((logprobs, self.lp_old), (ref_logprobs, self.ref_lp)):
+            if t is not None and (t.data_ptr() != own.data_ptr() or t.stride() != own.stride()):
+                own.copy_(t)
+        self._experience_tail(s, labels, old_values, scores, lengths, mask, group, g_mom, work)
+        return self.lp_old, self.ref_lp
+
     def _use_split(self, split, idx):
         """Select the unsplit GAE / loss kernels or the split-beta ones with buffer set `idx`."""
         self._split_mode, self._sidx, self._coef_ready = bool(split), idx, False
