@@ -89,6 +89,8 @@ const char* trlx_last_error(void);
  *   "lmloss_dwp_form"   saved-P dW blocking: 0 auto (= 2: 32 rows a wave x H/2), 1 = 16 rows a wave x H
  *   "store_policy"      gradient-row store cache policy: 0 auto (default: nt; sc1 for all-VGPR rows
  *                       launches writing > 1.5 GB), 1 none, 2 sc1, 3 sc0|sc1, 4 nt|sc1, 5 nt
+ *   "vhead_splits"      value head column splits: 0 auto (trlx_value_head_splits), 1..64 fixed (capped
+ *                       at one split per 32 columns)
  * Results are identical up to fp32 summation order; only speed changes. */
 int trlx_set_tuning(const char* key, int64_t value);
 
@@ -367,6 +369,39 @@ int trlx_ilql_tq_at_actions(const trlx_ilql_tq_args* args, void* stream);
 #define TRLX_POLYAK_MAX_TENSORS 16
 int trlx_polyak_update(const void* const* src, void* const* target, const int64_t* numel, int64_t count,
                        int dtype, double alpha, void* stream);
+
+/* ---------------------------------------------------------------- fused bf16 value head
+ * The PPO value head — replaces `make_head(n_embd, 1)` (ppo_models.py:216-222: Linear(H, 2H),
+ * ReLU, Linear(2H, 1), all bf16) and its use at :618,:641:
+ *   z[t, j]   = bf16(sum_k h[t, k] * w1[j, k] + b1[j])      fp32 accumulation, ONE bf16 rounding
+ *   values[t] = sum_j relu(z[t, j]) * w2[j] + b2            fp32 accumulation, rounded once
+ * h: bf16 [N, H], row t at h + t*ldh (ldh >= H, a multiple of 8, <= 2^24; 16-byte aligned base);
+ * w1: bf16 [2H, H] contiguous, 16-byte aligned; b1, w2: bf16 [2H]; b2: bf16 [1]; values: [N] of
+ * values_dtype (TRLX_F32 / TRLX_BF16).  32 <= H <= 8192, H a multiple of 32, 1 <= N <= 2^30;
+ * anything else is refused before any launch.  z is never written.  A workgroup owns 64 tokens
+ * and one of S contiguous column slices; S = trlx_value_head_splits(N, H) is a function of N, H
+ * and the device's compute units (tuning "vhead_splits" overrides it).  S = 1: one launch.
+ * S > 1: one fp32 partial per (split, token) in `workspace`
+ * (>= trlx_value_head_workspace_bytes(N, H), enough for every S; may be NULL when S = 1) and a
+ * second small launch that adds them in split order.  For fixed (N, H, S) the result is
+ * bit-reproducible and independent of ldh and of the base address. */
+int trlx_value_head_splits(int64_t N, int64_t H);          /* 0 for a refused shape */
+int64_t trlx_value_head_workspace_bytes(int64_t N, int64_t H);
+int trlx_value_head_fwd(const void* h, int64_t ldh, const void* w1, const void* b1, const void* w2,
+                        const void* b2, int64_t N, int64_t H, void* values, int values_dtype,
+                        void* workspace, void* stream);
+
+/* The head's own backward from dv [N] (dv_dtype TRLX_F32 / TRLX_BF16): z is recomputed and
+ *   dz[t, j] = bf16(dv[t] * w2[j]) where z[t, j] > 0, else 0        bf16 [N, 2H], contiguous
+ *   dw2[j]   = sum_t dv[t] * relu(z[t, j])      db1[j] = sum_t dz[t, j]      db2 = sum_t dv[t]
+ * dw2, db1 [2H] and db2 [1] of grad_dtype, summed in fp32 in a fixed order (per 32-token half
+ * block, then the half blocks in order) in `workspace`
+ * (>= trlx_value_head_bwd_workspace_bytes(N, H)).  dh = dz * w1 and dw1 = dz^T * h are plain
+ * GEMMs left to the caller's BLAS.  Two launches; operands and limits as the forward. */
+int64_t trlx_value_head_bwd_workspace_bytes(int64_t N, int64_t H);
+int trlx_value_head_bwd(const void* h, int64_t ldh, const void* w1, const void* b1, const void* w2,
+                        const void* dv, int dv_dtype, int64_t N, int64_t H, void* dz, void* dw2,
+                        void* db1, void* db2, int grad_dtype, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------- §8f rank 2: fused lm_head + logprobs
  * lp[n] = h[n]·W[y_n] − logsumexp_v h[n]·W[v] without materialising the [N, V] logits —

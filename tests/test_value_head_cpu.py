@@ -1,0 +1,131 @@
+"""CPU-only checks of the fused value head: the oracle's restatement (a) reproduces the reference's
+make_head(n_embd, 1) bit for bit (tests/golden/value_head.npz, written by
+tests/golden/make_golden_value_head.py from the reference), ValueHead is the reference's module
+to a state_dict, the argument checks raise before any library call, and the binding table holds
+the new entries."""
+import re
+import os
+
+import pytest
+import torch
+
+import trlx_t5_amd as P
+from trlx_t5_amd import _lib
+from golden_util import T
+import value_head_checks as C
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "trlx_t5_amd.h")
+NAMES = ["0.weight", "0.bias", "2.weight", "2.bias"]
+
+
+def bits(t):
+    return t.detach().contiguous().view(torch.int16)
+
+
+def fixture_state(z):
+    return {n: T(z["sd/" + n]) for n in NAMES}
+
+
+def test_restatement_a_reproduces_the_reference_bit_for_bit(golden):
+    z = golden("value_head")
+    H, N = int(z["H"]), int(z["N"])
+    assert (H, N) == (64, 20) and [str(n) for n in z["names"]] == NAMES
+    sd = fixture_state(z)
+    h, dv = T(z["h"]), T(z["dv"])
+    assert tuple(h.shape) == (N, H) and tuple(dv.shape) == (N, 1)
+    got = C.reference_bf16(h, sd["0.weight"], sd["0.bias"], sd["2.weight"], sd["2.bias"], dv=dv)
+    assert torch.equal(bits(got["values"]), bits(T(z["out"]).squeeze(-1)))
+    assert torch.equal(bits(got["dh"]), bits(T(z["dh"])))
+    for key, name in (("dw1", "0.weight"), ("db1", "0.bias"), ("dw2", "2.weight"), ("db2", "2.bias")):
+        assert torch.equal(bits(got[key]).reshape(-1), bits(T(z["grad/" + name])).reshape(-1)), name
+
+
+def test_oracle_b_stays_within_bf16_of_the_reference(golden):
+    """(b) is the same function: (a) differs from it by its bf16 roundings only."""
+    z = golden("value_head")
+    sd = fixture_state(z)
+    h, dv = T(z["h"]), T(z["dv"]).reshape(-1)
+    args = (h, sd["0.weight"], sd["0.bias"], sd["2.weight"], sd["2.bias"])
+    a, b = C.reference_bf16(*args, dv=dv), C.oracle_fp64(*args, dv=dv)
+    for k in ("values",) + C.GRADS:
+        assert a[k].numel() == b[k].numel()
+        scale = float(b[k].abs().max())
+        assert C.max_err(a[k], b[k]) <= 2.0 ** -7 * scale, k
+
+
+def test_value_head_module_is_the_reference_module(golden):
+    z = golden("value_head")
+    H = int(z["H"])
+    sd = fixture_state(z)
+    head = P.ValueHead(H)
+    assert isinstance(head, torch.nn.Sequential)
+    assert list(head.state_dict()) == NAMES
+    assert all(v.dtype == torch.bfloat16 for v in head.state_dict().values())
+    assert [tuple(v.shape) for v in head.state_dict().values()] == [(2 * H, H), (2 * H,), (1, 2 * H), (1,)]
+    res = head.load_state_dict(sd, strict=True)
+    assert not res.missing_keys and not res.unexpected_keys
+    for n, t in head.state_dict().items():
+        assert torch.equal(bits(t), bits(sd[n]))
+    assert all(p.requires_grad for p in head.parameters())
+    assert isinstance(P.make_value_head(H, 1), P.ValueHead)
+    other = P.make_value_head(H, 5)
+    assert not isinstance(other, P.ValueHead) and other[2].weight.dtype == torch.bfloat16
+    assert tuple(other[2].weight.shape) == (5, 2 * H)
+
+
+def test_argument_checks_raise_before_any_library_call(monkeypatch):
+    def no_library(*a, **k):
+        raise AssertionError("the library was reached")
+
+    for fn in ("call", "query", "load"):
+        monkeypatch.setattr(_lib, fn, no_library)
+
+    def ops(H, N=3, dtype=torch.bfloat16):
+        c = C.make_case(N, max(H, 1), 0)
+        h = torch.zeros(N, H, dtype=dtype)
+        return [h, torch.zeros(2 * H, H, dtype=torch.bfloat16), torch.zeros(2 * H, dtype=torch.bfloat16),
+                torch.zeros(1, 2 * H, dtype=torch.bfloat16), c["b2"]]
+
+    with pytest.raises(ValueError, match="multiple of 32"):
+        P.value_head(*ops(48))
+    with pytest.raises(ValueError, match="H = 0"):
+        P.value_head(*ops(0))
+    with pytest.raises(ValueError, match="H = 8224"):
+        P.value_head(torch.zeros(1, 8224, dtype=torch.bfloat16), *ops(64)[1:])
+    with pytest.raises(TypeError, match="bfloat16"):
+        P.value_head(*ops(64, dtype=torch.float32))
+    a = ops(64)
+    a[1] = torch.zeros(128, 32, dtype=torch.bfloat16)
+    with pytest.raises(ValueError, match="w1 must be"):
+        P.value_head(*a)
+    a = ops(64)
+    a[2] = a[2][:-1]
+    with pytest.raises(ValueError, match="b1 must be"):
+        P.value_head(*a)
+    with pytest.raises(ValueError, match="no token"):
+        P.value_head(torch.zeros(0, 64, dtype=torch.bfloat16), *ops(64)[1:])
+    with pytest.raises(TypeError, match="out_dtype"):
+        P.value_head(*ops(64), out_dtype=torch.float16)
+    with pytest.raises(ValueError, match="ROCm"):   # the wrong device: there is no CPU path
+        P.value_head(*ops(64))
+    head = P.ValueHead(64)
+    with pytest.raises(ValueError, match="ROCm"):
+        head(torch.zeros(2, 3, 64, dtype=torch.bfloat16))
+    with pytest.raises(ValueError, match="ROCm"):   # also through autograd's forward
+        P.value_head(*[t.requires_grad_(True) for t in ops(64)])
+
+
+def test_binding_table_and_header_hold_the_new_entries():
+    names = ("trlx_value_head_fwd", "trlx_value_head_bwd", "trlx_value_head_workspace_bytes",
+             "trlx_value_head_bwd_workspace_bytes", "trlx_value_head_splits")
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    for name in names:
+        assert name in _lib.SIGNATURES
+        assert re.search(rf"^(?:int|int64_t) {name}\(", txt, flags=re.M), name
+        # the binding's argument count is the header's
+        decl = re.search(rf"{name}\((.*?)\);", txt, flags=re.S).group(1)
+        assert len(decl.split(",")) == len(_lib.SIGNATURES[name][1]), name
+    assert "vhead_splits" in open(HEADER).read()
+    for name in ("value_head", "ValueHead"):
+        assert name in P.__all__ and hasattr(P, name)

@@ -21,6 +21,9 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
       PPOHotPath.experience_from_logprobs the teacher-forced second pass over [B, T, V] logits
       goes away      trlx/orchestrator/ppo_orchestrator.py:116-167
   lm_head_logprobs — fused lm_head GEMM (MFMA) + logprobs, logits never in HBM
+  ValueHead (.values), value_head, make_value_head — the bf16 value head make_head(n_embd, 1)
+      fused: values and their gradient from hidden states, the [N, 2H] activation never
+      written by the forward      trlx/model/nn/ppo_models.py:216-222,:618,:641
   PPORolloutStorage, PPORLElement, PPORLBatch
       trlx/pipeline/ppo_pipeline.py, trlx/data/ppo_types.py (device-resident store)
   ILQLRolloutStorage (.from_samples = make_experience, .collate, .create_loader), ILQLElement
@@ -42,6 +45,8 @@ from .rollout_store import PPORLBatch, PPORLElement, PPORolloutRecorder, PPORoll
 from .ilql import ILQL_LOSS_KEYS, ILQLBatch, ILQLConfig, ILQLHotPath, ilql_sample_step
 from .ilql_heads import ILQLHeads, ilql_target_q_at_actions, make_head, polyak_update
 from .ilql_store import ILQLElement, ILQLRolloutStorage
+from .value_head import ValueHead, value_head, value_head_splits
+from .value_head import make_head as make_value_head
 from .sampling import ppo_sample_step
 from .control import PPOControlState
 from .step import PPOHotPath
@@ -58,6 +63,7 @@ __all__ = [
     "ILQLRolloutStorage", "ILQLElement",
     "PPORLElement", "PPORLBatch", "lm_head_logprobs", "PPOControlState",
     "RcclComm", "shift_tokens_right", "get_model_inputs",
+    "ValueHead", "value_head", "value_head_splits", "make_value_head",
 ]
 
 

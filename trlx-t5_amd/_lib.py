@@ -231,6 +231,13 @@ SIGNATURES = {
     "trlx_ilql_tq_at_actions": (_c_int, [_ilql_tq_p, _c_vp]),
     "trlx_polyak_update": (_c_int, [ctypes.POINTER(_c_vp), ctypes.POINTER(_c_vp), ctypes.POINTER(_c_i64), _c_i64,
                                     _c_int, _c_d, _c_vp]),
+    "trlx_value_head_splits": (_c_int, [_c_i64, _c_i64]),
+    "trlx_value_head_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
+    "trlx_value_head_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
+    "trlx_value_head_fwd": (_c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_int,
+                                     _c_vp, _c_vp]),
+    "trlx_value_head_bwd": (_c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_i64, _c_i64, _c_vp,
+                                     _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp]),
 }
 
 _lib = None

@@ -998,6 +998,7 @@ static size_t carve_workspace(void* base, int64_t B, int64_t T, Workspace* w) {
 size_t carve_ppo_workspace(void* base, int64_t B, int64_t T, Workspace* w) { return carve_workspace(base, B, T, w); }
 
 int lmloss_set_tuning(const char* key, int64_t value, bool* handled);  // lmhead_loss.hip
+int vhead_set_tuning(const char* key, int64_t value, bool* handled);   // value_head.hip
 
 // One launch while its workgroups' passes over all B lengths stay small (each reads every
 // length: O(B²·T / 1024) loads in all — 12 x 256 at C3); past kOrderOneLaunchChunks the two
@@ -1434,7 +1435,9 @@ extern "C" int trlx_set_tuning(const char* key, int64_t value) {
         g_stream_unroll = int(value);
     } else {
         bool handled = false;
-        const int rc = lmloss_set_tuning(key, value, &handled);
+        int rc = lmloss_set_tuning(key, value, &handled);
+        if (handled) return rc;
+        rc = vhead_set_tuning(key, value, &handled);
         if (handled) return rc;
         set_error("unknown tuning key '%s'", k.c_str());
         return TRLX_ERR_ARG;
