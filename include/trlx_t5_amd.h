@@ -625,6 +625,98 @@ int trlx_ppo_sample_record(const void* logits, int64_t ld_logits, int dtype, int
                            const void* step_values, int values_dtype, int64_t* lengths,
                            int score_finished, void* stream);
 
+/* The processing step: trlx_ppo_sample / trlx_ppo_sample_record with HF's prefix-aware logits
+ * processors and the forced token (transformers 4.21 _get_logits_processor order; the rollouts
+ * of T5HeadWithValueModel.generate, ppo_models.py:620-622, pass forced_bos_token_id and any
+ * gen_kwargs key).  The prefix of row b — HF's input_ids[b], the same length n = prefix0_len +
+ * prefix1_len for every row, pad tokens counted like any other — is prefix0[b, 0:prefix0_len]
+ * followed by prefix1[b, 0:prefix1_len] (device int64, row strides in elements).  The processed
+ * row of a live row, x = logits[b] in fp32:
+ *   1. repetition_penalty rp != 1: for every distinct prefix token v,
+ *      x[v] = x[v] < 0 ? x[v] * rp : x[v] / rp (fp32 multiplication / division, correctly
+ *      rounded: equal to torch's on fp32 rows; bf16 rows are not rounded back to bf16);
+ *   2. no_repeat_ngram_size g > 0, when n + 1 >= g: for every i with
+ *      p[i : i+g-1] == p[n-g+1 : n], x[p[i+g-1]] = -inf (g = 1 bans every prefix token);
+ *   3. bad words, n_bad_words sequences s = bad_words[off[s] .. off[s+1]) = [w0 .. wk]:
+ *      k = 0 always gives x[w0] = -inf; k >= 1 bans wk when n >= k and the prefix ends
+ *      with w0 .. w(k-1);
+ *   4. x[eos] = -inf while cur_len < min_length, as trlx_ppo_sample;
+ *   5. forced_token_id f >= 0 (the caller's forced bos / eos decision for this cur_len): every
+ *      entry -inf except x[f] = 0 — out_ids[b] = f, out_min_kept[b] = 0, out_kept_count[b] = 1;
+ *   6. temperature, top-k, top-p, the draw at u[b], unfinished / pad, as trlx_ppo_sample.
+ * out_logprobs, and with a record block logprobs[b, t] and ref_logprobs[b, t], stay the
+ * log-softmax of the unmodified rows at the token, forced tokens included; out_min_kept and
+ * out_kept_count describe the processed row.  A prefix token outside [0, V) is ignored by every
+ * processor (tested before any address is formed); it keeps its position in the n-gram and
+ * bad-word matches, which compare the int64 values.  Finished rows as in the other two entries.
+ * Record block: ref_logits == NULL is the plain step and the block is not read; otherwise its
+ * fields and checks are trlx_ppo_sample_record's.
+ * Bad words: the device table (bad_words, bad_words_offsets of n_bad_words + 1 entries) is
+ * what the kernel reads; bad_words_host / bad_words_offsets_host are the same arrays in host
+ * memory, read during the call only, and are what the argument checks read.
+ * Refused before any launch: repetition_penalty <= 0, no_repeat_ngram_size < 0, forced_token_id
+ * outside [-1, V), a bad-word token outside [0, V), offsets that do not start at 0 or do not
+ * ascend strictly, a missing table pointer (TRLX_ERR_ARG); a segment with n > 0 and a NULL
+ * pointer (TRLX_ERR_ARG) or a row stride below n (TRLX_ERR_SHAPE); and whatever the other two
+ * entries refuse.  With repetition_penalty = 1, no_repeat_ngram_size = 0, n_bad_words = 0 and
+ * forced_token_id = -1 the call launches the kernel of trlx_ppo_sample / trlx_ppo_sample_record. */
+typedef struct TrlxPpoSampleProcArgs {
+    /* the plain step: the arguments of trlx_ppo_sample */
+    const void* logits;
+    int64_t ld_logits;
+    int64_t B;
+    int64_t V;
+    int dtype;
+    int top_k;
+    float temperature;
+    float top_p;
+    int min_tokens_to_keep;
+    int score_finished;
+    int64_t cur_len;
+    int64_t min_length;
+    int64_t eos_token_id;
+    int64_t pad_token_id;
+    const float* u;
+    int64_t* out_ids;
+    float* out_logprobs;
+    float* out_min_kept;
+    int32_t* out_kept_count;
+    int64_t* unfinished;
+    /* the record block: the arguments of trlx_ppo_sample_record (score_finished above) */
+    const void* ref_logits;
+    int64_t ld_ref;
+    int64_t t;
+    int64_t T;
+    int64_t* tokens;
+    int64_t ld_tokens;
+    float* logprobs;
+    int64_t ld_logprobs;
+    float* ref_logprobs;
+    int64_t ld_ref_logprobs;
+    float* values;
+    int64_t ld_values;
+    const void* step_values;
+    int64_t* lengths;
+    int ref_dtype;
+    int values_dtype;
+    /* the processor block */
+    float repetition_penalty;
+    int no_repeat_ngram_size;
+    int64_t forced_token_id;
+    const int64_t* prefix0;
+    int64_t prefix0_ld;
+    int64_t prefix0_len;
+    const int64_t* prefix1;
+    int64_t prefix1_ld;
+    int64_t prefix1_len;
+    const int64_t* bad_words;
+    const int64_t* bad_words_offsets;
+    const int64_t* bad_words_host;
+    const int64_t* bad_words_offsets_host;
+    int64_t n_bad_words;
+} TrlxPpoSampleProcArgs;
+int trlx_ppo_sample_proc(const TrlxPpoSampleProcArgs* a, void* stream);
+
 /* ---------------------------------------------------------------- §8f: device-resident rollout store
  * Row copy between padded columnar [rows, W] buffers — replaces the reference's
  * `.cpu()` of the experience tensors, per-sample PPORLElement lists and the pad_sequence

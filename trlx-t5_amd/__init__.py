@@ -20,6 +20,10 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
       tokens, policy and reference log-probs and values per step; with
       PPOHotPath.experience_from_logprobs the teacher-forced second pass over [B, T, V] logits
       goes away      trlx/orchestrator/ppo_orchestrator.py:116-167
+  PPOLogitsProcessors + ppo_sample_step(processors=, prefix=) — repetition penalty, no-repeat
+      n-gram, bad words and the forced bos / eos token of generate(forced_bos_token_id=...,
+      **gen_kwargs) inside the same launch; the recorded log-probs stay those of the
+      unmodified rows      trlx/model/nn/ppo_models.py:620-622
   lm_head_logprobs — fused lm_head GEMM (MFMA) + logprobs, logits never in HBM
   ValueHead (.values), value_head, make_value_head — the bf16 value head make_head(n_embd, 1)
       fused: values and their gradient from hidden states, the [N, 2H] activation never
@@ -47,7 +51,7 @@ from .ilql_heads import ILQLHeads, ilql_target_q_at_actions, make_head, polyak_u
 from .ilql_store import ILQLElement, ILQLRolloutStorage
 from .value_head import ValueHead, value_head, value_head_splits
 from .value_head import make_head as make_value_head
-from .sampling import ppo_sample_step
+from .sampling import PPOLogitsProcessors, ppo_sample_step
 from .control import PPOControlState
 from .step import PPOHotPath
 from .comm import RcclComm
@@ -59,7 +63,7 @@ __all__ = [
     "prepare_scores", "stats_dict", "STATS_KEYS", "PPOHotPath", "load_library",
     "ILQLConfig", "ILQLBatch", "ILQLHotPath", "ILQL_LOSS_KEYS", "ilql_sample_step", "ppo_sample_step",
     "ILQLHeads", "ilql_target_q_at_actions", "polyak_update", "make_head", "PPORolloutStorage",
-    "PPORolloutRecorder",
+    "PPORolloutRecorder", "PPOLogitsProcessors",
     "ILQLRolloutStorage", "ILQLElement",
     "PPORLElement", "PPORLBatch", "lm_head_logprobs", "PPOControlState",
     "RcclComm", "shift_tokens_right", "get_model_inputs",

@@ -58,6 +58,28 @@ class IlqlTqArgs(ctypes.Structure):
     ]
 
 
+class PpoSampleProcArgs(ctypes.Structure):
+    """Mirror of TrlxPpoSampleProcArgs (include/trlx_t5_amd.h): the plain step, the record block
+    (ref_logits NULL = none), the processor block."""
+    _fields_ = [
+        ("logits", _c_vp), ("ld_logits", _c_i64), ("B", _c_i64), ("V", _c_i64),
+        ("dtype", _c_int), ("top_k", _c_int), ("temperature", _c_f), ("top_p", _c_f),
+        ("min_tokens_to_keep", _c_int), ("score_finished", _c_int),
+        ("cur_len", _c_i64), ("min_length", _c_i64), ("eos_token_id", _c_i64), ("pad_token_id", _c_i64),
+        ("u", _c_vp), ("out_ids", _c_vp), ("out_logprobs", _c_vp), ("out_min_kept", _c_vp),
+        ("out_kept_count", _c_vp), ("unfinished", _c_vp),
+        ("ref_logits", _c_vp), ("ld_ref", _c_i64), ("t", _c_i64), ("T", _c_i64),
+        ("tokens", _c_vp), ("ld_tokens", _c_i64), ("logprobs", _c_vp), ("ld_logprobs", _c_i64),
+        ("ref_logprobs", _c_vp), ("ld_ref_logprobs", _c_i64), ("values", _c_vp), ("ld_values", _c_i64),
+        ("step_values", _c_vp), ("lengths", _c_vp), ("ref_dtype", _c_int), ("values_dtype", _c_int),
+        ("repetition_penalty", _c_f), ("no_repeat_ngram_size", _c_int), ("forced_token_id", _c_i64),
+        ("prefix0", _c_vp), ("prefix0_ld", _c_i64), ("prefix0_len", _c_i64),
+        ("prefix1", _c_vp), ("prefix1_ld", _c_i64), ("prefix1_len", _c_i64),
+        ("bad_words", _c_vp), ("bad_words_offsets", _c_vp), ("bad_words_host", _c_vp),
+        ("bad_words_offsets_host", _c_vp), ("n_bad_words", _c_i64),
+    ]
+
+
 POLYAK_MAX_TENSORS = 16
 
 _ilql_p = ctypes.POINTER(IlqlArgs)
@@ -185,6 +207,7 @@ SIGNATURES = {
                                         _c_i64, _c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                         _c_vp, _c_i64, _c_int, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp,
                                         _c_i64, _c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_int, _c_vp]),
+    "trlx_ppo_sample_proc": (_c_int, [ctypes.POINTER(PpoSampleProcArgs), _c_vp]),
     "trlx_rows_copy": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                 _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_shift_tokens_right": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp]),

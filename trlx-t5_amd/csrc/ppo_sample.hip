@@ -86,6 +86,36 @@ __device__ __forceinline__ const PpoSampleArgs& sample_args(const PpoSampleRecAr
 __device__ __forceinline__ PpoRecordArgs record_args(const PpoSampleArgs&) { return PpoRecordArgs{}; }
 __device__ __forceinline__ PpoRecordArgs record_args(const PpoSampleRecArgs& a) { return a.r; }
 
+// The processing step (trlx_ppo_sample_proc): HF's prefix-aware logits processors and the forced
+// token.  The prefix of row b is seg0[b, 0:n0] followed by seg1[b, 0:n1] (row strides in elements).
+struct PpoProcArgs {
+    const int64_t* seg0;
+    int64_t ld0;
+    const int64_t* seg1;
+    int64_t ld1;
+    int n0, n1;
+    const int64_t* bw_tok;   // bad words: flat tokens, sequence s = bw_tok[bw_off[s] .. bw_off[s + 1])
+    const int64_t* bw_off;
+    int n_bw;
+    int ngram;               // 0 = off
+    float rp;                // 1 = off
+    int edits;               // any of the three on
+    int64_t forced;          // -1 = none
+};
+struct PpoSampleProcArgs {
+    PpoSampleArgs s;
+    PpoRecordArgs r;         // r.ref_logits == NULL: no recording
+    PpoProcArgs p;
+};
+__device__ __forceinline__ const PpoSampleArgs& sample_args(const PpoSampleProcArgs& a) { return a.s; }
+__device__ __forceinline__ PpoRecordArgs record_args(const PpoSampleProcArgs& a) { return a.r; }
+__device__ __forceinline__ PpoProcArgs proc_args(const PpoSampleArgs&) { return PpoProcArgs{}; }
+__device__ __forceinline__ PpoProcArgs proc_args(const PpoSampleRecArgs&) { return PpoProcArgs{}; }
+__device__ __forceinline__ PpoProcArgs proc_args(const PpoSampleProcArgs& a) { return a.p; }
+template <bool REC, bool PROC>
+using ppo_sample_args_t =
+    std::conditional_t<PROC, PpoSampleProcArgs, std::conditional_t<REC, PpoSampleRecArgs, PpoSampleArgs>>;
+
 // One row's step.  REC: the recording step — the reference row is reduced to per-wave
 // (max, sum exp) pairs first, parked in LDS (nothing of it stays in registers while the
 // policy row is held), and the thread that finds the token reads x_ref[token] beside x[token].
@@ -94,10 +124,24 @@ __device__ __forceinline__ PpoRecordArgs record_args(const PpoSampleRecArgs& a) 
 // (One kernel template, not a shared device function called by two kernels: through such a
 // wrapper hipcc 7.2 schedules the plain step differently — 89 -> 128 VGPRs + 52 B scratch at
 // bf16 4 x 1024.  REC = false compiles to the kernel this file had before the recording step.)
-template <class DT, int NV, int NT, bool REC = false>
-__global__ __launch_bounds__(NT) void k_ppo_sample(std::conditional_t<REC, PpoSampleRecArgs, PpoSampleArgs> args) {
+//
+// PROC: the processing step (an instantiation of its own, REC compiled in and switched by
+// r.ref_logits at run time; PROC = false leaves the two kernels above as they were).  The
+// prefix-aware processors are sparse edits of the row, gathered first as two bitmaps over V in
+// LDS — "penalised" (repetition penalty) and "banned" (no-repeat n-gram, bad words) — by loops
+// over the prefix and the bad-word table that stride over the workgroup.  The log-softmax
+// statistics are reduced from the registers before any edit; the edits are then applied where
+// min-length drops eos: every thread tests the EPV bits of each vector it holds (two LDS words
+// per bitmap and vector).  A forced token needs no selection at all: the row is reduced for
+// the log-prob and the thread 0 writes the forced id, kept count 1, smallest kept logit 0.
+template <class DT, int NV, int NT, bool REC = false, bool PROC = false>
+__global__ __launch_bounds__(NT) void k_ppo_sample(ppo_sample_args_t<REC, PROC> args) {
+    static_assert(REC || !PROC, "the processing step carries the record block");
     const PpoSampleArgs& a = sample_args(args);
     const PpoRecordArgs r = record_args(args);
+    [[maybe_unused]] const PpoProcArgs p = proc_args(args);
+    [[maybe_unused]] bool rec_on = true;  // PROC: recording is a run-time choice (block-uniform)
+    if constexpr (PROC) rec_on = r.ref_logits != nullptr;
     constexpr int kWaves = NT / kWave;
     typedef typename DT::elem_t E;
     constexpr int EPV = DT::kEPV;
@@ -142,10 +186,11 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(std::conditional_t<REC, PpoSa
     if constexpr (REC) {
         const bool finished = a.unfinished && a.unfinished[b] == 0;
         pad_scored = finished && r.score_finished;
+        if constexpr (PROC) pad_scored = pad_scored && rec_on;
         if (finished && !pad_scored) {  // pad, 0, 0; neither row is read
             if (tid == 0) {
                 finish(padtok, 0.f, 0.f, 0);
-                record(padtok, 0.f, 0.f, false, false);
+                if (rec_on) record(padtok, 0.f, 0.f, false, false);
             }
             return;
         }
@@ -154,13 +199,57 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(std::conditional_t<REC, PpoSa
         return;
     }
 
+    // ---- processing step: the edit bitmaps.  Bit v of `pen` / `ban`: token v takes the
+    // repetition penalty / becomes -inf.  A prefix token outside [0, V) sets no bit (tested
+    // before any address is formed) but keeps its position in the n-gram and bad-word matches,
+    // where the comparison is on the int64 values.  One spare word: a vector's bits are read
+    // as the two words from its first element's.  (V < NV * NT * EPV by the launch table.)
+    constexpr int kBmWords = PROC ? NV * NT * DT::kEPV / 32 + 2 : 1;
+    __shared__ uint32_t pen[kBmWords], ban[kBmWords];
+    if constexpr (PROC) {
+        if (p.edits && p.forced < 0) {  // block-uniform
+            const int nw = int((V + 31) / 32) + 1;
+            for (int i = tid; i < nw; i += NT) {
+                pen[i] = 0u;
+                ban[i] = 0u;
+            }
+            __syncthreads();
+            const int n = p.n0 + p.n1;
+            auto ptok = [&](int j) __attribute__((always_inline)) {
+                return j < p.n0 ? p.seg0[b * p.ld0 + j] : p.seg1[b * p.ld1 + (j - p.n0)];
+            };
+            auto mark = [&](uint32_t* bm, int64_t tok) __attribute__((always_inline)) {
+                if (uint64_t(tok) < uint64_t(V)) atomicOr(&bm[int(tok >> 5)], 1u << int(tok & 31));
+            };
+            if (p.rp != 1.f)
+                for (int j = tid; j < n; j += NT) mark(pen, ptok(j));
+            const int g = p.ngram;
+            if (g > 0 && n + 1 >= g) {  // p[i : i + g - 1] == p[n - g + 1 : n] bans p[i + g - 1]
+                for (int i = tid; i + g - 1 < n; i += NT) {
+                    bool eq = true;
+                    for (int q = 0; eq && q < g - 1; ++q) eq = ptok(i + q) == ptok(n - g + 1 + q);
+                    if (eq) mark(ban, ptok(i + g - 1));
+                }
+            }
+            for (int sq = tid; sq < p.n_bw; sq += NT) {  // [w0 .. wk] bans wk after a prefix ending w0 .. w(k-1)
+                const int64_t o = p.bw_off[sq];
+                const int k = int(p.bw_off[sq + 1] - o) - 1;
+                if (k < 0 || k > n) continue;
+                bool eq = true;
+                for (int q = 0; eq && q < k; ++q) eq = ptok(n - k + q) == p.bw_tok[o + q];
+                if (eq) mark(ban, p.bw_tok[o + k]);
+            }
+            // (read after the barrier that the policy row's statistics take below)
+        }
+    }
+
     // ---- recording step: the reference row, streamed once on its own head / body / tail split
     // and line shift: per-thread online (max, sum exp) in fp32 over the steps in order, then the
     // wave's pair in LDS.  The pairs are combined in wave order by ref_logprob(), after the
     // barrier that the policy row's statistics take below.
     __shared__ float r_max[REC ? kWaves : 1], r_sum[REC ? kWaves : 1], s_rlp;
     const E* xr = nullptr;
-    if constexpr (REC) {
+    if constexpr (REC) if (rec_on) {
         xr = reinterpret_cast<const E*>(r.ref_logits) + b * r.ld_ref;
         const RowSplit<DT> sr(xr, V);
         const int nvr = int(sr.nvec);
@@ -290,9 +379,52 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(std::conditional_t<REC, PpoSa
             return;
         }
     }
+    if constexpr (PROC) {
+        // ---- forced token: every other entry is -inf and this one 0 — nothing to select or draw
+        if (p.forced >= 0) {  // block-uniform
+            if (tid == 0) {
+                const int64_t tok = p.forced;
+                const float lp = (DT::load1(x, tok) - row_max) - log_sum;
+                finish(tok, lp, 0.f, 1);
+                if (rec_on) record(tok, lp, ref_logprob(tok), true, true);
+                if (a.unfinished && a.eos >= 0) a.unfinished[b] = tok != a.eos ? 1 : 0;
+            }
+            return;
+        }
+    }
 
     // ---- min length: the thread that holds x[eos] drops it; the row maximum again
     float xmax = m;
+    if constexpr (PROC) {
+        // ---- the processors' edits, in HF's order: repetition penalty (fp32, a true
+        // multiplication / division), then the bans; min length follows as in the plain step
+        if (p.edits) {  // block-uniform
+            const float rp = p.rp;
+            auto edit = [&](float v, bool pn, bool bn) __attribute__((always_inline)) {
+                if (pn) v = v < 0.f ? __fmul_rn(v, rp) : __fdiv_rn(v, rp);
+                return bn ? -INFINITY : v;
+            };
+            if (je >= 0) fe = edit(fe, (pen[je >> 5] >> (je & 31)) & 1u, (ban[je >> 5] >> (je & 31)) & 1u);
+            float mx = fe;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                if (valid(k)) {
+                    const int64_t j0 = index_of(k, 0);
+                    const int w = int(j0 >> 5), sh = int(j0 & 31);
+                    constexpr uint32_t kMask = (1u << EPV) - 1u;
+                    const uint32_t pb = uint32_t(((uint64_t(pen[w + 1]) << 32 | pen[w]) >> sh)) & kMask;
+                    const uint32_t bb = uint32_t(((uint64_t(ban[w + 1]) << 32 | ban[w]) >> sh)) & kMask;
+                    if (pb | bb) {
+#pragma unroll
+                        for (int e = 0; e < EPV; ++e) f[k][e] = edit(f[k][e], (pb >> e) & 1u, (bb >> e) & 1u);
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < EPV; ++e) mx = fmaxf(mx, f[k][e]);
+            }
+            if (!a.suppress_eos) xmax = block_max(mx, sh_red3);
+        }
+    }
     if (a.suppress_eos) {  // block-uniform
         if (je == a.eos) fe = -INFINITY;
         int ks = -1, es = -1;
@@ -317,7 +449,7 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(std::conditional_t<REC, PpoSa
     if (xmax == -INFINITY) {  // no finite logit left (HF's multinomial would raise): pad, nothing kept
         if (tid == 0) {
             finish(padtok, 0.f, 0.f, 0);
-            if constexpr (REC) record(padtok, 0.f, 0.f, true, true);
+            if constexpr (REC) if (rec_on) record(padtok, 0.f, 0.f, true, true);
             if (a.unfinished && a.eos >= 0) a.unfinished[b] = padtok != a.eos ? 1 : 0;
         }
         return;
@@ -633,7 +765,7 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(std::conditional_t<REC, PpoSa
         s_pick[2] = int(pick);
         // the row's registers hold weights by now: the drawn logit comes from memory again
         if (pick >= 0) s_lp = (DT::load1(x, pick) - row_max) - log_sum;
-        if constexpr (REC) s_rlp = pick >= 0 ? ref_logprob(pick) : 0.f;
+        if constexpr (REC) if (rec_on) s_rlp = pick >= 0 ? ref_logprob(pick) : 0.f;
     }
     __syncthreads();
     if (tid == 0) {
@@ -646,7 +778,7 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(std::conditional_t<REC, PpoSa
         const bool got = s_pick[2] >= 0;
         const int64_t tok = got ? s_pick[2] : padtok;
         finish(tok, got ? s_lp : 0.f, got ? mnk : 0.f, got ? n : 0);
-        if constexpr (REC) record(tok, got ? s_lp : 0.f, got ? s_rlp : 0.f, true, true);
+        if constexpr (REC) if (rec_on) record(tok, got ? s_lp : 0.f, got ? s_rlp : 0.f, true, true);
         if (a.unfinished && a.eos >= 0) a.unfinished[b] = tok != a.eos ? 1 : 0;
     }
 }
@@ -655,12 +787,14 @@ __global__ __launch_bounds__(NT) void k_ppo_sample(std::conditional_t<REC, PpoSa
 
 using namespace trlx;
 
-// Both entries: the arguments they share, one launch table.  rec = NULL: the plain step.
+// All entries: the arguments they share, one launch table.  rec = NULL: the plain step;
+// proc = NULL: the kernels without the processing step.
 static int ppo_sample_launch(const char* who, const void* logits, int64_t ld_logits, int dtype, int64_t B, int64_t V,
                              float temperature, int top_k, float top_p, int min_tokens_to_keep, int64_t cur_len,
                              int64_t min_length, int64_t eos_token_id, int64_t pad_token_id, const float* u,
                              int64_t* out_ids, float* out_logprobs, float* out_min_kept, int32_t* out_kept_count,
-                             int64_t* unfinished, const PpoRecordArgs* rec, void* stream) {
+                             int64_t* unfinished, const PpoRecordArgs* rec, void* stream,
+                             const PpoProcArgs* proc = nullptr) {
     TRLX_REQUIRE(B == 0 || (logits && u && out_ids && out_logprobs && out_min_kept && out_kept_count), TRLX_ERR_ARG,
                  "NULL argument to %s", who);
     TRLX_REQUIRE(dtype == TRLX_F32 || dtype == TRLX_BF16, TRLX_ERR_DTYPE, "dtype %d", dtype);
@@ -694,6 +828,11 @@ static int ppo_sample_launch(const char* who, const void* logits, int64_t ld_log
     // cannot hold the row beside this kernel's state without scratch: rows end at ~53k entries)
 #define TRLX_PSMP(DTT, N, NT)                                                                                  \
     if (need(NT) <= N) {                                                                                       \
+        if (proc) {                                                                                            \
+            hipLaunchKernelGGL((k_ppo_sample<DTT, N, NT, true, true>), dim3(unsigned(B)), dim3(NT), 0,         \
+                               (hipStream_t)stream, PpoSampleProcArgs{a, rec ? *rec : PpoRecordArgs{}, *proc}); \
+            return check_launch("k_ppo_sample<proc>");                                                         \
+        }                                                                                                      \
         if (rec) {                                                                                             \
             hipLaunchKernelGGL((k_ppo_sample<DTT, N, NT, true>), dim3(unsigned(B)), dim3(NT), 0,               \
                                (hipStream_t)stream, PpoSampleRecArgs{a, *rec});                                \
@@ -728,18 +867,19 @@ extern "C" int trlx_ppo_sample(const void* logits, int64_t ld_logits, int dtype,
                              out_logprobs, out_min_kept, out_kept_count, unfinished, nullptr, stream);
 }
 
-extern "C" int trlx_ppo_sample_record(const void* logits, int64_t ld_logits, int dtype, int64_t B, int64_t V,
-                                      float temperature, int top_k, float top_p, int min_tokens_to_keep,
-                                      int64_t cur_len, int64_t min_length, int64_t eos_token_id,
-                                      int64_t pad_token_id, const float* u, int64_t* out_ids, float* out_logprobs,
-                                      float* out_min_kept, int32_t* out_kept_count, int64_t* unfinished,
-                                      const void* ref_logits, int64_t ld_ref, int ref_dtype, int64_t t, int64_t T,
-                                      int64_t* tokens, int64_t ld_tokens, float* logprobs, int64_t ld_logprobs,
-                                      float* ref_logprobs, int64_t ld_ref_logprobs, float* values, int64_t ld_values,
-                                      const void* step_values, int values_dtype, int64_t* lengths,
-                                      int score_finished, void* stream) {
+// The recording entries: the record block's checks, then the launch (proc = NULL: trlx_ppo_sample_record).
+static int ppo_sample_record_launch(const char* who, const void* logits, int64_t ld_logits, int dtype, int64_t B,
+                                    int64_t V, float temperature, int top_k, float top_p, int min_tokens_to_keep,
+                                    int64_t cur_len, int64_t min_length, int64_t eos_token_id, int64_t pad_token_id,
+                                    const float* u, int64_t* out_ids, float* out_logprobs, float* out_min_kept,
+                                    int32_t* out_kept_count, int64_t* unfinished, const void* ref_logits,
+                                    int64_t ld_ref, int ref_dtype, int64_t t, int64_t T, int64_t* tokens,
+                                    int64_t ld_tokens, float* logprobs, int64_t ld_logprobs, float* ref_logprobs,
+                                    int64_t ld_ref_logprobs, float* values, int64_t ld_values,
+                                    const void* step_values, int values_dtype, int64_t* lengths, int score_finished,
+                                    void* stream, const PpoProcArgs* proc) {
     TRLX_REQUIRE(B == 0 || (ref_logits && tokens && logprobs && ref_logprobs), TRLX_ERR_ARG,
-                 "NULL argument to trlx_ppo_sample_record (ref_logits, tokens, logprobs, ref_logprobs)");
+                 "NULL argument to %s (ref_logits, tokens, logprobs, ref_logprobs)", who);
     TRLX_REQUIRE(ref_dtype == dtype, TRLX_ERR_DTYPE, "reference rows of dtype %d, policy rows of dtype %d", ref_dtype,
                  dtype);
     TRLX_REQUIRE(T > 0 && t >= 0 && t < T, TRLX_ERR_SHAPE, "column t = %lld outside [0, T = %lld)", (long long)t,
@@ -768,7 +908,87 @@ extern "C" int trlx_ppo_sample_record(const void* logits, int64_t ld_logits, int
     r.v_dtype = values_dtype;
     r.score_finished = score_finished != 0;
     r.lengths = lengths;
-    return ppo_sample_launch("trlx_ppo_sample_record", logits, ld_logits, dtype, B, V, temperature, top_k, top_p,
-                             min_tokens_to_keep, cur_len, min_length, eos_token_id, pad_token_id, u, out_ids,
-                             out_logprobs, out_min_kept, out_kept_count, unfinished, &r, stream);
+    return ppo_sample_launch(who, logits, ld_logits, dtype, B, V, temperature, top_k, top_p, min_tokens_to_keep,
+                             cur_len, min_length, eos_token_id, pad_token_id, u, out_ids, out_logprobs, out_min_kept,
+                             out_kept_count, unfinished, &r, stream, proc);
+}
+
+extern "C" int trlx_ppo_sample_record(const void* logits, int64_t ld_logits, int dtype, int64_t B, int64_t V,
+                                      float temperature, int top_k, float top_p, int min_tokens_to_keep,
+                                      int64_t cur_len, int64_t min_length, int64_t eos_token_id,
+                                      int64_t pad_token_id, const float* u, int64_t* out_ids, float* out_logprobs,
+                                      float* out_min_kept, int32_t* out_kept_count, int64_t* unfinished,
+                                      const void* ref_logits, int64_t ld_ref, int ref_dtype, int64_t t, int64_t T,
+                                      int64_t* tokens, int64_t ld_tokens, float* logprobs, int64_t ld_logprobs,
+                                      float* ref_logprobs, int64_t ld_ref_logprobs, float* values, int64_t ld_values,
+                                      const void* step_values, int values_dtype, int64_t* lengths,
+                                      int score_finished, void* stream) {
+    return ppo_sample_record_launch("trlx_ppo_sample_record", logits, ld_logits, dtype, B, V, temperature, top_k,
+                                    top_p, min_tokens_to_keep, cur_len, min_length, eos_token_id, pad_token_id, u,
+                                    out_ids, out_logprobs, out_min_kept, out_kept_count, unfinished, ref_logits,
+                                    ld_ref, ref_dtype, t, T, tokens, ld_tokens, logprobs, ld_logprobs, ref_logprobs,
+                                    ld_ref_logprobs, values, ld_values, step_values, values_dtype, lengths,
+                                    score_finished, stream, nullptr);
+}
+
+extern "C" int trlx_ppo_sample_proc(const TrlxPpoSampleProcArgs* a, void* stream) {
+    TRLX_REQUIRE(a, TRLX_ERR_ARG, "NULL argument to trlx_ppo_sample_proc");
+    const int64_t V = a->V;
+    TRLX_REQUIRE(a->repetition_penalty > 0.f, TRLX_ERR_ARG, "repetition_penalty %g must be > 0",
+                 double(a->repetition_penalty));
+    TRLX_REQUIRE(a->no_repeat_ngram_size >= 0, TRLX_ERR_ARG, "no_repeat_ngram_size %d must be >= 0",
+                 a->no_repeat_ngram_size);
+    TRLX_REQUIRE(a->forced_token_id >= -1 && a->forced_token_id < V, TRLX_ERR_ARG,
+                 "forced token %lld outside [0, V) (-1 = none)", (long long)a->forced_token_id);
+    TRLX_REQUIRE(a->prefix0_len >= 0 && a->prefix1_len >= 0 &&
+                     a->prefix0_len + a->prefix1_len < (int64_t(1) << 30),
+                 TRLX_ERR_SHAPE, "prefix lengths %lld + %lld", (long long)a->prefix0_len, (long long)a->prefix1_len);
+    TRLX_REQUIRE((a->prefix0_len == 0 || a->prefix0) && (a->prefix1_len == 0 || a->prefix1), TRLX_ERR_ARG,
+                 "a prefix segment with n > 0 and a NULL pointer");
+    TRLX_REQUIRE((a->prefix0_len == 0 || a->prefix0_ld >= a->prefix0_len) &&
+                     (a->prefix1_len == 0 || a->prefix1_ld >= a->prefix1_len),
+                 TRLX_ERR_SHAPE, "a prefix segment's row stride is below its length");
+    const int64_t nbw = a->n_bad_words;
+    TRLX_REQUIRE(nbw >= 0 && nbw < (int64_t(1) << 30), TRLX_ERR_SHAPE, "n_bad_words %lld", (long long)nbw);
+    if (nbw > 0) {  // the host mirror of the table is what is checked; the kernel bounds-checks every ban again
+        TRLX_REQUIRE(a->bad_words && a->bad_words_offsets && a->bad_words_host && a->bad_words_offsets_host,
+                     TRLX_ERR_ARG, "bad words: the device table and its host mirror (tokens, offsets) are needed");
+        const int64_t* off = a->bad_words_offsets_host;
+        TRLX_REQUIRE(off[0] == 0, TRLX_ERR_ARG, "bad-word offsets must start at 0");
+        for (int64_t s = 0; s < nbw; ++s)
+            TRLX_REQUIRE(off[s + 1] > off[s], TRLX_ERR_ARG, "bad-word offsets not ascending at sequence %lld",
+                         (long long)s);
+        for (int64_t i = 0; i < off[nbw]; ++i)
+            TRLX_REQUIRE(a->bad_words_host[i] >= 0 && a->bad_words_host[i] < V, TRLX_ERR_ARG,
+                         "bad-word token %lld outside [0, V)", (long long)a->bad_words_host[i]);
+    }
+    PpoProcArgs p = {};
+    p.seg0 = a->prefix0;
+    p.ld0 = a->prefix0_ld;
+    p.n0 = int(a->prefix0_len);
+    p.seg1 = a->prefix1;
+    p.ld1 = a->prefix1_ld;
+    p.n1 = int(a->prefix1_len);
+    p.bw_tok = a->bad_words;
+    p.bw_off = a->bad_words_offsets;
+    p.n_bw = int(nbw);
+    p.ngram = a->no_repeat_ngram_size;
+    p.rp = a->repetition_penalty;
+    p.edits = p.rp != 1.f || p.ngram > 0 || p.n_bw > 0;
+    p.forced = a->forced_token_id;
+    // every processor off and no forced token: the kernels of the other two entries
+    const PpoProcArgs* proc = (p.edits || p.forced >= 0) ? &p : nullptr;
+    if (a->ref_logits)
+        return ppo_sample_record_launch("trlx_ppo_sample_proc", a->logits, a->ld_logits, a->dtype, a->B, V,
+                                        a->temperature, a->top_k, a->top_p, a->min_tokens_to_keep, a->cur_len,
+                                        a->min_length, a->eos_token_id, a->pad_token_id, a->u, a->out_ids,
+                                        a->out_logprobs, a->out_min_kept, a->out_kept_count, a->unfinished,
+                                        a->ref_logits, a->ld_ref, a->ref_dtype, a->t, a->T, a->tokens, a->ld_tokens,
+                                        a->logprobs, a->ld_logprobs, a->ref_logprobs, a->ld_ref_logprobs, a->values,
+                                        a->ld_values, a->step_values, a->values_dtype, a->lengths,
+                                        a->score_finished, stream, proc);
+    return ppo_sample_launch("trlx_ppo_sample_proc", a->logits, a->ld_logits, a->dtype, a->B, V, a->temperature,
+                             a->top_k, a->top_p, a->min_tokens_to_keep, a->cur_len, a->min_length, a->eos_token_id,
+                             a->pad_token_id, a->u, a->out_ids, a->out_logprobs, a->out_min_kept, a->out_kept_count,
+                             a->unfinished, nullptr, stream, proc);
 }

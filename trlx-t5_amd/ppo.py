@@ -276,14 +276,33 @@ class PPOConfig:
         sampling.ppo_sample_step.  Reads temperature, top_k, top_p, min_length, eos_token_id and
         pad_token_id; `do_sample: False` (greedy) maps to top_k = 1.  `overrides` are passed on
         (u=, out=, generator=, the recording step's ref_logits=, recorder=, values=,
-        score_finished=, or any of the keys above).  Returns (ids [B, 1], logprobs [B])."""
-        from .sampling import ppo_sample_step
+        score_finished=, or any of the keys above).  Returns (ids [B, 1], logprobs [B]).
+
+        With any of repetition_penalty, no_repeat_ngram_size, bad_words_ids, forced_bos_token_id,
+        forced_eos_token_id (and max_length, which the forced eos needs) in gen_kwargs the step is
+        the processing one: a PPOLogitsProcessors is built once per (V, device) and passed on with
+        the override `prefix=` ([B, L] int64: HF's input_ids of the step without the recorder's
+        own tokens) and `prefix_len=`.  Without those keys the step is the plain one and a
+        prefix is not read."""
+        from .sampling import PPOLogitsProcessors, ppo_sample_step
         gk = self.gen_kwargs
         kw = {k: gk[k] for k in ("temperature", "top_k", "top_p", "min_length", "eos_token_id", "pad_token_id")
               if gk.get(k) is not None}
         if not gk.get("do_sample", True):
             kw.update(top_k=1, top_p=1.0)
         kw.update(overrides)
+        pk = {k: gk[k] for k in ("repetition_penalty", "no_repeat_ngram_size", "bad_words_ids",
+                                 "forced_bos_token_id", "forced_eos_token_id") if gk.get(k) is not None}
+        if pk and "processors" not in kw:
+            cache = self.__dict__.setdefault("_processors", {})
+            key = (int(logits.shape[-1]), str(logits.device))
+            if key not in cache:
+                cache[key] = PPOLogitsProcessors(key[0], logits.device, max_length=gk.get("max_length"),
+                                                 eos_token_id=gk.get("eos_token_id"), **pk)
+            kw["processors"] = cache[key]
+        if kw.get("processors") is None:
+            kw.pop("prefix", None)
+            kw.pop("prefix_len", None)
         return ppo_sample_step(logits, cur_len=cur_len, unfinished=unfinished, **kw)
 
     # -------------------------------------------------------------- A5
