@@ -370,6 +370,57 @@ int trlx_ilql_tq_at_actions(const trlx_ilql_tq_args* args, void* stream);
 int trlx_polyak_update(const void* const* src, void* const* target, const int64_t* numel, int64_t count,
                        int dtype, double alpha, void* stream);
 
+/* ---------------------------------------------------------------- fused multi-tensor AdamW
+ * The three lines every update of the reference ends with (accelerate_base_model.py:94-106,
+ * 263-265: opt.step() of torch.optim.AdamW) and, for ILQL, the Polyak sync of
+ * post_backward_callback in the same pass.  For each of `count` tensors, element by element in
+ * fp32, in the order of torch's _single_tensor_adam with decoupled decay, every op rounded
+ * separately (no fma):
+ *   p = p * (1 - lr*wd)
+ *   m = m + (1-b1) * (g - m)
+ *   v = v*b2 + (1-b2) * (g*g)
+ *   p = p + (-(lr/bc1)) * (m / (sqrt(v)/sqrt(bc2) + eps))      bc1 = 1 - b1^step, bc2 = 1 - b2^step
+ * The scalars 1 - lr*wd, 1-b1, b2, 1-b2, -(lr/bc1), sqrt(bc2) and eps are formed in double
+ * by this call and rounded to fp32 once.  step >= 1 is the number of the update being made.
+ *   p      : p_dtype (TRLX_F32 / TRLX_BF16), in/out.
+ *   g      : g_dtype (TRLX_F32 / TRLX_BF16).          m, v : fp32, in/out.
+ *   master : NULL array, or per tensor NULL or an fp32 copy of a bf16 p: the master is what is
+ *            updated and p is written as the master rounded to bf16 (round-to-nearest-even).
+ *            Without it a bf16 p is upcast, updated in fp32 and rounded to bf16 once.  A master
+ *            for an fp32 p is refused.
+ *   target : NULL array, or per tensor NULL or a tensor of p_dtype that receives
+ *              target = (alpha * p_new) + (1 - alpha) * target
+ *            rounded exactly as trlx_polyak_update rounds it (bf16 form included), where p_new
+ *            is the value stored to p (for bf16 the rounded one).
+ * The pointers travel to the kernel by value, TRLX_ADAMW_MAX_TENSORS tensors per launch; a
+ * longer list is split into several launches.  One workgroup takes TRLX_ADAMW_CHUNK elements
+ * of one tensor.  16-byte loads and stores wherever all pointers of a tensor share a 16-byte
+ * phase (one head of fewer than 8 elements brings every one of them to a 16-byte boundary),
+ * element accesses otherwise: any element alignment, any tail length; the result bits do not
+ * depend on the path.  Zero-length tensors are skipped.  The host arrays are read during the
+ * call only.  Refused before anything is launched: a NULL pointer in a live entry
+ * (TRLX_ERR_ARG), a dtype other than the above (TRLX_ERR_DTYPE), a pointer not aligned to its
+ * element size (TRLX_ERR_ARG), any overlap among p, g, m, v, master and target of one entry
+ * (TRLX_ERR_ARG), a tensor of more than TRLX_ADAMW_CHUNK * 2^30 elements (TRLX_ERR_SHAPE),
+ * step < 1 or a NaN scalar (TRLX_ERR_ARG). */
+#define TRLX_ADAMW_MAX_TENSORS 32
+#define TRLX_ADAMW_CHUNK 8192
+typedef struct {
+    int p_dtype, g_dtype;
+    int64_t count;
+    void* const* p;
+    const void* const* g;
+    void* const* m;
+    void* const* v;
+    void* const* master;              /* NULL = no tensor has one */
+    void* const* target;              /* NULL = no tensor has one */
+    const int64_t* numel;
+    int64_t step;
+    double lr, beta1, beta2, eps, weight_decay;
+    double alpha;                     /* read only where a target is given */
+} trlx_adamw_args;
+int trlx_adamw_step(const trlx_adamw_args* args, void* stream);
+
 /* ---------------------------------------------------------------- fused bf16 value head
  * The PPO value head — replaces `make_head(n_embd, 1)` (ppo_models.py:216-222: Linear(H, 2H),
  * ReLU, Linear(2H, 1), all bf16) and its use at :618,:641:

@@ -81,9 +81,25 @@ class PpoSampleProcArgs(ctypes.Structure):
 
 
 POLYAK_MAX_TENSORS = 16
+ADAMW_MAX_TENSORS = 32
+ADAMW_CHUNK = 8192  # elements of one tensor per workgroup
+
+
+class AdamwArgs(ctypes.Structure):
+    """Mirror of trlx_adamw_args (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("p_dtype", _c_int), ("g_dtype", _c_int), ("count", _c_i64),
+        ("p", ctypes.POINTER(_c_vp)), ("g", ctypes.POINTER(_c_vp)), ("m", ctypes.POINTER(_c_vp)),
+        ("v", ctypes.POINTER(_c_vp)), ("master", ctypes.POINTER(_c_vp)), ("target", ctypes.POINTER(_c_vp)),
+        ("numel", ctypes.POINTER(_c_i64)),
+        ("step", _c_i64), ("lr", _c_d), ("beta1", _c_d), ("beta2", _c_d), ("eps", _c_d), ("weight_decay", _c_d),
+        ("alpha", _c_d),
+    ]
+
 
 _ilql_p = ctypes.POINTER(IlqlArgs)
 _ilql_tq_p = ctypes.POINTER(IlqlTqArgs)
+_adamw_p = ctypes.POINTER(AdamwArgs)
 
 CTL_SLOTS = 16
 (CTL_MEAN, CTL_VAR, CTL_STD, CTL_COUNT, CTL_REF_MEAN, CTL_REF_STD, CTL_REF_SET, CTL_KL_COEF, CTL_BATCH_MEAN,
@@ -254,6 +270,7 @@ SIGNATURES = {
     "trlx_ilql_tq_at_actions": (_c_int, [_ilql_tq_p, _c_vp]),
     "trlx_polyak_update": (_c_int, [ctypes.POINTER(_c_vp), ctypes.POINTER(_c_vp), ctypes.POINTER(_c_i64), _c_i64,
                                     _c_int, _c_d, _c_vp]),
+    "trlx_adamw_step": (_c_int, [_adamw_p, _c_vp]),
     "trlx_value_head_splits": (_c_int, [_c_i64, _c_i64]),
     "trlx_value_head_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
     "trlx_value_head_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),

@@ -4,6 +4,7 @@
   ilql_target_q_at_actions    the target heads' second Linear (:31-34, :156) evaluated only
                               at the action tokens a* = input_ids[b, 1 + actions_ixs[b, a]]
   polyak_update               _sync_target_q_heads (:161-168), one launch for all tensors
+  ILQLHeads.step_and_sync     the optimizer step and that sync in one pass (optim.FusedAdamW)
 
 ILQLConfig.loss reads ONE scalar per (b, a) from each target-Q tensor (tq_i[b, a, a*]); the
 reference still builds both target heads over the whole vocabulary ([B·A, 2H] x [2H, V] each).
@@ -86,13 +87,10 @@ def ilql_target_q_at_actions(zs, w2s, b2s, input_ids, actions_ixs):
     return tuple(outs)
 
 
-def polyak_update(targets: Sequence[torch.Tensor], sources: Sequence[torch.Tensor], alpha: float):
-    """target <- (alpha * source) + (1.0 - alpha) * target for every pair, in place, bit for bit
-    what torch's `target.copy_((alpha * source) + (1.0 - alpha) * target)` writes
-    (ilql_models.py:161-168) — one launch per dtype and _lib.POLYAK_MAX_TENSORS tensors instead of
-    three elementwise launches and two temporaries per tensor.  Each pair must agree in dtype
-    (fp32 / bf16) and shape and be contiguous; a source that overlaps its target is refused."""
-    targets, sources = list(targets), list(sources)
+def check_polyak_pairs(targets, sources):
+    """The argument checks of polyak_update (also those of the sync folded into
+    FusedAdamW.step): as many targets as sources, each pair of one dtype (fp32 / bf16) and
+    shape, contiguous."""
     if len(targets) != len(sources):
         raise ValueError(f"{len(targets)} targets but {len(sources)} sources")
     for i, (t, s) in enumerate(zip(targets, sources)):
@@ -104,6 +102,16 @@ def polyak_update(targets: Sequence[torch.Tensor], sources: Sequence[torch.Tenso
             raise ValueError(f"pair {i}: target has shape {tuple(t.shape)} but source {tuple(s.shape)}")
         if not (t.is_contiguous() and s.is_contiguous()):
             raise ValueError(f"pair {i}: tensors must be contiguous")
+
+
+def polyak_update(targets: Sequence[torch.Tensor], sources: Sequence[torch.Tensor], alpha: float):
+    """target <- (alpha * source) + (1.0 - alpha) * target for every pair, in place, bit for bit
+    what torch's `target.copy_((alpha * source) + (1.0 - alpha) * target)` writes
+    (ilql_models.py:161-168) — one launch per dtype and _lib.POLYAK_MAX_TENSORS tensors instead of
+    three elementwise launches and two temporaries per tensor.  Each pair must agree in dtype
+    (fp32 / bf16) and shape and be contiguous; a source that overlaps its target is refused."""
+    targets, sources = list(targets), list(sources)
+    check_polyak_pairs(targets, sources)
     _lib.require_cuda(*targets, *sources)
     for dt in (torch.float32, torch.bfloat16):
         pairs = [(t, s) for t, s in zip(targets, sources) if t.dtype == dt]
@@ -180,3 +188,13 @@ class ILQLHeads(nn.Module):
         targets = [p.data for h in self.target_q_heads for p in h.parameters()]
         sources = [p.data for h in self.q_heads for p in h.parameters()]
         polyak_update(targets, sources, self.config.alpha)
+
+    def step_and_sync(self, opt, closure=None):
+        """opt.step() and sync_target_q_heads() in one pass (opt: a FusedAdamW over these heads'
+        parameters): every Q parameter the optimizer steps updates its target from the value
+        just formed, bit for bit what the two calls leave; a Q parameter without a gradient is
+        synced by polyak_update.  For the updates on which post_backward_callback syncs
+        (every steps_for_target_q_sync); the others call opt.step()."""
+        targets = [p.data for h in self.target_q_heads for p in h.parameters()]
+        sources = [p.data for h in self.q_heads for p in h.parameters()]
+        return opt.step(closure, polyak=(targets, sources, self.config.alpha))

@@ -1,0 +1,245 @@
+"""Fused multi-tensor AdamW for MI355X — the counterpart of the three lines every update of the
+reference ends with (accelerate_base_model.py:94-106, 263-265):
+
+  FusedAdamW      torch.optim.AdamW's constructor, param_groups and state keys (step, exp_avg,
+                  exp_avg_sq), so CosineAnnealingLR drives it unchanged and state_dicts move
+                  between the two; one launch per dtype combination instead of torch's launch
+                  train.  master_weights=True keeps an fp32 master per bf16 parameter.
+  adamw_step      the functional form over lists of tensors.
+  step(polyak=)   the ILQL target-head sync (post_backward_callback, ilql_models.py:161-181)
+                  folded into the same pass: the target is updated from the parameter values
+                  still in registers (ILQLHeads.step_and_sync).
+
+Every element goes through torch's _single_tensor_adam ops in fp32, each rounded separately
+(trlx_adamw_step in include/trlx_t5_amd.h).  exp_avg and exp_avg_sq are always fp32.
+"""
+import ctypes
+from itertools import chain
+from typing import Optional, Sequence
+
+import torch
+
+from . import _lib
+from .ilql_heads import check_polyak_pairs, polyak_update
+
+__all__ = ["FusedAdamW", "adamw_step"]
+
+_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def _check_entry(i, p, g, m, v, master):
+    if p.dtype not in _DTYPES:
+        raise ValueError(f"tensor {i}: unsupported parameter dtype {p.dtype} (float32 / bfloat16)")
+    if g.dtype not in _DTYPES:
+        raise ValueError(f"tensor {i}: unsupported gradient dtype {g.dtype} (float32 / bfloat16)")
+    if g.layout != torch.strided:
+        raise ValueError(f"tensor {i}: sparse gradients are not supported")
+    for name, t in (("exp_avg", m), ("exp_avg_sq", v), ("master", master)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise ValueError(f"tensor {i}: {name} must be float32, got {t.dtype}")
+    if master is not None and p.dtype != torch.bfloat16:
+        raise ValueError(f"tensor {i}: a master is for a bfloat16 parameter, this one is {p.dtype}")
+    for name, t in (("grad", g), ("exp_avg", m), ("exp_avg_sq", v), ("master", master)):
+        if t is None:
+            continue
+        if tuple(t.shape) != tuple(p.shape):
+            raise ValueError(f"tensor {i}: {name} has shape {tuple(t.shape)} but the parameter {tuple(p.shape)}")
+        if t.device != p.device:
+            raise ValueError(f"tensor {i}: {name} is on {t.device} but the parameter on {p.device}")
+    for name, t in (("parameter", p), ("grad", g), ("exp_avg", m), ("exp_avg_sq", v), ("master", master)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"tensor {i}: {name} must be contiguous")
+
+
+def _key(t):
+    return (t.data_ptr(), tuple(t.shape), t.dtype, t.device)
+
+
+def _fold(params, polyak):
+    """(targets aligned with params, alpha, leftover targets, leftover sources): a source that
+    is one of `params` gets its target updated inside the step, the others by polyak_update."""
+    if polyak is None:
+        return [None] * len(params), 0.0, [], []
+    targets, sources, alpha = polyak
+    targets, sources = list(targets), list(sources)
+    check_polyak_pairs(targets, sources)
+    _lib.require_cuda(*targets, *sources)
+    where = {_key(p): i for i, p in enumerate(params) if p.numel()}
+    aligned, rest_t, rest_s = [None] * len(params), [], []
+    for t, s in zip(targets, sources):
+        i = where.get(_key(s))
+        if i is None or aligned[i] is not None:
+            rest_t.append(t)
+            rest_s.append(s)
+        else:
+            aligned[i] = t
+    return aligned, float(alpha), rest_t, rest_s
+
+
+def _launch(entries, step, lr, beta1, beta2, eps, weight_decay, alpha):
+    """entries: (p, g, m, v, master or None, target or None), validated.  One trlx_adamw_step per
+    (parameter dtype, gradient dtype, device)."""
+    groups = {}
+    for e in entries:
+        groups.setdefault((e[0].dtype, e[1].dtype, e[0].device), []).append(e)
+    for (pd, gd, dev), es in groups.items():
+        n = len(es)
+
+        def column(k):
+            return (ctypes.c_void_p * n)(*[_lib.ptr(e[k]) for e in es])
+
+        cols = [column(k) for k in range(6)]
+        a = _lib.AdamwArgs()
+        a.p_dtype, a.g_dtype, a.count = _lib.dtype_code(es[0][0]), _lib.dtype_code(es[0][1]), n
+        a.p, a.g, a.m, a.v, a.master, a.target = cols
+        a.numel = (ctypes.c_int64 * n)(*[e[0].numel() for e in es])
+        a.step, a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = int(step), lr, beta1, beta2, eps, weight_decay
+        a.alpha = alpha
+        with torch.cuda.device(dev):
+            _lib.call("trlx_adamw_step", ctypes.byref(a), _lib.stream_of(es[0][0]))
+
+
+def _check_hyper(lr, betas, eps, weight_decay):
+    lr, (b1, b2), eps, wd = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+    if not 0.0 <= lr:
+        raise ValueError(f"Invalid learning rate: {lr}")
+    if not 0.0 <= eps:
+        raise ValueError(f"Invalid epsilon value: {eps}")
+    if not 0.0 <= b1 < 1.0:
+        raise ValueError(f"Invalid beta parameter at index 0: {b1}")
+    if not 0.0 <= b2 < 1.0:
+        raise ValueError(f"Invalid beta parameter at index 1: {b2}")
+    if not 0.0 <= wd:
+        raise ValueError(f"Invalid weight_decay value: {wd}")
+    return lr, b1, b2, eps, wd
+
+
+def adamw_step(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp_avgs: Sequence[torch.Tensor],
+               exp_avg_sqs: Sequence[torch.Tensor], *, step: int, lr: float, betas, eps: float, weight_decay: float,
+               masters: Optional[Sequence[Optional[torch.Tensor]]] = None, polyak=None):
+    """One AdamW update (decoupled decay) of every tensor, in place, `step` >= 1 being the number
+    of this update (torch's state["step"] after its increment).  params: fp32 / bf16; grads:
+    fp32 / bf16; exp_avgs, exp_avg_sqs: fp32; masters: None, or per tensor None or the fp32
+    master of a bf16 parameter (the master is updated, the parameter is the master rounded to
+    bf16).  polyak=(targets, sources, alpha): after the update, target <- alpha·source +
+    (1 - alpha)·target as polyak_update writes it; a source that is one of `params` is synced
+    inside the same launch.  Tensors are grouped by dtype combination and device: one launch per
+    group and _lib.ADAMW_MAX_TENSORS tensors.  All tensors contiguous, on a ROCm device."""
+    params, grads, exp_avgs, exp_avg_sqs = list(params), list(grads), list(exp_avgs), list(exp_avg_sqs)
+    masters = [None] * len(params) if masters is None else list(masters)
+    if not (len(params) == len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(masters)):
+        raise ValueError(f"{len(params)} params but {len(grads)} grads, {len(exp_avgs)} exp_avgs, "
+                         f"{len(exp_avg_sqs)} exp_avg_sqs, {len(masters)} masters")
+    if int(step) != step or step < 1:
+        raise ValueError(f"step must be an integer >= 1 (the number of this update), got {step}")
+    lr, b1, b2, eps, wd = _check_hyper(lr, betas, eps, weight_decay)
+    for i, e in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs, masters)):
+        _check_entry(i, *e)
+    if polyak is not None:
+        check_polyak_pairs(list(polyak[0]), list(polyak[1]))
+    _lib.require_cuda(*params, *grads, *exp_avgs, *exp_avg_sqs, *masters)
+    targets, alpha, rest_t, rest_s = _fold(params, polyak)
+    _launch(list(zip(params, grads, exp_avgs, exp_avg_sqs, masters, targets)), step, lr, b1, b2, eps, wd, alpha)
+    if rest_t:
+        polyak_update(rest_t, rest_s, alpha)
+
+
+class FusedAdamW(torch.optim.Optimizer):
+    """torch.optim.AdamW on the fused kernel.  Same constructor arguments (lr, betas, eps,
+    weight_decay), param_groups and state keys (step: a CPU scalar tensor, exp_avg, exp_avg_sq),
+    so lr schedulers drive it unchanged and a torch.optim.AdamW.state_dict() loads into it and
+    the other way round.  exp_avg and exp_avg_sq are fp32 whatever the parameter's dtype.
+    master_weights=True keeps an fp32 `master` state per bf16 parameter (absent for fp32
+    parameters): the master takes the update, the parameter is the master rounded to bf16.
+    A parameter whose .grad is None is skipped and its step does not advance.  amsgrad,
+    maximize, sparse gradients and complex parameters raise ValueError."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *,
+                 maximize=False, master_weights=False):
+        if isinstance(lr, torch.Tensor):
+            lr = float(lr)
+        _check_hyper(lr, betas, eps, weight_decay)
+        if amsgrad:
+            raise ValueError("FusedAdamW does not support amsgrad")
+        if maximize:
+            raise ValueError("FusedAdamW does not support maximize")
+        # the keys of torch.optim.AdamW's groups, so the two state_dicts have one structure
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                        foreach=None, capturable=False, differentiable=False, fused=None,
+                        decoupled_weight_decay=True)
+        self.master_weights = bool(master_weights)
+        super().__init__(params, defaults)
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.is_complex():
+                    raise ValueError("FusedAdamW does not support complex parameters")
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            if group.get("amsgrad") or group.get("maximize"):
+                raise ValueError("FusedAdamW does not support amsgrad / maximize (loaded param_groups)")
+        # Optimizer.load_state_dict casts every state tensor to its parameter's dtype; exp_avg,
+        # exp_avg_sq and master of a bf16 parameter are fp32 here: take them from the saved values
+        saved = state_dict["state"]
+        ids = chain.from_iterable(g["params"] for g in state_dict["param_groups"])
+        ours = chain.from_iterable(g["params"] for g in self.param_groups)
+        for pid, p in zip(ids, ours):
+            if pid not in saved or p.dtype == torch.float32:
+                continue
+            for k in ("exp_avg", "exp_avg_sq", "master"):
+                if k in saved[pid]:
+                    self.state[p][k] = saved[pid][k].to(device=p.device, dtype=torch.float32, copy=True)
+
+    def _init_state(self, p):
+        state = self.state[p]
+        if "step" not in state:
+            state["step"] = torch.tensor(0.0, dtype=torch.float32)
+            state["exp_avg"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+            state["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+        if self.master_weights and p.dtype == torch.bfloat16 and "master" not in state:
+            state["master"] = p.detach().to(torch.float32, memory_format=torch.contiguous_format, copy=True)
+        return state
+
+    @torch.no_grad()
+    def step(self, closure=None, *, polyak=None):
+        """One update of every parameter that has a gradient.  polyak=(targets, sources, alpha):
+        the Polyak sync target <- alpha·source + (1 - alpha)·target after the update, bit for
+        bit what step() followed by polyak_update(targets, sources, alpha) leaves; every source
+        that is stepped in this call is synced inside the optimizer's launch, any other one by
+        polyak_update."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        work = []  # (group, p, state), everything validated before any state changes
+        for group in self.param_groups:
+            if group.get("amsgrad") or group.get("maximize"):
+                raise ValueError("FusedAdamW does not support amsgrad / maximize")
+            _check_hyper(group["lr"], group["betas"], group["eps"], group["weight_decay"])
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise ValueError("FusedAdamW does not support sparse gradients")
+                if p.is_complex():
+                    raise ValueError("FusedAdamW does not support complex parameters")
+                _lib.require_cuda(p, p.grad)
+                state = self._init_state(p)
+                _check_entry(len(work), p, p.grad, state["exp_avg"], state["exp_avg_sq"], state.get("master"))
+                work.append((group, p, state))
+        targets, alpha, rest_t, rest_s = _fold([p for _, p, _ in work], polyak)
+        buckets = {}  # one launch set per (group, step number): the scalars are per launch
+        for (group, p, state), target in zip(work, targets):
+            state["step"] += 1
+            k = (id(group), int(state["step"].item()))
+            buckets.setdefault(k, (group, []))[1].append(
+                (p, p.grad, state["exp_avg"], state["exp_avg_sq"], state.get("master"), target))
+        for (_, step), (group, entries) in buckets.items():
+            lr, b1, b2, eps, wd = _check_hyper(group["lr"], group["betas"], group["eps"], group["weight_decay"])
+            _launch(entries, step, lr, b1, b2, eps, wd, alpha)
+        if rest_t:
+            polyak_update(rest_t, rest_s, alpha)
+        return loss
