@@ -6,12 +6,34 @@ against the fp64 oracle on the same inputs; the kernel must satisfy
     max|kernel − (b)| <= 2·e_ref + 1e-6·max|(b)|
 for the values and for each of dh, dW1, db1, dw2, db2 (see value_head_checks).
 
-Shapes: H in {32, 64, 160, 768} (one K step, one MFMA column group, a ragged column slice, the
-product size) with N in {1, 65}, and N in {1, 63, 64, 65, 130} (one token, a partial block, an
-exact block, one and two over) with H = 64.
+Shapes, automatic split count (on a 256-CU part every one of them gives each workgroup ONE
+32-column slice, so one chunk and one epilogue): H in {32, 64, 160, 768} (one K step, one MFMA
+column group, a ragged column slice, the product size) with N in {1, 65}, and N in {1, 63, 64, 65,
+130} (one token, a partial block, an exact block, one and two over) with H = 64.
+
+Shapes, forced split count S in {1, 2, 3} (value_head_checks.multi_chunk_cases: the training
+shapes' geometry, several 128-column chunks per workgroup, at small N; S = 3 and S = 2 are what
+C2 and the C3 shard get).  With nk = H/32 K steps a chunk, the stage ring's phase at a chunk
+boundary is (chunk·nk) mod 3 and the b1 / w2 vector slot is chunk mod 3:
+    H   96  nk  3 (mod 3 = 0)   2 chunks at S = 1 (128 + a ragged 64): the smallest multi-chunk walk
+    H  128  nk  4 (1)           2 chunks: a step right after an epilogue, ring phase 1
+    H  256  nk  8 (2)           4 chunks: the first reuse of a vector slot; S 2, 3: 2 chunks, ragged at 3
+    H  288  nk  9 (0)           5 chunks, the last a ragged 64 after a slot reuse; S 2: 3, S 3: 2 chunks
+    H  320  nk 10 (1)           5 chunks; S 2: 3 (ragged 64), S 3: 2 (ragged 64 / 96)
+    H  448  nk 14 (2)           7 chunks: the vector ring wraps twice; S 2: 4 (ragged), S 3: 3 (ragged)
+    H  768  nk 24 (0)           12 chunks, the product's H; S 2: 6 chunks (C3 shard), S 3: 4 (C2)
+(H 96 and 128 only at S = 1: their S = 2, 3 slices are single chunks.)  N = 65 (two token blocks,
+the second with one token) at every H; at H 256 and 768 also N = 1, N = 33 (the second half block
+holds one token) and N = 130 (three blocks, the last with an empty half block that has to write
+zero column sums).  Beside the tolerance rule, checks no tolerance can hide: the raw backward's dz,
+dw2, db1, db2 are bit-identical for S in {1, 2, 3, cap} (a column's z has one K order whatever
+slice or chunk holds it, dz is element-wise, the column sums run over tokens); with a one-hot w2
+and b2 = 0 the fp32 values are relu(bf16(z_j)) and bit-identical over S; fp32 gradients round to
+the bf16 ones; a row-strided h gives the contiguous backward's bits; guard elements past values,
+dz, dw2, db1 stay intact.  Every raw call here starts from a workspace of NaN bit patterns.
 
 TRLX_VALUE_HEAD_PARITY_OUT=<file>: the measured figures of the parity cases are written there
-(profiles/value_head_parity.json is such a run).
+(profiles/value_head_parity.json is such a run; "S" is the forced split count, 0 = automatic).
 """
 import json
 import os
@@ -30,6 +52,8 @@ VH = sys.modules["trlx_t5_amd.value_head"]
 KEYS = ("h", "w1", "b1", "w2", "b2")
 SHAPES = [(1, 32), (65, 32), (1, 64), (63, 64), (64, 64), (65, 64), (130, 64), (1, 160), (65, 160), (1, 768),
           (65, 768)]
+MULTI = C.multi_chunk_cases()
+MULTI_NH = sorted({(N, H) for N, H, _ in MULTI}, key=lambda k: (k[1], k[0]))
 _REFS = {}
 _FIGURES = {}
 
@@ -37,7 +61,7 @@ _FIGURES = {}
 def refs(N, H):
     """The case's operands and both restatements, computed once and shared (never modified)."""
     if (N, H) not in _REFS:
-        c = C.make_case(N, H, 1000 * H + N)
+        c = C.make_case(N, H, C.case_seed(N, H))
         args = [c[k] for k in KEYS]
         _REFS[(N, H)] = (c, C.reference_bf16(*args, dv=c["dv"]), C.oracle_fp64(*args, dv=c["dv"]))
     return _REFS[(N, H)]
@@ -62,16 +86,18 @@ def parity_figures():
                        "cases": [_FIGURES[k] for k in sorted(_FIGURES)]}, f, indent=1)
 
 
-@pytest.mark.parametrize("N,H", SHAPES)
-def test_parity_values_and_gradients(N, H):
+def parity(N, H, S):
+    """Values and the five gradients through autograd under the rule; S = 0: the automatic split count."""
     c, a, b = refs(N, H)
     ops = dev_ops(c, grad=True)
-    v = P.value_head(*ops)
-    assert v.dtype == torch.float32 and tuple(v.shape) == (N,)
-    v.backward(c["dv"].float().to(DEV))
-    torch.cuda.synchronize()
+    with _lib.tuning(vhead_splits=S):
+        splits = P.value_head_splits(N, H)
+        v = P.value_head(*ops)
+        assert v.dtype == torch.float32 and tuple(v.shape) == (N,)
+        v.backward(c["dv"].float().to(DEV))
+        torch.cuda.synchronize()
     got = dict(values=v, dh=ops[0].grad, dw1=ops[1].grad, db1=ops[2].grad, dw2=ops[3].grad, db2=ops[4].grad)
-    fig = {"N": N, "H": H, "splits": P.value_head_splits(N, H)}
+    fig = {"N": N, "H": H, "S": S, "splits": splits}
     failed = []
     for k in ("values",) + C.GRADS:
         assert got[k] is not None, k
@@ -80,11 +106,25 @@ def test_parity_values_and_gradients(N, H):
         e_ref, e_k = C.max_err(a[k], b[k]), C.max_err(got[k], b[k])
         lim = C.bound(e_ref, b[k])
         fig[k] = {"e_ref": e_ref, "e_kernel": e_k, "bound": lim, "max_abs": float(b[k].abs().max())}
-        print(f"N={N} H={H} {k}: e_ref={e_ref:.6g} e_kernel={e_k:.6g} bound={lim:.6g}")
+        print(f"N={N} H={H} S={S} {k}: e_ref={e_ref:.6g} e_kernel={e_k:.6g} bound={lim:.6g}")
         if not e_k <= lim:
             failed.append(k)
-    _FIGURES[(H, N)] = fig
+    _FIGURES[(H, N, S)] = fig
     assert not failed, f"over the bound: {failed}: {fig}"
+    return splits
+
+
+@pytest.mark.parametrize("N,H", SHAPES)
+def test_parity_values_and_gradients(N, H):
+    assert parity(N, H, 0) == P.value_head_splits(N, H)
+
+
+@pytest.mark.parametrize("N,H,S", MULTI)
+def test_multi_chunk_parity_values_and_gradients(N, H, S):
+    """Forward and backward at a forced split count that gives a workgroup two to twelve chunks
+    (the header's table), under the unchanged rule."""
+    assert max(C.chunks(H, S)) >= 2
+    assert parity(N, H, S) == S
 
 
 @pytest.mark.parametrize("S", [1, 2, 3, 64])
@@ -142,19 +182,188 @@ def test_output_dtype_rounds_once(N, H):
     assert v16.dtype == torch.bfloat16 and torch.equal(bits(v16), bits(v32.to(torch.bfloat16)))
 
 
-def raw_backward(ops, dv, dv_dtype=None):
-    """trlx_value_head_bwd itself: (dz, dw2, db1, db2)."""
+def nan_workspace(nbytes):
+    """A workspace whose every fp32 is a NaN bit pattern: what a launch does not write shows."""
+    return torch.full((max(int(nbytes), 4),), 0xFF, dtype=torch.uint8, device=DEV)
+
+
+def raw_forward(ops, extra=0, out_dtype=torch.float32):
+    """trlx_value_head_fwd itself into a [N + extra] tensor preset to 7."""
+    h, w1, b1, w2, b2 = ops
+    N, H = h.shape
+    out = torch.full((N + extra,), 7.0, dtype=out_dtype, device=DEV)
+    ws = nan_workspace(_lib.query("trlx_value_head_workspace_bytes", N, H))
+    _lib.call("trlx_value_head_fwd", h.data_ptr(), h.stride(0), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+              b2.data_ptr(), N, H, out.data_ptr(), _lib.dtype_code(out), ws.data_ptr(), _lib.stream_of(h))
+    return out
+
+
+def raw_backward(ops, dv, dv_dtype=None, grad_dtype=torch.bfloat16, extra_rows=0, extra=0):
+    """trlx_value_head_bwd itself: (dz, dw2, db1, db2), preset to 7, dz with extra_rows rows and
+    dw2 / db1 / db2 with `extra` elements beyond what the entry owns."""
     h, w1, b1, w2 = ops[:4]
     N, H = h.shape
-    dz = torch.full((N, 2 * H), 7.0, dtype=torch.bfloat16, device=DEV)
-    dw2 = torch.full((2 * H,), 7.0, dtype=torch.bfloat16, device=DEV)
-    db1 = torch.full((2 * H,), 7.0, dtype=torch.bfloat16, device=DEV)
-    db2 = torch.full((1,), 7.0, dtype=torch.bfloat16, device=DEV)
-    ws = torch.empty(_lib.query("trlx_value_head_bwd_workspace_bytes", N, H), dtype=torch.uint8, device=DEV)
+    dz = torch.full((N + extra_rows, 2 * H), 7.0, dtype=torch.bfloat16, device=DEV)
+    dw2 = torch.full((2 * H + extra,), 7.0, dtype=grad_dtype, device=DEV)
+    db1 = torch.full((2 * H + extra,), 7.0, dtype=grad_dtype, device=DEV)
+    db2 = torch.full((1 + extra,), 7.0, dtype=grad_dtype, device=DEV)
+    ws = nan_workspace(_lib.query("trlx_value_head_bwd_workspace_bytes", N, H))
     _lib.call("trlx_value_head_bwd", h.data_ptr(), h.stride(0), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
               dv.data_ptr(), _lib.dtype_code(dv) if dv_dtype is None else dv_dtype, N, H, dz.data_ptr(),
-              dw2.data_ptr(), db1.data_ptr(), db2.data_ptr(), _lib.BF16, ws.data_ptr(), _lib.stream_of(h))
+              dw2.data_ptr(), db1.data_ptr(), db2.data_ptr(), _lib.dtype_code(dw2), ws.data_ptr(), _lib.stream_of(h))
     return dz, dw2, db1, db2
+
+
+def split_counts(H):
+    return sorted({1, 2, 3, C.split_cap(H)})
+
+
+@pytest.mark.parametrize("N,H", MULTI_NH)
+def test_backward_bits_do_not_depend_on_the_split_count(N, H):
+    """dz, dw2, db1 and db2 of the raw entry at S in {1, 2, 3, cap}: a column's z is the same MFMA
+    K order in whatever slice and chunk it sits, dz is element-wise and the column sums run over
+    the tokens in half-block order, so nothing may differ.  The cap is the one-chunk path of the
+    automatic cases: the multi-chunk walk (epilogue stores in the queue of the next steps' DMAs,
+    a reused vector slot, a ragged last chunk) is tied to it bit for bit."""
+    c, _, b = refs(N, H)
+    ops, dv = dev_ops(c), c["dv"].to(DEV)
+    got = {}
+    for S in split_counts(H):
+        with _lib.tuning(vhead_splits=S):
+            assert P.value_head_splits(N, H) == S
+            got[S] = [bits(t) for t in raw_backward(ops, dv)]
+    torch.cuda.synchronize()
+    for S in split_counts(H)[1:]:
+        for name, x, y in zip(("dz", "dw2", "db1", "db2"), got[1], got[S]):
+            assert torch.equal(x, y), f"{name} at S={S} differs from S=1 in {int((x != y).sum())} elements"
+    assert float((got[1][0] != 0).double().mean()) > 0.2   # not a row of sentinels or zeros
+
+
+@pytest.mark.parametrize("H", [256, 288, 768])
+def test_one_hot_w2_returns_the_column_for_every_split_count(H):
+    """w2 = e_j, b2 = 0: v_t = relu(bf16(z_tj)) exactly (every other term is fma(r, 0, acc)), so
+    the fp32 values are bit-identical over S in {1, 2, 3, cap} and meet the rule against the
+    oracle, for the first and last column of every chunk and the column-group edges inside one:
+    a wrong column, vector slot or mask that a random w2 averages away shows at its column."""
+    N = 65
+    c = dict(refs(N, H)[0])
+    h, w1, b1 = (c[k].to(DEV) for k in ("h", "w1", "b1"))
+    b2 = torch.zeros(1, dtype=torch.bfloat16)
+    w2d, b2d = torch.zeros(1, 2 * H, dtype=torch.bfloat16, device=DEV), b2.to(DEV)
+    z64 = c["h"].double() @ c["w1"].double().t() + c["b1"].double()
+    want = torch.relu(z64.float().to(torch.bfloat16).double())
+    failed = []
+    for j in C.one_hot_columns(H):
+        w2 = torch.zeros(1, 2 * H, dtype=torch.bfloat16)
+        w2[0, j] = 1.0
+        w2d.zero_()
+        w2d[0, j] = 1.0
+        got = {}
+        for S in split_counts(H):
+            with _lib.tuning(vhead_splits=S):
+                got[S] = P.value_head(h, w1, b1, w2d, b2d)
+        torch.cuda.synchronize()
+        for S in split_counts(H)[1:]:
+            assert torch.equal(bits(got[1]), bits(got[S])), (j, S)
+        a = C.reference_bf16(c["h"], c["w1"], c["b1"], w2, b2)
+        oracle = C.oracle_fp64(c["h"], c["w1"], c["b1"], w2, b2)["values"]
+        assert torch.equal(oracle, want[:, j])
+        e_ref, e_k = C.max_err(a["values"], oracle), C.max_err(got[1], oracle)
+        print(f"one-hot H={H} j={j}: e_ref={e_ref:.6g} e_kernel={e_k:.6g} max={float(oracle.max()):.6g}")
+        assert float(oracle.max()) > 0   # the column is live for some token
+        if not e_k <= C.bound(e_ref, oracle):
+            failed.append((j, e_ref, e_k))
+    assert not failed, failed
+
+
+def test_backward_dtypes_round_once():
+    """grad_dtype F32: the three fp32 outputs, rounded to bf16 by torch, are the bf16 outputs; dv
+    as fp32 holding the same bf16 numbers gives the bits of dv as bf16."""
+    N, H = 65, 256
+    c, _, b = refs(N, H)
+    ops, dv = dev_ops(c), c["dv"].to(DEV)
+    with _lib.tuning(vhead_splits=1):
+        assert P.value_head_splits(N, H) == 1
+        base = raw_backward(ops, dv)
+        wide = raw_backward(ops, dv, grad_dtype=torch.float32)
+        dv32 = raw_backward(ops, dv.float())
+        both = raw_backward(ops, dv.float(), grad_dtype=torch.float32)
+    torch.cuda.synchronize()
+    for res in (wide, both):
+        assert torch.equal(bits(res[0]), bits(base[0]))
+        for name, x, y in zip(("dw2", "db1", "db2"), res[1:], base[1:]):
+            assert x.dtype == torch.float32 and y.dtype == torch.bfloat16
+            assert torch.equal(bits(x.to(torch.bfloat16)), bits(y)), name
+    assert bool((wide[1] != wide[1].to(torch.bfloat16).float()).any())   # fp32 sums, not widened bf16
+    for name, x, y in zip(("dz", "dw2", "db1", "db2"), dv32, base):
+        assert x.dtype == torch.bfloat16 and torch.equal(bits(x), bits(y)), name
+    # and the fp32 sums are nearer the oracle than their bf16 roundings may be
+    for k, x in (("dw2", wide[1]), ("db1", wide[2]), ("db2", wide[3])):
+        assert C.max_err(x, b[k]) <= C.max_err(x.to(torch.bfloat16), b[k]) + 1e-6 * float(b[k].abs().max()), k
+
+
+@pytest.mark.parametrize("N,H,S", [(65, 256, 1), (65, 768, 2)])
+def test_backward_reads_row_strided_h_in_place(N, H, S):
+    """Autograd through h3[:, -1, :] of a [N, 3, H] tensor and through a view behind a one-row
+    offset: all five gradients carry the contiguous case's bits, dh has the view's shape and
+    nothing else of the base receives a gradient."""
+    c, _, _ = refs(N, H)
+    dv = c["dv"].float().to(DEV)
+    g = torch.Generator().manual_seed(5)
+    with _lib.tuning(vhead_splits=S):
+        assert P.value_head_splits(N, H) == S
+        ops = dev_ops(c, grad=True)
+        P.value_head(*ops).backward(dv)
+        want = [bits(t.grad) for t in ops]
+        h3 = torch.randn(N, 3, H, generator=g).to(torch.bfloat16).to(DEV)
+        h3[:, -1, :] = ops[0].detach()
+        big = torch.randn(N + 1, H, generator=g).to(torch.bfloat16).to(DEV)
+        big[1:] = ops[0].detach()
+        for base, pick in ((h3, lambda t: t[:, -1, :]), (big, lambda t: t[1:])):
+            base.requires_grad_(True)
+            view = pick(base)
+            view.retain_grad()
+            assert tuple(view.shape) == (N, H) and VH._rows(view.detach(), H).data_ptr() == view.data_ptr()
+            assert not view.is_contiguous() or view.data_ptr() != base.data_ptr()
+            rest = dev_ops(c, grad=True)[1:]
+            v = P.value_head(view, *rest)
+            v.backward(dv)
+            torch.cuda.synchronize()
+            assert tuple(view.grad.shape) == (N, H) and view.grad.dtype == torch.bfloat16
+            for name, x, t in zip(C.GRADS, want, [view] + rest):
+                assert torch.equal(x, bits(t.grad)), name
+            assert base.grad.shape == base.shape and torch.equal(bits(pick(base.grad)), want[0])
+            outside = base.grad.clone()
+            pick(outside).zero_()
+            assert float(outside.float().abs().max()) == 0
+    assert h3.stride(0) == 3 * H
+
+
+@pytest.mark.parametrize("N,H,S", [(65, 288, 1), (130, 256, 2)])
+def test_raw_entries_leave_guard_elements_intact(N, H, S):
+    """values with N + 8 elements, dz with N + 1 rows, dw2 / db1 / db2 with 8 elements more: the
+    sentinels in the excess survive, and what the entries own is what the exact-size call writes
+    (a ragged last chunk whose masked columns lie past 2H at (65, 288, 1); an empty half block
+    and the combine at (130, 256, 2))."""
+    c, _, _ = refs(N, H)
+    ops, dv = dev_ops(c), c["dv"].to(DEV)
+    with _lib.tuning(vhead_splits=S):
+        assert P.value_head_splits(N, H) == S
+        v, vg = raw_forward(ops), raw_forward(ops, extra=8)
+        v16 = raw_forward(ops, extra=8, out_dtype=torch.bfloat16)
+        exact = raw_backward(ops, dv)
+        guard = raw_backward(ops, dv, extra_rows=1, extra=8)
+        guard32 = raw_backward(ops, dv, grad_dtype=torch.float32, extra_rows=1, extra=8)
+    torch.cuda.synchronize()
+    assert bool((vg[N:] == 7.0).all()) and torch.equal(bits(vg[:N]), bits(v))
+    assert bool((v16[N:] == 7.0).all()) and torch.equal(bits(v16[:N]), bits(v.to(torch.bfloat16)))
+    for res in (guard, guard32):
+        dz, dw2, db1, db2 = res
+        assert bool((dz[N:] == 7.0).all()) and torch.equal(bits(dz[:N]), bits(exact[0]))
+        for name, x, y, n in (("dw2", dw2, exact[1], 2 * H), ("db1", db1, exact[2], 2 * H), ("db2", db2, exact[3], 1)):
+            assert bool((x[n:] == 7.0).all()), name
+            assert torch.equal(bits(x[:n].to(torch.bfloat16)), bits(y)), name
+    assert not bool((exact[0] == 7.0).all(1).any())   # every dz row was written
 
 
 @pytest.mark.parametrize("N,H,S", [(65, 64, 0), (65, 160, 3)])

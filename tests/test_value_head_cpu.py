@@ -1,8 +1,10 @@
 """CPU-only checks of the fused value head: the oracle's restatement (a) reproduces the reference's
 make_head(n_embd, 1) bit for bit (tests/golden/value_head.npz, written by
 tests/golden/make_golden_value_head.py from the reference), ValueHead is the reference's module
-to a state_dict, the argument checks raise before any library call, and the binding table holds
-the new entries."""
+to a state_dict, the argument checks raise before any library call, the binding table holds
+the new entries, and the GPU suite's acceptance rule passes a restatement of the kernel's chunked
+column walk and rejects the defects that only a multi-chunk workgroup can have."""
+import functools
 import re
 import os
 
@@ -129,3 +131,52 @@ def test_binding_table_and_header_hold_the_new_entries():
     assert "vhead_splits" in open(HEADER).read()
     for name in ("value_head", "ValueHead"):
         assert name in P.__all__ and hasattr(P, name)
+
+
+# ---- the acceptance rule can fail: value_head_checks.chunked_walk and its defect switch
+MULTI = C.multi_chunk_cases()
+# (defect, N, H, S) where the walk has the defect's place but the rule does not see it; none so far
+NOT_REJECTED = set()
+
+
+@functools.lru_cache(maxsize=None)
+def _case_refs(N, H):
+    c = C.make_case(N, H, C.case_seed(N, H))
+    args = [c[k] for k in ("h", "w1", "b1", "w2", "b2")]
+    return c, C.reference_bf16(*args, dv=c["dv"]), C.oracle_fp64(*args, dv=c["dv"])
+
+
+def test_multi_chunk_case_list_is_the_planned_one():
+    assert len(MULTI) == len(set(MULTI)) == 35
+    assert {(H, S) for _, H, S in MULTI} == {(96, 1), (128, 1)} | {(H, S) for H in (256, 288, 320, 448, 768)
+                                                                  for S in (1, 2, 3)}
+    assert [C.chunks(H, 1)[0] for H in C.MULTI_H] == [2, 2, 4, 5, 5, 7, 12]
+    assert [(H // 32) % 3 for H in C.MULTI_H] == [0, 1, 2, 0, 1, 2, 0]
+    assert C.slices(768, 3) == [(0, 512), (512, 1024), (1024, 1536)] and C.chunks(768, 2) == [6, 6]   # C2, C3
+    assert C.slices(160, 3) == [(0, 96), (96, 192), (192, 320)] and C.slices(32, 64) == [(0, 32), (32, 64)]
+    assert {N for N, H, _ in MULTI if H in C.FULL_N_H} == set(C.FULL_N)
+    assert {N for N, H, _ in MULTI if H not in C.FULL_N_H} == {65}
+    # every defect has its place in some case, the slot reuse at every S
+    for d in C.DEFECTS:
+        assert any(C.defect_reachable(d, *k) for k in MULTI), d
+    assert {S for N, H, S in MULTI if C.defect_reachable("stale_vector", N, H, S)} == {1, 2, 3}
+    assert C.one_hot_columns(288) == [0, 127, 128, 143, 144, 191, 192, 255, 256, 383, 384, 511, 512, 527, 528, 575]
+    assert [len(C.one_hot_columns(H)) for H in (256, 288, 768)] == [16, 16, 32]
+
+
+@pytest.mark.parametrize("N,H,S", MULTI)
+def test_rule_passes_the_chunked_walk_and_rejects_its_defects(N, H, S):
+    """The clean restatement meets max|x − oracle| <= 2·e_ref + 1e-6·max|oracle| on the values and
+    all five gradients; with a defect switched on, at every case where the walk has the defect's
+    place, the values or at least one gradient are over the bound."""
+    c, a, b = _case_refs(N, H)
+    args = [c[k] for k in ("h", "w1", "b1", "w2", "b2", "dv")]
+    assert C.over_the_bound(C.chunked_walk(*args, S), a, b) == []
+    for defect in C.DEFECTS:
+        if not C.defect_reachable(defect, N, H, S) or (defect, N, H, S) in NOT_REJECTED:
+            continue
+        bad = C.over_the_bound(C.chunked_walk(*args, S, defect=defect), a, b)
+        print(f"N={N} H={H} S={S} {defect}: over the bound on {bad}")
+        assert bad, f"{defect} passes the rule at N={N} H={H} S={S}"
+        if defect == "empty_half":   # the forward and dz do not see the column sums
+            assert set(bad) <= {"dw2", "db1"}, bad
