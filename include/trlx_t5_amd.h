@@ -421,6 +421,60 @@ typedef struct {
 } trlx_adamw_args;
 int trlx_adamw_step(const trlx_adamw_args* args, void* stream);
 
+/* ---------------------------------------------------------------- global-norm gradient clipping
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type=2.0) — what DeepSpeed's
+ * `gradient_clipping: 1.0` does before every update of the reference — as a device record that
+ * the AdamW step reads, so the clip costs one more read of the gradients and no host sync:
+ *   sumsq = Σ over all tensors Σ g²              every square and every sum in fp64, fixed order
+ *   norm  = float(sqrt(sumsq))
+ *   coef  = min(max_norm * (1 / (norm + 1e-6)), 1)    separately rounded fp32 ops (torch evaluates
+ *           `max_norm / tensor` as tensor.reciprocal() * max_norm); a NaN stays NaN;
+ *           max_norm = +inf records the norm only: coef = 1
+ *   g'    = g * coef                              fp32 product; for a bf16 g, coef is first rounded to
+ *           bf16 and the product rounded back to bf16: what torch's g.mul_(coef) with a 0-d device
+ *           tensor (and its _foreach_mul_) computes on the device
+ * trlx_grad_norm runs k_grad_sumsq (one workgroup per TRLX_ADAMW_CHUNK elements of one tensor,
+ * TRLX_ADAMW_MAX_TENSORS tensors per launch, fp32 and bf16 tensors mixed, 16-byte loads from the
+ * first 16-byte boundary at any element alignment and any length; one fp64 partial per workgroup
+ * in `workspace`), then k_grad_norm_finish (all partials in a fixed order -> `record`), then,
+ * as scale_in_place asks, k_grad_scale (g <- g' in place).  No atomics: for the same tensors at
+ * the same addresses the record is bit-reproducible.  Zero-length tensors are skipped; with no
+ * live tensor the record is that of an all-zero gradient.
+ * trlx_adamw_step_clipped is trlx_adamw_step with every gradient element replaced by g' as it is
+ * read (coef from `record`, on the device); g itself is not written.  Bit for bit it leaves what
+ * trlx_grad_norm(scale_in_place = 1) followed by trlx_adamw_step leaves in p, m, v, master and
+ * target.
+ * Refused before anything is launched: a NULL pointer in a live entry, a NULL record or
+ * workspace, a workspace smaller than trlx_grad_norm_workspace_bytes, a record not aligned to
+ * 8 bytes, a gradient not aligned to its element size, a NaN or negative max_norm, a record or
+ * workspace that overlaps a gradient or each other (trlx_adamw_step_clipped: a record that
+ * overlaps any tensor of the step) — all TRLX_ERR_ARG; a dtype other than TRLX_F32 / TRLX_BF16
+ * (TRLX_ERR_DTYPE); a negative numel or a tensor too large for the grid (TRLX_ERR_SHAPE). */
+typedef struct {
+    float norm;                       /* float(sqrt(sumsq)) */
+    float coef;                       /* the clip coefficient, <= 1 (or NaN) */
+    int32_t nonfinite;                /* 1 when norm is inf or NaN */
+    int32_t pad;
+    double sumsq;                     /* kept so that ranks can add theirs before the root */
+    int64_t reserved;                 /* written as 0 */
+} trlx_grad_norm_record;              /* 32 bytes */
+typedef struct {
+    int64_t count;
+    const void* const* g;
+    const int* g_dtype;               /* per tensor: TRLX_F32 / TRLX_BF16 */
+    const int64_t* numel;
+    double max_norm;                  /* >= 0, or +inf: record the norm only */
+    void* record;                     /* trlx_grad_norm_record on the device, 8-byte aligned */
+    void* workspace;
+    int64_t workspace_bytes;
+    int scale_in_place;               /* 0: record only; 1: record, then g <- g'; 2: g <- g' from a
+                                         record already written (nothing else is launched) */
+} trlx_grad_norm_args;
+/* 8 bytes per workgroup of k_grad_sumsq (at least 8); -1 for a NULL list or a negative numel */
+int64_t trlx_grad_norm_workspace_bytes(const int64_t* numel, int64_t count);
+int trlx_grad_norm(const trlx_grad_norm_args* args, void* stream);
+int trlx_adamw_step_clipped(const trlx_adamw_args* args, const void* record, void* stream);
+
 /* ---------------------------------------------------------------- fused bf16 value head
  * The PPO value head — replaces `make_head(n_embd, 1)` (ppo_models.py:216-222: Linear(H, 2H),
  * ReLU, Linear(2H, 1), all bf16) and its use at :618,:641:

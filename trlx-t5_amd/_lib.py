@@ -97,9 +97,25 @@ class AdamwArgs(ctypes.Structure):
     ]
 
 
+class GradNormRecord(ctypes.Structure):
+    """Mirror of trlx_grad_norm_record (include/trlx_t5_amd.h): 32 bytes on the device."""
+    _fields_ = [("norm", _c_f), ("coef", _c_f), ("nonfinite", ctypes.c_int32), ("pad", ctypes.c_int32),
+                ("sumsq", _c_d), ("reserved", _c_i64)]
+
+
+class GradNormArgs(ctypes.Structure):
+    """Mirror of trlx_grad_norm_args (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("count", _c_i64), ("g", ctypes.POINTER(_c_vp)), ("g_dtype", ctypes.POINTER(_c_int)),
+        ("numel", ctypes.POINTER(_c_i64)), ("max_norm", _c_d), ("record", _c_vp), ("workspace", _c_vp),
+        ("workspace_bytes", _c_i64), ("scale_in_place", _c_int),
+    ]
+
+
 _ilql_p = ctypes.POINTER(IlqlArgs)
 _ilql_tq_p = ctypes.POINTER(IlqlTqArgs)
 _adamw_p = ctypes.POINTER(AdamwArgs)
+_grad_norm_p = ctypes.POINTER(GradNormArgs)
 
 CTL_SLOTS = 16
 (CTL_MEAN, CTL_VAR, CTL_STD, CTL_COUNT, CTL_REF_MEAN, CTL_REF_STD, CTL_REF_SET, CTL_KL_COEF, CTL_BATCH_MEAN,
@@ -271,6 +287,9 @@ SIGNATURES = {
     "trlx_polyak_update": (_c_int, [ctypes.POINTER(_c_vp), ctypes.POINTER(_c_vp), ctypes.POINTER(_c_i64), _c_i64,
                                     _c_int, _c_d, _c_vp]),
     "trlx_adamw_step": (_c_int, [_adamw_p, _c_vp]),
+    "trlx_grad_norm_workspace_bytes": (_c_i64, [ctypes.POINTER(_c_i64), _c_i64]),
+    "trlx_grad_norm": (_c_int, [_grad_norm_p, _c_vp]),
+    "trlx_adamw_step_clipped": (_c_int, [_adamw_p, _c_vp, _c_vp]),
     "trlx_value_head_splits": (_c_int, [_c_i64, _c_i64]),
     "trlx_value_head_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
     "trlx_value_head_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),

@@ -7,7 +7,14 @@
 //             m and v fp32.  An entry with a target also writes k_polyak's
 //             target <- alpha·p_new + (1 - alpha)·target from the p just formed, so the sync never
 //             re-reads the parameters.  HBM-bound: 28 B per fp32 parameter (read p, g, m, v, write
-//             p, m, v), 36 B with the fold.
+//             p, m, v), 36 B with the fold.  The clipped instantiation (trlx_adamw_step_clipped)
+//             feeds g·coef, coef read from a device record, and leaves g as it is.
+//   k_grad_sumsq, k_grad_norm_finish, k_grad_scale
+//             torch's clip_grad_norm_ (C ABI: trlx_grad_norm): Σ g² over a by-value table of fp32 /
+//             bf16 gradients in fp64, one partial per workgroup; one small launch that adds the
+//             partials in a fixed order and writes {norm, coef, nonfinite, sumsq}; the in-place
+//             g <- g·coef of the stand-alone clip.  The fold costs one more read of g (+4 B per
+//             fp32 parameter) where the two-call route costs +12 B.
 //
 // One workgroup takes one chunk of TRLX_ADAMW_CHUNK elements of one tensor.  A tensor whose
 // pointers share a 16-B phase is processed as [head | groups of G elements | tail], G = 4 (all
@@ -112,11 +119,15 @@ template <>
 __device__ __forceinline__ float as_stored<BF16T>(float x) { return bf2f(f2bf(x)); }
 
 // One element through scalar accesses (the head, the tail and tensors of mixed phase).
-template <class PT, class GT>
-__device__ __forceinline__ void adamw_elem(const AdamwEntry& e, int64_t k, const AdamwScalars& s) {
+// CLIP: the gradient is g·coef as a store of dtype GT would leave it (k_grad_scale's value);
+// coef arrives already rounded to GT.
+template <class PT, class GT, bool CLIP>
+__device__ __forceinline__ void adamw_elem(const AdamwEntry& e, int64_t k, const AdamwScalars& s, float coef) {
     float p = e.master ? e.master[k] : PT::load1(e.p, k);
     float m = e.m[k], v = e.v[k];
-    adamw_one(p, GT::load1(e.g, k), m, v, s);
+    float g = GT::load1(e.g, k);
+    if (CLIP) g = as_stored<GT>(mul_rn(g, coef));
+    adamw_one(p, g, m, v, s);
     e.m[k] = m;
     e.v[k] = v;
     if (e.master) e.master[k] = p;
@@ -151,8 +162,8 @@ __device__ __forceinline__ void store_group(void* base, int64_t grp, const float
     }
 }
 
-template <class PT, class GT>
-__global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t) {
+template <class PT, class GT, bool CLIP = false>
+__global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t, const trlx_grad_norm_record* rec) {
     typedef typename PT::elem_t PE;
     typedef typename GT::elem_t GE;
     constexpr int G = (PT::kEPV == 8 || GT::kEPV == 8) ? 8 : 4;
@@ -162,11 +173,15 @@ __global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t) {
     const int64_t j = int(blockIdx.x) - t.blk0[i];
     const AdamwEntry e = t.e[i];
     const AdamwScalars s = t.s;
+    // torch multiplies a tensor by a 0-d device tensor in the tensor's dtype: a bf16 gradient
+    // meets the coefficient rounded to bf16 (fp32 product, rounded to bf16 once more)
+    const float coef = CLIP ? as_stored<GT>(rec->coef) : 1.f;
     const int tid = threadIdx.x;
     const AdamwSplit sp(e, int(sizeof(PE)), int(sizeof(GE)));
     if (!sp.vec) {
         const int64_t k1 = min(e.n, (j + 1) * int64_t(TRLX_ADAMW_CHUNK));
-        for (int64_t k = j * int64_t(TRLX_ADAMW_CHUNK) + tid; k < k1; k += kAdamwThreads) adamw_elem<PT, GT>(e, k, s);
+        for (int64_t k = j * int64_t(TRLX_ADAMW_CHUNK) + tid; k < k1; k += kAdamwThreads)
+            adamw_elem<PT, GT, CLIP>(e, k, s, coef);
         return;
     }
     // every array from its first 16-B boundary (element sp.head)
@@ -184,6 +199,10 @@ __global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t) {
         load_group<GT, G, true>(gb, q, g);
         load_group<F32T, G, false>(mb, q, m);
         load_group<F32T, G, false>(vb, q, v);
+        if (CLIP) {
+#pragma unroll
+            for (int k = 0; k < G; ++k) g[k] = as_stored<GT>(mul_rn(g[k], coef));
+        }
 #pragma unroll
         for (int k = 0; k < G; ++k) adamw_one(p[k], g[k], m[k], v[k], s);
         store_group<F32T, G>(mb, q, m);
@@ -202,24 +221,160 @@ __global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t) {
         int64_t k = -1;
         if (tid < sp.head) k = tid;
         else if (tid - sp.head < e.n - sp.tail0) k = sp.tail0 + (tid - sp.head);
-        if (k >= 0) adamw_elem<PT, GT>(e, k, s);
+        if (k >= 0) adamw_elem<PT, GT, CLIP>(e, k, s, coef);
     }
+}
+
+// ------------------------------------------------------------------ global gradient norm
+constexpr int kFinishThreads = 1024;
+
+struct GradEntry {
+    void* g;
+    int64_t n;
+    int dtype;  // TRLX_F32 / TRLX_BF16, per entry
+};
+struct GradTable {
+    GradEntry e[TRLX_ADAMW_MAX_TENSORS];
+    int blk0[TRLX_ADAMW_MAX_TENSORS + 1];  // first workgroup of each entry; [count] = the grid
+    int count;
+};
+
+// [head | nvec 16-B vectors | tail] of one gradient, head and tail shorter than a vector; a
+// workgroup takes TRLX_ADAMW_CHUNK elements' worth of vectors, workgroup 0 the head and tail too.
+struct GradSplit {
+    int64_t head, nvec, tail0, blocks;
+    __host__ __device__ GradSplit(const GradEntry& e) {
+        const int es = e.dtype == TRLX_BF16 ? 2 : 4, epv = 16 / es;
+        head = int64_t(((16u - unsigned(reinterpret_cast<uintptr_t>(e.g) & 15u)) & 15u) / unsigned(es));
+        if (head > e.n) head = e.n;
+        nvec = (e.n - head) / epv;
+        tail0 = head + nvec * epv;
+        blocks = (nvec + TRLX_ADAMW_CHUNK / epv - 1) / (TRLX_ADAMW_CHUNK / epv);
+        if (blocks < 1) blocks = 1;
+    }
+};
+
+__device__ __forceinline__ int grad_entry_of_block(const GradTable& t) {
+    int i = 0;
+    while (i + 1 < t.count && int(blockIdx.x) >= t.blk0[i + 1]) ++i;  // block-uniform
+    return i;
+}
+
+// This thread's share of Σ g² of chunk j: every element widened to fp64 before it is squared
+// (1e20² is finite there), four chains per thread joined in a fixed order.
+template <class GT>
+__device__ __forceinline__ double grad_sumsq_chunk(const GradEntry& e, int64_t j, int tid) {
+    typedef typename GT::elem_t GE;
+    constexpr int kVecs = TRLX_ADAMW_CHUNK / GT::kEPV;  // vectors per workgroup
+    const GradSplit sp(e);
+    const vec4u* body = reinterpret_cast<const vec4u*>(static_cast<const GE*>(e.g) + sp.head);
+    const int64_t v1 = min(sp.nvec, (j + 1) * kVecs);
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+    for (int64_t q = j * kVecs + tid; q < v1; q += kAdamwThreads) {
+        float f[GT::kEPV];
+        GT::unpack(ld_stream(body + q), f);
+#pragma unroll
+        for (int k = 0; k < GT::kEPV; ++k) {
+            const double d = double(f[k]);
+            acc[k & 3] += d * d;
+        }
+    }
+    if (j == 0) {  // the head and tail elements, fewer than a vector each
+        int64_t k = -1;
+        if (tid < sp.head) k = tid;
+        else if (tid - sp.head < e.n - sp.tail0) k = sp.tail0 + (tid - sp.head);
+        if (k >= 0) {
+            const double d = double(GT::load1(e.g, k));
+            acc[0] += d * d;
+        }
+    }
+    return (acc[0] + acc[1]) + (acc[2] + acc[3]);
+}
+
+__global__ __launch_bounds__(kAdamwThreads) void k_grad_sumsq(GradTable t, double* partials) {
+    __shared__ double sh[kAdamwThreads / kWave];
+    const int i = grad_entry_of_block(t);
+    const int64_t j = int(blockIdx.x) - t.blk0[i];
+    const GradEntry e = t.e[i];
+    const double mine = e.dtype == TRLX_BF16 ? grad_sumsq_chunk<BF16T>(e, j, threadIdx.x)
+                                             : grad_sumsq_chunk<F32T>(e, j, threadIdx.x);
+    const double s = block_sum_d(mine, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// All partials of all launches in one fixed order -> the record.  max_norm = +inf: the norm only.
+__global__ __launch_bounds__(kFinishThreads) void k_grad_norm_finish(const double* partials, int n, float max_norm,
+                                                                     trlx_grad_norm_record* rec) {
+    __shared__ double sh[kFinishThreads / kWave];
+    const double sumsq = reduce_records<1>(partials, n, sh);
+    if (threadIdx.x != 0) return;
+    const float norm = float(sqrt(sumsq));
+    float coef = 1.f;
+    if (max_norm != INFINITY) {
+        // torch: max_norm / (norm + 1e-6) is (norm + 1e-6).reciprocal() * max_norm, then clamp(max=1)
+        coef = mul_rn(__fdiv_rn(1.f, add_rn(norm, 1e-6f)), max_norm);
+        if (coef > 1.f) coef = 1.f;  // a NaN stays
+    }
+    rec->norm = norm;
+    rec->coef = coef;
+    rec->nonfinite = isfinite(norm) ? 0 : 1;
+    rec->pad = 0;
+    rec->sumsq = sumsq;
+    rec->reserved = 0;
+}
+
+// g <- g·coef in place, coef and the product each rounded to g's dtype: the stand-alone clip_grad_norm_.
+template <class GT>
+__device__ __forceinline__ void grad_scale_chunk(const GradEntry& e, int64_t j, int tid, float record_coef) {
+    typedef typename GT::elem_t GE;
+    const float coef = as_stored<GT>(record_coef);  // in g's dtype, as torch's g.mul_(coef) takes it
+    constexpr int kVecs = TRLX_ADAMW_CHUNK / GT::kEPV;
+    const GradSplit sp(e);
+    vec4u* body = reinterpret_cast<vec4u*>(static_cast<GE*>(e.g) + sp.head);
+    const int64_t v1 = min(sp.nvec, (j + 1) * kVecs);
+#pragma unroll 4
+    for (int64_t q = j * kVecs + tid; q < v1; q += kAdamwThreads) {
+        float f[GT::kEPV];
+        GT::unpack(body[q], f);
+#pragma unroll
+        for (int k = 0; k < GT::kEPV; ++k) f[k] = mul_rn(f[k], coef);
+        body[q] = GT::pack(f);
+    }
+    if (j == 0) {
+        int64_t k = -1;
+        if (tid < sp.head) k = tid;
+        else if (tid - sp.head < e.n - sp.tail0) k = sp.tail0 + (tid - sp.head);
+        if (k >= 0) GT::store1(e.g, k, mul_rn(GT::load1(e.g, k), coef));
+    }
+}
+
+__global__ __launch_bounds__(kAdamwThreads) void k_grad_scale(GradTable t, const trlx_grad_norm_record* rec) {
+    const int i = grad_entry_of_block(t);
+    const int64_t j = int(blockIdx.x) - t.blk0[i];
+    const GradEntry e = t.e[i];
+    const float coef = rec->coef;
+    if (e.dtype == TRLX_BF16) grad_scale_chunk<BF16T>(e, j, threadIdx.x, coef);
+    else grad_scale_chunk<F32T>(e, j, threadIdx.x, coef);
 }
 
 }  // namespace trlx
 
 using namespace trlx;
 
-static int adamw_launch(const AdamwTable& t, int p_dtype, int g_dtype, hipStream_t stream) {
+static int adamw_launch(const AdamwTable& t, int p_dtype, int g_dtype, const trlx_grad_norm_record* rec,
+                        hipStream_t stream) {
     const dim3 grid{unsigned(t.blk0[t.count])}, block(kAdamwThreads);
-    if (p_dtype == TRLX_BF16 && g_dtype == TRLX_BF16)
-        hipLaunchKernelGGL((k_adamw<BF16T, BF16T>), grid, block, 0, stream, t);
-    else if (p_dtype == TRLX_BF16)
-        hipLaunchKernelGGL((k_adamw<BF16T, F32T>), grid, block, 0, stream, t);
-    else if (g_dtype == TRLX_BF16)
-        hipLaunchKernelGGL((k_adamw<F32T, BF16T>), grid, block, 0, stream, t);
-    else
-        hipLaunchKernelGGL((k_adamw<F32T, F32T>), grid, block, 0, stream, t);
+#define TRLX_ADAMW_LAUNCH(PT, GT)                                                                \
+    do {                                                                                         \
+        if (rec) hipLaunchKernelGGL((k_adamw<PT, GT, true>), grid, block, 0, stream, t, rec);    \
+        else hipLaunchKernelGGL((k_adamw<PT, GT, false>), grid, block, 0, stream, t, rec);       \
+    } while (0)
+    if (p_dtype == TRLX_BF16 && g_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(BF16T, BF16T);
+    else if (p_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(BF16T, F32T);
+    else if (g_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(F32T, BF16T);
+    else TRLX_ADAMW_LAUNCH(F32T, F32T);
+#undef TRLX_ADAMW_LAUNCH
     return check_launch("k_adamw");
 }
 
@@ -235,7 +390,12 @@ static AdamwEntry adamw_entry(const trlx_adamw_args& a, int64_t i) {
     return e;
 }
 
-extern "C" int trlx_adamw_step(const trlx_adamw_args* args, void* stream) {
+static bool disjoint(uintptr_t a, uintptr_t a_bytes, uintptr_t b, uintptr_t b_bytes) {
+    return a + a_bytes <= b || b + b_bytes <= a;
+}
+
+// rec: NULL for the plain step, the clip record (already checked non-NULL and aligned) otherwise
+static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_record* rec, void* stream) {
     TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_adamw_args");
     const trlx_adamw_args& a = *args;
     TRLX_REQUIRE(a.p_dtype == TRLX_F32 || a.p_dtype == TRLX_BF16, TRLX_ERR_DTYPE, "adamw parameter dtype %d", a.p_dtype);
@@ -272,6 +432,10 @@ extern "C" int trlx_adamw_step(const trlx_adamw_args* args, void* stream) {
                 TRLX_REQUIRE(ptr[x] + bx <= ptr[y] || ptr[y] + by <= ptr[x], TRLX_ERR_ARG,
                              "adamw tensor %lld: %s and %s alias", (long long)i, kNames[x], kNames[y]);
             }
+        for (int x = 0; rec && x < 6; ++x)
+            TRLX_REQUIRE(!ptr[x] || disjoint(reinterpret_cast<uintptr_t>(rec), sizeof(*rec), ptr[x],
+                                             uintptr_t(e.n) * uintptr_t(es[x])),
+                         TRLX_ERR_ARG, "adamw tensor %lld: the clip record overlaps %s", (long long)i, kNames[x]);
     }
     // the scalars, formed in double as torch forms them, rounded to fp32 once
     const double bc1 = 1.0 - pow(a.beta1, double(a.step)), bc2 = 1.0 - pow(a.beta2, double(a.step));
@@ -292,7 +456,7 @@ extern "C" int trlx_adamw_step(const trlx_adamw_args* args, void* stream) {
         if (e.n == 0) continue;  // zero-length tensors are skipped
         const int64_t blocks = AdamwSplit(e, p_es, g_es).blocks;
         if (t.count == TRLX_ADAMW_MAX_TENSORS || t.blk0[t.count] + blocks > kAdamwMaxGrid) {
-            const int rc = adamw_launch(t, a.p_dtype, a.g_dtype, (hipStream_t)stream);
+            const int rc = adamw_launch(t, a.p_dtype, a.g_dtype, rec, (hipStream_t)stream);
             if (rc) return rc;
             t.count = 0;
         }
@@ -300,5 +464,135 @@ extern "C" int trlx_adamw_step(const trlx_adamw_args* args, void* stream) {
         t.blk0[t.count + 1] = int(t.blk0[t.count] + blocks);
         ++t.count;
     }
-    return t.count ? adamw_launch(t, a.p_dtype, a.g_dtype, (hipStream_t)stream) : TRLX_OK;
+    return t.count ? adamw_launch(t, a.p_dtype, a.g_dtype, rec, (hipStream_t)stream) : TRLX_OK;
+}
+
+extern "C" int trlx_adamw_step(const trlx_adamw_args* args, void* stream) {
+    return adamw_step_impl(args, nullptr, stream);
+}
+
+static int check_record(const void* record) {
+    TRLX_REQUIRE(record, TRLX_ERR_ARG, "NULL grad-norm record");
+    TRLX_REQUIRE((reinterpret_cast<uintptr_t>(record) & 7u) == 0, TRLX_ERR_ARG,
+                 "the grad-norm record is not aligned to 8 bytes");
+    return TRLX_OK;
+}
+
+extern "C" int trlx_adamw_step_clipped(const trlx_adamw_args* args, const void* record, void* stream) {
+    TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_adamw_args");
+    const int rc = check_record(record);
+    if (rc) return rc;
+    return adamw_step_impl(args, static_cast<const trlx_grad_norm_record*>(record), stream);
+}
+
+// workgroups of k_grad_sumsq for n elements, whatever the dtype and the alignment: at most
+// ceil(n / CHUNK) (a head only shortens the body), at least one
+static int64_t grad_blocks_bound(int64_t n) {
+    return n == 0 ? 0 : (n + TRLX_ADAMW_CHUNK - 1) / TRLX_ADAMW_CHUNK;
+}
+
+extern "C" int64_t trlx_grad_norm_workspace_bytes(const int64_t* numel, int64_t count) {
+    if (count < 0 || (count > 0 && !numel)) return -1;
+    int64_t blocks = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        if (numel[i] < 0) return -1;
+        blocks += grad_blocks_bound(numel[i]);
+    }
+    return 8 * (blocks < 1 ? 1 : blocks);
+}
+
+static GradEntry grad_entry(const trlx_grad_norm_args& a, int64_t i) {
+    GradEntry e;
+    e.g = const_cast<void*>(a.g[i]);
+    e.n = a.numel[i];
+    e.dtype = a.g_dtype[i];
+    return e;
+}
+
+// One launch per table of up to TRLX_ADAMW_MAX_TENSORS live tensors: the sumsq launches write
+// their partials one after the other (*n_partials counts them), the scale launches read `rec`.
+static int grad_launches(const trlx_grad_norm_args& a, bool scale, double* partials, int64_t* n_partials,
+                         const trlx_grad_norm_record* rec, hipStream_t stream) {
+    GradTable t;
+    t.count = 0;
+    t.blk0[0] = 0;
+    int64_t done = 0;
+    for (int64_t i = 0; i <= a.count; ++i) {
+        GradEntry e{};
+        int64_t blocks = 0;
+        if (i < a.count) {
+            e = grad_entry(a, i);
+            if (e.n == 0) continue;  // zero-length tensors are skipped
+            blocks = GradSplit(e).blocks;
+        }
+        if (t.count && (i == a.count || t.count == TRLX_ADAMW_MAX_TENSORS || t.blk0[t.count] + blocks > kAdamwMaxGrid)) {
+            const dim3 grid{unsigned(t.blk0[t.count])}, block(kAdamwThreads);
+            if (scale) hipLaunchKernelGGL(k_grad_scale, grid, block, 0, stream, t, rec);
+            else hipLaunchKernelGGL(k_grad_sumsq, grid, block, 0, stream, t, partials + done);
+            const int rc = check_launch(scale ? "k_grad_scale" : "k_grad_sumsq");
+            if (rc) return rc;
+            done += t.blk0[t.count];
+            t.count = 0;
+        }
+        if (i == a.count) break;
+        t.e[t.count] = e;
+        t.blk0[t.count + 1] = int(t.blk0[t.count] + blocks);
+        ++t.count;
+    }
+    if (n_partials) *n_partials = done;
+    return TRLX_OK;
+}
+
+extern "C" int trlx_grad_norm(const trlx_grad_norm_args* args, void* stream) {
+    TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_grad_norm_args");
+    const trlx_grad_norm_args& a = *args;
+    TRLX_REQUIRE(a.count >= 0 && (a.count == 0 || (a.g && a.g_dtype && a.numel)), TRLX_ERR_ARG,
+                 "bad grad-norm tensor list");
+    TRLX_REQUIRE(a.max_norm == a.max_norm && a.max_norm >= 0.0, TRLX_ERR_ARG,
+                 "grad-norm max_norm %g (must be >= 0, +inf records the norm only)", a.max_norm);
+    TRLX_REQUIRE(a.scale_in_place >= 0 && a.scale_in_place <= 2, TRLX_ERR_ARG, "grad-norm scale_in_place %d",
+                 a.scale_in_place);
+    const int rc = check_record(a.record);
+    if (rc) return rc;
+    TRLX_REQUIRE(a.workspace, TRLX_ERR_ARG, "NULL grad-norm workspace");
+    TRLX_REQUIRE((reinterpret_cast<uintptr_t>(a.workspace) & 7u) == 0, TRLX_ERR_ARG,
+                 "the grad-norm workspace is not aligned to 8 bytes");
+    const uintptr_t rec = reinterpret_cast<uintptr_t>(a.record), ws = reinterpret_cast<uintptr_t>(a.workspace);
+    int64_t bound = 0;
+    for (int64_t i = 0; i < a.count; ++i) {  // validate everything before the first launch
+        const GradEntry e = grad_entry(a, i);
+        TRLX_REQUIRE(e.n >= 0, TRLX_ERR_SHAPE, "grad-norm tensor %lld: numel %lld", (long long)i, (long long)e.n);
+        if (e.n == 0) continue;
+        TRLX_REQUIRE(e.dtype == TRLX_F32 || e.dtype == TRLX_BF16, TRLX_ERR_DTYPE, "grad-norm tensor %lld: dtype %d",
+                     (long long)i, e.dtype);
+        TRLX_REQUIRE(e.g, TRLX_ERR_ARG, "grad-norm tensor %lld: NULL pointer", (long long)i);
+        TRLX_REQUIRE(e.n <= int64_t(TRLX_ADAMW_CHUNK) * kAdamwMaxGrid, TRLX_ERR_SHAPE,
+                     "grad-norm tensor %lld too large (%lld elements)", (long long)i, (long long)e.n);
+        const int es = e.dtype == TRLX_BF16 ? 2 : 4;
+        const uintptr_t g = reinterpret_cast<uintptr_t>(e.g), bytes = uintptr_t(e.n) * uintptr_t(es);
+        TRLX_REQUIRE((g & uintptr_t(es - 1)) == 0, TRLX_ERR_ARG,
+                     "grad-norm tensor %lld: g not aligned to the element size", (long long)i);
+        bound += grad_blocks_bound(e.n);
+        TRLX_REQUIRE(bound < (int64_t(1) << 31), TRLX_ERR_SHAPE, "grad-norm: too many elements for one record");
+        TRLX_REQUIRE(disjoint(rec, sizeof(trlx_grad_norm_record), g, bytes), TRLX_ERR_ARG,
+                     "grad-norm tensor %lld: the record overlaps g", (long long)i);
+        TRLX_REQUIRE(a.workspace_bytes <= 0 || disjoint(ws, uintptr_t(a.workspace_bytes), g, bytes), TRLX_ERR_ARG,
+                     "grad-norm tensor %lld: the workspace overlaps g", (long long)i);
+    }
+    const int64_t need = 8 * (bound < 1 ? 1 : bound);
+    TRLX_REQUIRE(a.workspace_bytes >= need, TRLX_ERR_ARG, "grad-norm workspace of %lld bytes, %lld needed",
+                 (long long)a.workspace_bytes, (long long)need);
+    TRLX_REQUIRE(disjoint(rec, sizeof(trlx_grad_norm_record), ws, uintptr_t(a.workspace_bytes)), TRLX_ERR_ARG,
+                 "grad-norm: the record overlaps the workspace");
+    trlx_grad_norm_record* record = static_cast<trlx_grad_norm_record*>(a.record);
+    if (a.scale_in_place != 2) {
+        int64_t n_partials = 0;
+        int rc2 = grad_launches(a, false, static_cast<double*>(a.workspace), &n_partials, nullptr, (hipStream_t)stream);
+        if (rc2) return rc2;
+        hipLaunchKernelGGL(k_grad_norm_finish, dim3(1), dim3(kFinishThreads), 0, (hipStream_t)stream,
+                           static_cast<const double*>(a.workspace), int(n_partials), float(a.max_norm), record);
+        rc2 = check_launch("k_grad_norm_finish");
+        if (rc2) return rc2;
+    }
+    return a.scale_in_place ? grad_launches(a, true, nullptr, nullptr, record, (hipStream_t)stream) : TRLX_OK;
 }

@@ -23,6 +23,8 @@ from . import _lib
 
 __all__ = ["ILQLHeads", "ilql_target_q_at_actions", "make_head", "polyak_update"]
 
+UNSET = object()  # "the optimizer's own value" for a keyword whose None means something else
+
 
 def make_head(n_embd: int, out: int):
     """ilql_models.py:31-34."""
@@ -189,12 +191,15 @@ class ILQLHeads(nn.Module):
         sources = [p.data for h in self.q_heads for p in h.parameters()]
         polyak_update(targets, sources, self.config.alpha)
 
-    def step_and_sync(self, opt, closure=None):
+    def step_and_sync(self, opt, closure=None, *, max_grad_norm=UNSET):
         """opt.step() and sync_target_q_heads() in one pass (opt: a FusedAdamW over these heads'
         parameters): every Q parameter the optimizer steps updates its target from the value
         just formed, bit for bit what the two calls leave; a Q parameter without a gradient is
         synced by polyak_update.  For the updates on which post_backward_callback syncs
-        (every steps_for_target_q_sync); the others call opt.step()."""
+        (every steps_for_target_q_sync); the others call opt.step().  max_grad_norm= is passed
+        on to FusedAdamW.step (the global-norm clip folded into the same update; left out, the
+        optimizer's own max_grad_norm holds)."""
+        step_kw = {} if max_grad_norm is UNSET else {"max_grad_norm": max_grad_norm}
         targets = [p.data for h in self.target_q_heads for p in h.parameters()]
         sources = [p.data for h in self.q_heads for p in h.parameters()]
-        return opt.step(closure, polyak=(targets, sources, self.config.alpha))
+        return opt.step(closure, polyak=(targets, sources, self.config.alpha), **step_kw)

@@ -9,6 +9,13 @@ reference ends with (accelerate_base_model.py:94-106, 263-265):
   step(polyak=)   the ILQL target-head sync (post_backward_callback, ilql_models.py:161-181)
                   folded into the same pass: the target is updated from the parameter values
                   still in registers (ILQLHeads.step_and_sync).
+  clip_grad_norm_ torch.nn.utils.clip_grad_norm_ (norm_type 2) — DeepSpeed's `gradient_clipping:
+                  1.0` of the reference's launch config — as a device record {norm, coef,
+                  nonfinite, sumsq}: Σ g² in fp64 over all tensors, no host sync.
+  step(max_grad_norm=)
+                  that clip folded into the update: the step reads the coefficient from the
+                  record on the device and scales every gradient element as it loads it, so the
+                  clip costs one more read of the gradients and .grad is never rewritten.
 
 Every element goes through torch's _single_tensor_adam ops in fp32, each rounded separately
 (trlx_adamw_step in include/trlx_t5_amd.h).  exp_avg and exp_avg_sq are always fp32.
@@ -20,9 +27,9 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from .ilql_heads import check_polyak_pairs, polyak_update
+from .ilql_heads import UNSET as _UNSET, check_polyak_pairs, polyak_update
 
-__all__ = ["FusedAdamW", "adamw_step"]
+__all__ = ["FusedAdamW", "adamw_step", "clip_grad_norm_"]
 
 _DTYPES = (torch.float32, torch.bfloat16)
 
@@ -78,9 +85,101 @@ def _fold(params, polyak):
     return aligned, float(alpha), rest_t, rest_s
 
 
-def _launch(entries, step, lr, beta1, beta2, eps, weight_decay, alpha):
+RECORD_FLOATS = ctypes.sizeof(_lib.GradNormRecord) // 4  # the record as a float32 tensor
+
+
+def _check_max_norm(max_norm, name="max_norm"):
+    max_norm = float(max_norm)
+    if max_norm != max_norm or max_norm < 0.0:
+        raise ValueError(f"{name} must be >= 0 (inf: the norm is recorded, nothing is clipped), got {max_norm}")
+    return max_norm
+
+
+def _check_grads(grads):
+    for i, g in enumerate(grads):
+        if g.layout != torch.strided:
+            raise ValueError(f"gradient {i}: sparse gradients are not supported")
+        if g.dtype not in _DTYPES:
+            raise ValueError(f"gradient {i}: unsupported gradient dtype {g.dtype} (float32 / bfloat16)")
+        if not g.is_contiguous():
+            raise ValueError(f"gradient {i}: must be contiguous")
+    _lib.require_cuda(*grads)
+    if len({g.device for g in grads}) > 1:
+        raise ValueError("the global norm is taken on one device: the gradients live on several")
+
+
+def _check_record(record, dev):
+    if not (isinstance(record, torch.Tensor) and record.dtype == torch.float32 and record.numel() == RECORD_FLOATS
+            and record.is_contiguous() and record.device == dev):
+        raise ValueError(f"grad_norm_record must be a contiguous float32 tensor of {RECORD_FLOATS} elements on {dev}")
+    return record
+
+
+def _workspace_bytes(grads):
+    numel = (ctypes.c_int64 * len(grads))(*[g.numel() for g in grads])
+    return int(_lib.query("trlx_grad_norm_workspace_bytes", numel, len(grads)))
+
+
+def _grad_norm(grads, max_norm, record, workspace, scale_in_place):
+    """trlx_grad_norm over validated gradients of one device, on that device's current stream."""
+    n = len(grads)
+    a = _lib.GradNormArgs()
+    a.count = n
+    a.g = (ctypes.c_void_p * n)(*[_lib.ptr(g) for g in grads])
+    a.g_dtype = (ctypes.c_int * n)(*[_lib.dtype_code(g) for g in grads])
+    a.numel = (ctypes.c_int64 * n)(*[g.numel() for g in grads])
+    a.max_norm = max_norm
+    a.record, a.workspace = record.data_ptr(), workspace.data_ptr()
+    a.workspace_bytes = workspace.numel() * workspace.element_size()
+    a.scale_in_place = scale_in_place
+    with torch.cuda.device(grads[0].device):
+        _lib.call("trlx_grad_norm", ctypes.byref(a), _lib.stream_of(grads[0]))
+
+
+def _nonfinite_error():
+    # torch.nn.utils.clip_grad_norm_'s message
+    return RuntimeError("The total norm of order 2.0 for gradients from `parameters` is non-finite, so it cannot be "
+                        "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                        "`error_if_nonfinite=False`")
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ for the L2 norm: total_norm = sqrt(Σ over all gradients Σ g²),
+    every gradient scaled in place by min(max_norm / (total_norm + 1e-6), 1) — fp32 ops rounded as
+    torch rounds them on the device (a bf16 gradient: coefficient and product each rounded to bf16) — and total_norm returned as a 0-d
+    fp32 tensor on the device.  Unlike torch, Σ g² is accumulated in fp64 in a fixed order (the
+    norm is the fp64 one rounded once, finite wherever the true norm fits fp32), fp32 and bf16
+    gradients go through the same launches, and nothing syncs with the host unless
+    error_if_nonfinite=True, which reads the record's flag and raises torch's RuntimeError before
+    any gradient is touched.  max_norm: >= 0; inf records the norm and leaves the gradients
+    (ValueError otherwise).  norm_type other than 2 raises ValueError; `foreach` is accepted
+    for the signature and ignored.  Gradients: contiguous, fp32 / bf16, on one ROCm device."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    max_norm = _check_max_norm(max_norm)
+    if float(norm_type) != 2.0:
+        raise ValueError(f"clip_grad_norm_ takes the L2 norm only (norm_type=2.0), got {norm_type}")
+    if len(grads) == 0:
+        return torch.tensor(0.0)
+    _check_grads(grads)
+    dev = grads[0].device
+    record = torch.zeros(RECORD_FLOATS, dtype=torch.float32, device=dev)
+    workspace = torch.empty(_workspace_bytes(grads) // 8, dtype=torch.float64, device=dev)
+    if error_if_nonfinite:
+        _grad_norm(grads, max_norm, record, workspace, 0)
+        if int(record.view(torch.int32)[2].item()):  # the one host sync
+            raise _nonfinite_error()
+        _grad_norm(grads, max_norm, record, workspace, 2)
+    else:
+        _grad_norm(grads, max_norm, record, workspace, 1)
+    return record[0]
+
+
+def _launch(entries, step, lr, beta1, beta2, eps, weight_decay, alpha, record=None):
     """entries: (p, g, m, v, master or None, target or None), validated.  One trlx_adamw_step per
-    (parameter dtype, gradient dtype, device)."""
+    (parameter dtype, gradient dtype, device); with a clip record trlx_adamw_step_clipped."""
     groups = {}
     for e in entries:
         groups.setdefault((e[0].dtype, e[1].dtype, e[0].device), []).append(e)
@@ -98,7 +197,10 @@ def _launch(entries, step, lr, beta1, beta2, eps, weight_decay, alpha):
         a.step, a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = int(step), lr, beta1, beta2, eps, weight_decay
         a.alpha = alpha
         with torch.cuda.device(dev):
-            _lib.call("trlx_adamw_step", ctypes.byref(a), _lib.stream_of(es[0][0]))
+            if record is None:
+                _lib.call("trlx_adamw_step", ctypes.byref(a), _lib.stream_of(es[0][0]))
+            else:
+                _lib.call("trlx_adamw_step_clipped", ctypes.byref(a), record.data_ptr(), _lib.stream_of(es[0][0]))
 
 
 def _check_hyper(lr, betas, eps, weight_decay):
@@ -118,7 +220,8 @@ def _check_hyper(lr, betas, eps, weight_decay):
 
 def adamw_step(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], exp_avgs: Sequence[torch.Tensor],
                exp_avg_sqs: Sequence[torch.Tensor], *, step: int, lr: float, betas, eps: float, weight_decay: float,
-               masters: Optional[Sequence[Optional[torch.Tensor]]] = None, polyak=None):
+               masters: Optional[Sequence[Optional[torch.Tensor]]] = None, polyak=None,
+               max_grad_norm: Optional[float] = None, grad_norm_record: Optional[torch.Tensor] = None):
     """One AdamW update (decoupled decay) of every tensor, in place, `step` >= 1 being the number
     of this update (torch's state["step"] after its increment).  params: fp32 / bf16; grads:
     fp32 / bf16; exp_avgs, exp_avg_sqs: fp32; masters: None, or per tensor None or the fp32
@@ -126,7 +229,11 @@ def adamw_step(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], ex
     bf16).  polyak=(targets, sources, alpha): after the update, target <- alpha·source +
     (1 - alpha)·target as polyak_update writes it; a source that is one of `params` is synced
     inside the same launch.  Tensors are grouped by dtype combination and device: one launch per
-    group and _lib.ADAMW_MAX_TENSORS tensors.  All tensors contiguous, on a ROCm device."""
+    group and _lib.ADAMW_MAX_TENSORS tensors.  max_grad_norm: the update takes every gradient
+    clipped by the global L2 norm of `grads` (clip_grad_norm_'s values, bit for bit) without
+    writing the gradients; grad_norm_record, a float32 tensor of 8 elements on the device,
+    receives {norm, coef, nonfinite (int32), -, sumsq (float64)} (None: a temporary).
+    All tensors contiguous, on a ROCm device."""
     params, grads, exp_avgs, exp_avg_sqs = list(params), list(grads), list(exp_avgs), list(exp_avg_sqs)
     masters = [None] * len(params) if masters is None else list(masters)
     if not (len(params) == len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(masters)):
@@ -135,13 +242,27 @@ def adamw_step(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], ex
     if int(step) != step or step < 1:
         raise ValueError(f"step must be an integer >= 1 (the number of this update), got {step}")
     lr, b1, b2, eps, wd = _check_hyper(lr, betas, eps, weight_decay)
+    if max_grad_norm is not None:
+        max_grad_norm = _check_max_norm(max_grad_norm, "max_grad_norm")
+    elif grad_norm_record is not None:
+        raise ValueError("grad_norm_record is written by the clip: give max_grad_norm too")
     for i, e in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs, masters)):
         _check_entry(i, *e)
     if polyak is not None:
         check_polyak_pairs(list(polyak[0]), list(polyak[1]))
     _lib.require_cuda(*params, *grads, *exp_avgs, *exp_avg_sqs, *masters)
+    record = None
+    if max_grad_norm is not None and grads:
+        _check_grads(grads)
+        dev = grads[0].device
+        record = (torch.zeros(RECORD_FLOATS, dtype=torch.float32, device=dev) if grad_norm_record is None
+                  else _check_record(grad_norm_record, dev))
     targets, alpha, rest_t, rest_s = _fold(params, polyak)
-    _launch(list(zip(params, grads, exp_avgs, exp_avg_sqs, masters, targets)), step, lr, b1, b2, eps, wd, alpha)
+    if record is not None:
+        workspace = torch.empty(_workspace_bytes(grads) // 8, dtype=torch.float64, device=record.device)
+        _grad_norm(grads, max_grad_norm, record, workspace, 0)
+    _launch(list(zip(params, grads, exp_avgs, exp_avg_sqs, masters, targets)), step, lr, b1, b2, eps, wd, alpha,
+            record)
     if rest_t:
         polyak_update(rest_t, rest_s, alpha)
 
@@ -154,10 +275,23 @@ class FusedAdamW(torch.optim.Optimizer):
     master_weights=True keeps an fp32 `master` state per bf16 parameter (absent for fp32
     parameters): the master takes the update, the parameter is the master rounded to bf16.
     A parameter whose .grad is None is skipped and its step does not advance.  amsgrad,
-    maximize, sparse gradients and complex parameters raise ValueError."""
+    maximize, sparse gradients and complex parameters raise ValueError.
+    max_grad_norm (keyword only; None: no clipping) is the default of step(max_grad_norm=): the
+    global L2 norm over every parameter that has a gradient, all param groups together, clips
+    the update as clip_grad_norm_ followed by step() would — bit for bit in the parameters and
+    the state — with one difference: .grad is left UNCLIPPED (the kernel scales each element as
+    it reads it), so code that inspects .grad after the step sees the raw gradients.  It is an
+    attribute of the optimizer, not a key of defaults / param_groups: the state_dict stays
+    torch.optim.AdamW's.  After a clipped step, grad_norm and clip_coef are 0-d fp32 device
+    views of the record (None before); reading them is the caller's only host sync."""
+
+    max_grad_norm = None
+    grad_norm = None
+    clip_coef = None
+    _clip_buffers = None  # (record, workspace), allocated by the first clipped step
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *,
-                 maximize=False, master_weights=False):
+                 maximize=False, master_weights=False, max_grad_norm=None):
         if isinstance(lr, torch.Tensor):
             lr = float(lr)
         _check_hyper(lr, betas, eps, weight_decay)
@@ -170,6 +304,8 @@ class FusedAdamW(torch.optim.Optimizer):
                         foreach=None, capturable=False, differentiable=False, fused=None,
                         decoupled_weight_decay=True)
         self.master_weights = bool(master_weights)
+        if max_grad_norm is not None:
+            self.max_grad_norm = _check_max_norm(max_grad_norm, "max_grad_norm")
         super().__init__(params, defaults)
         for group in self.param_groups:
             for p in group["params"]:
@@ -203,13 +339,29 @@ class FusedAdamW(torch.optim.Optimizer):
             state["master"] = p.detach().to(torch.float32, memory_format=torch.contiguous_format, copy=True)
         return state
 
+    def _clip_record(self, grads):
+        """The cached record and workspace, (re)allocated only when the gradients need more."""
+        dev, need = grads[0].device, _workspace_bytes(grads)
+        buf = self._clip_buffers
+        if buf is None or buf[0].device != dev or buf[1].numel() * 8 < need:
+            record = torch.zeros(RECORD_FLOATS, dtype=torch.float32, device=dev)
+            buf = self._clip_buffers = (record, torch.empty(need // 8, dtype=torch.float64, device=dev))
+            self.grad_norm, self.clip_coef = record[0], record[1]
+        return buf
+
     @torch.no_grad()
-    def step(self, closure=None, *, polyak=None):
+    def step(self, closure=None, *, polyak=None, max_grad_norm=_UNSET):
         """One update of every parameter that has a gradient.  polyak=(targets, sources, alpha):
         the Polyak sync target <- alpha·source + (1 - alpha)·target after the update, bit for
         bit what step() followed by polyak_update(targets, sources, alpha) leaves; every source
         that is stepped in this call is synced inside the optimizer's launch, any other one by
-        polyak_update."""
+        polyak_update.  max_grad_norm (default: the constructor's; None: no clipping): one
+        global norm over all gradients of this call, then the clipped launches — no host sync,
+        no allocation after the first clipped step, .grad left unclipped (see the class)."""
+        if max_grad_norm is _UNSET:
+            max_grad_norm = self.max_grad_norm
+        if max_grad_norm is not None:
+            max_grad_norm = _check_max_norm(max_grad_norm, "max_grad_norm")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -231,6 +383,12 @@ class FusedAdamW(torch.optim.Optimizer):
                 _check_entry(len(work), p, p.grad, state["exp_avg"], state["exp_avg_sq"], state.get("master"))
                 work.append((group, p, state))
         targets, alpha, rest_t, rest_s = _fold([p for _, p, _ in work], polyak)
+        record = None
+        if max_grad_norm is not None and work:
+            grads = [p.grad for _, p, _ in work]
+            _check_grads(grads)
+            record, workspace = self._clip_record(grads)
+            _grad_norm(grads, max_grad_norm, record, workspace, 0)
         buckets = {}  # one launch set per (group, step number): the scalars are per launch
         for (group, p, state), target in zip(work, targets):
             state["step"] += 1
@@ -239,7 +397,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 (p, p.grad, state["exp_avg"], state["exp_avg_sq"], state.get("master"), target))
         for (_, step), (group, entries) in buckets.items():
             lr, b1, b2, eps, wd = _check_hyper(group["lr"], group["betas"], group["eps"], group["weight_decay"])
-            _launch(entries, step, lr, b1, b2, eps, wd, alpha)
+            _launch(entries, step, lr, b1, b2, eps, wd, alpha, record)
         if rest_t:
             polyak_update(rest_t, rest_s, alpha)
         return loss
