@@ -418,6 +418,8 @@ typedef struct {
     int64_t step;
     double lr, beta1, beta2, eps, weight_decay;
     double alpha;                     /* read only where a target is given */
+    const void* lr_table;             /* read by the _dev entries only (below): the device fp64 table that */
+    int64_t n_lr;                     /* trlx_adamw_advance reads for this record, or NULL / 0: not given */
 } trlx_adamw_args;
 int trlx_adamw_step(const trlx_adamw_args* args, void* stream);
 
@@ -474,6 +476,66 @@ typedef struct {
 int64_t trlx_grad_norm_workspace_bytes(const int64_t* numel, int64_t count);
 int trlx_grad_norm(const trlx_grad_norm_args* args, void* stream);
 int trlx_adamw_step_clipped(const trlx_adamw_args* args, const void* record, void* stream);
+
+/* ---------------------------------------------------------------- device-resident AdamW schedule
+ * The step counter, the learning rate and the per-update scalars of the AdamW step in one small
+ * device record, so that an update can be captured in a graph and replayed: nothing the update
+ * depends on is baked into a launch.  Per update: trlx_adamw_advance (k_adamw_advance, one wave),
+ * then the _dev step entries, which read the record where trlx_adamw_step reads its arguments.
+ * trlx_adamw_advance, in this order:
+ *   1. skip_nonfinite != 0, grad_record given and its `nonfinite` set: apply = 0, sync = 0,
+ *      skipped += 1; step, lr and the scalars stay as they are; done.
+ *   2. step += 1, apply = 1, lr = lr_table[min(step, n_lr) - 1] (entry k-1 is the rate of update
+ *      k, the last entry holds afterwards).
+ *   3. the nine scalars from step and lr as trlx_adamw_step forms them — in fp64, each rounded to
+ *      fp32 once — with one difference: b^step is a square-and-multiply product chain over the
+ *      bits of step (r = 1; for each bit from the lowest: if set r = r*x; x = x*x), every product
+ *      a separately rounded fp64 multiplication, where trlx_adamw_step calls pow().  A CPU can
+ *      restate a product chain bit for bit, not another library's pow; 1 - b^step, the division
+ *      and the square root are IEEE-exact on both sides.  trlx_adamw_sched_scalars_host is the
+ *      same function on the host (no device, no stream): out[9] = {decay, w1, b2, w2, neg_step,
+ *      sqrt_bc2, eps, alpha, beta}.
+ *   4. sync = (sync_every > 0 && step % sync_every == 0).
+ * trlx_adamw_step_dev / trlx_adamw_step_clipped_dev are trlx_adamw_step / trlx_adamw_step_clipped
+ * with the scalars read from `sched` on the device: step, lr, beta1, beta2, eps, weight_decay
+ * and alpha of `args` are IGNORED (and not validated).  lr_table / n_lr of `args` name the table
+ * the record's advance reads, so that the step can refuse a table its tensors would overwrite;
+ * trlx_adamw_step and trlx_adamw_step_clipped never read the two fields.  With apply == 0 every workgroup returns
+ * before its first load: nothing of p, m, v, master, target is read or written.  With sync == 0
+ * the update is applied and `target` is neither read nor written.  For the same scalars the
+ * result bits are those of trlx_adamw_step / trlx_adamw_step_clipped.
+ * Refused before anything is launched (TRLX_ERR_ARG): a NULL sched or lr_table, a sched, lr_table
+ * or grad_record not aligned to 8 bytes, n_lr < 1, sync_every < 0, a NaN hyper-parameter, any
+ * overlap among sched, lr_table and grad_record (advance), a sched or an lr_table that overlaps
+ * any tensor of the step, the clip record or each other, an lr_table not aligned to 8 bytes or
+ * given with n_lr < 1 (_dev entries). */
+typedef struct {
+    int64_t step;                     /* updates applied so far */
+    int64_t skipped;                  /* updates skipped because of a non-finite norm */
+    int32_t apply;                    /* 1: the current update is applied */
+    int32_t sync;                     /* 1: the current update syncs the targets */
+    float decay, w1, b2, w2, neg_step, sqrt_bc2, eps;  /* 1 - lr*wd, 1-b1, b2, 1-b2, -(lr/bc1), sqrt(bc2), eps */
+    float alpha, beta;                /* alpha and 1 - alpha of the folded sync */
+    float pad;
+    double lr;                        /* the rate of the current update, for inspection */
+    int64_t reserved[3];
+} trlx_adamw_sched;                   /* 96 bytes, 8-byte aligned */
+typedef struct {
+    void* sched;                      /* trlx_adamw_sched on the device, in/out */
+    double beta1, beta2, eps, weight_decay;
+    double alpha;                     /* of the folded sync */
+    const void* lr_table;             /* device fp64 [n_lr] */
+    int64_t n_lr;                     /* >= 1 */
+    int64_t sync_every;               /* >= 0; 0: never */
+    const void* grad_record;          /* NULL, or the trlx_grad_norm_record of this update */
+    int skip_nonfinite;
+} trlx_adamw_advance_args;
+int trlx_adamw_advance(const trlx_adamw_advance_args* args, void* stream);
+int trlx_adamw_sched_scalars_host(int64_t step, double lr, double beta1, double beta2, double eps,
+                                  double weight_decay, double alpha, float* out);
+int trlx_adamw_step_dev(const trlx_adamw_args* args, const void* sched, void* stream);
+int trlx_adamw_step_clipped_dev(const trlx_adamw_args* args, const void* grad_record, const void* sched,
+                                void* stream);
 
 /* ---------------------------------------------------------------- fused bf16 value head
  * The PPO value head — replaces `make_head(n_embd, 1)` (ppo_models.py:216-222: Linear(H, 2H),

@@ -16,6 +16,8 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
   FusedAdamW (.step(polyak=, max_grad_norm=)), adamw_step — opt.step() of torch.optim.AdamW as
       one launch per dtype group, fp32 masters for bf16 parameters, the ILQL target sync folded
       into the same pass (ILQLHeads.step_and_sync)   trlx/model/accelerate_base_model.py:94-106,263-265
+      FusedAdamW(capturable=True, lr_schedule=, skip_nonfinite=, sync_every=), schedule_table —
+      step counter, learning rate, non-finite skip and sync cadence on the device (graph capture)
   clip_grad_norm_ — the global-L2-norm clip (DeepSpeed `gradient_clipping: 1.0`), stand-alone
       or folded into the step through a device record     configs/deepspeed_configs/default_configs.yml
   ppo_sample_step — one rollout token of generate(**gen_kwargs): min length, temperature,
@@ -53,7 +55,7 @@ from .lm_head import lm_head_logprobs
 from .rollout_store import PPORLBatch, PPORLElement, PPORolloutRecorder, PPORolloutStorage
 from .ilql import ILQL_LOSS_KEYS, ILQLBatch, ILQLConfig, ILQLHotPath, ilql_sample_step
 from .ilql_heads import ILQLHeads, ilql_target_q_at_actions, make_head, polyak_update
-from .optim import FusedAdamW, adamw_step, clip_grad_norm_
+from .optim import FusedAdamW, adamw_step, clip_grad_norm_, schedule_table
 from .ilql_store import ILQLElement, ILQLRolloutStorage
 from .value_head import ValueHead, value_head, value_head_splits
 from .value_head import make_head as make_value_head
@@ -74,7 +76,7 @@ __all__ = [
     "PPORLElement", "PPORLBatch", "lm_head_logprobs", "PPOControlState",
     "RcclComm", "shift_tokens_right", "get_model_inputs",
     "ValueHead", "value_head", "value_head_splits", "make_value_head",
-    "FusedAdamW", "adamw_step", "clip_grad_norm_",
+    "FusedAdamW", "adamw_step", "clip_grad_norm_", "schedule_table",
 ]
 
 

@@ -93,7 +93,7 @@ class AdamwArgs(ctypes.Structure):
         ("v", ctypes.POINTER(_c_vp)), ("master", ctypes.POINTER(_c_vp)), ("target", ctypes.POINTER(_c_vp)),
         ("numel", ctypes.POINTER(_c_i64)),
         ("step", _c_i64), ("lr", _c_d), ("beta1", _c_d), ("beta2", _c_d), ("eps", _c_d), ("weight_decay", _c_d),
-        ("alpha", _c_d),
+        ("alpha", _c_d), ("lr_table", _c_vp), ("n_lr", _c_i64),
     ]
 
 
@@ -110,6 +110,20 @@ class GradNormArgs(ctypes.Structure):
         ("numel", ctypes.POINTER(_c_i64)), ("max_norm", _c_d), ("record", _c_vp), ("workspace", _c_vp),
         ("workspace_bytes", _c_i64), ("scale_in_place", _c_int),
     ]
+
+
+class AdamwSched(ctypes.Structure):
+    """Mirror of trlx_adamw_sched (include/trlx_t5_amd.h): 96 bytes on the device."""
+    _fields_ = [("step", _c_i64), ("skipped", _c_i64), ("apply", ctypes.c_int32), ("sync", ctypes.c_int32),
+                ("decay", _c_f), ("w1", _c_f), ("b2", _c_f), ("w2", _c_f), ("neg_step", _c_f), ("sqrt_bc2", _c_f),
+                ("eps", _c_f), ("alpha", _c_f), ("beta", _c_f), ("pad", _c_f), ("lr", _c_d), ("reserved", _c_i64 * 3)]
+
+
+class AdamwAdvanceArgs(ctypes.Structure):
+    """Mirror of trlx_adamw_advance_args (include/trlx_t5_amd.h)."""
+    _fields_ = [("sched", _c_vp), ("beta1", _c_d), ("beta2", _c_d), ("eps", _c_d), ("weight_decay", _c_d),
+                ("alpha", _c_d), ("lr_table", _c_vp), ("n_lr", _c_i64), ("sync_every", _c_i64),
+                ("grad_record", _c_vp), ("skip_nonfinite", _c_int)]
 
 
 _ilql_p = ctypes.POINTER(IlqlArgs)
@@ -290,6 +304,11 @@ SIGNATURES = {
     "trlx_grad_norm_workspace_bytes": (_c_i64, [ctypes.POINTER(_c_i64), _c_i64]),
     "trlx_grad_norm": (_c_int, [_grad_norm_p, _c_vp]),
     "trlx_adamw_step_clipped": (_c_int, [_adamw_p, _c_vp, _c_vp]),
+    "trlx_adamw_advance": (_c_int, [ctypes.POINTER(AdamwAdvanceArgs), _c_vp]),
+    "trlx_adamw_sched_scalars_host": (_c_int, [_c_i64, _c_d, _c_d, _c_d, _c_d, _c_d, _c_d,
+                                               ctypes.POINTER(_c_f)]),
+    "trlx_adamw_step_dev": (_c_int, [_adamw_p, _c_vp, _c_vp]),
+    "trlx_adamw_step_clipped_dev": (_c_int, [_adamw_p, _c_vp, _c_vp, _c_vp]),
     "trlx_value_head_splits": (_c_int, [_c_i64, _c_i64]),
     "trlx_value_head_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
     "trlx_value_head_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),

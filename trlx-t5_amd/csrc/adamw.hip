@@ -162,22 +162,31 @@ __device__ __forceinline__ void store_group(void* base, int64_t grp, const float
     }
 }
 
-template <class PT, class GT, bool CLIP = false>
-__global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t, const trlx_grad_norm_record* rec) {
+// DEV: the scalars come from the device schedule record (trlx_adamw_advance wrote it) instead
+// of the by-value table: uniform loads from a kernel-argument pointer, so they sit in SGPRs as
+// t.s does.  apply == 0: the workgroup leaves before its first load of a tensor; sync == 0: the
+// entry is taken without its target (the split stays the host's, which counted the target).
+template <class PT, class GT, bool CLIP = false, bool DEV = false>
+__global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t, const trlx_grad_norm_record* rec,
+                                                         const trlx_adamw_sched* __restrict__ sched) {
     typedef typename PT::elem_t PE;
     typedef typename GT::elem_t GE;
     constexpr int G = (PT::kEPV == 8 || GT::kEPV == 8) ? 8 : 4;
     constexpr int kGroups = TRLX_ADAMW_CHUNK / G;  // groups per workgroup
+    if (DEV && sched->apply == 0) return;  // a skipped update: block-uniform
     int i = 0;
     while (i + 1 < t.count && int(blockIdx.x) >= t.blk0[i + 1]) ++i;  // block-uniform
     const int64_t j = int(blockIdx.x) - t.blk0[i];
-    const AdamwEntry e = t.e[i];
-    const AdamwScalars s = t.s;
+    AdamwEntry e = t.e[i];
+    const AdamwSplit sp(e, int(sizeof(PE)), int(sizeof(GE)));
+    if (DEV && sched->sync == 0) e.target = nullptr;
+    const AdamwScalars s = DEV ? AdamwScalars{sched->decay, sched->w1, sched->b2, sched->w2, sched->neg_step,
+                                              sched->sqrt_bc2, sched->eps, sched->alpha, sched->beta}
+                               : t.s;
     // torch multiplies a tensor by a 0-d device tensor in the tensor's dtype: a bf16 gradient
     // meets the coefficient rounded to bf16 (fp32 product, rounded to bf16 once more)
     const float coef = CLIP ? as_stored<GT>(rec->coef) : 1.f;
     const int tid = threadIdx.x;
-    const AdamwSplit sp(e, int(sizeof(PE)), int(sizeof(GE)));
     if (!sp.vec) {
         const int64_t k1 = min(e.n, (j + 1) * int64_t(TRLX_ADAMW_CHUNK));
         for (int64_t k = j * int64_t(TRLX_ADAMW_CHUNK) + tid; k < k1; k += kAdamwThreads)
@@ -223,6 +232,78 @@ __global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t, const trl
         else if (tid - sp.head < e.n - sp.tail0) k = sp.tail0 + (tid - sp.head);
         if (k >= 0) adamw_elem<PT, GT, CLIP>(e, k, s, coef);
     }
+}
+
+// ------------------------------------------------------------------ device-resident schedule
+// b^n by square-and-multiply over the bits of n from the lowest, every product a separately
+// rounded fp64 multiplication (this file is built with -ffp-contract=off): a chain a CPU can
+// restate bit for bit, which it cannot do for another library's pow.
+__host__ __device__ inline double pow_chain(double b, int64_t n) {
+    double r = 1.0, x = b;
+    for (uint64_t k = uint64_t(n); k; k >>= 1) {
+        if (k & 1) r = r * x;
+        if (k >> 1) x = x * x;
+    }
+    return r;
+}
+
+// The scalars of update `step` at rate `lr`, as adamw_step_impl forms them: in fp64, each rounded
+// to fp32 once; b^step by pow_chain.  The subtraction, the division and sqrt are IEEE-exact on
+// the host and on the device (fp64 division and sqrt are correctly rounded there).
+__host__ __device__ inline AdamwScalars adamw_sched_scalars(int64_t step, double lr, double beta1, double beta2,
+                                                            double eps, double weight_decay, double alpha) {
+    const double bc1 = 1.0 - pow_chain(beta1, step), bc2 = 1.0 - pow_chain(beta2, step);
+    AdamwScalars s;
+    s.decay = float(1.0 - lr * weight_decay);
+    s.w1 = float(1.0 - beta1);
+    s.b2 = float(beta2);
+    s.w2 = float(1.0 - beta2);
+    s.neg_step = float(-(lr / bc1));
+    s.sqrt_bc2 = float(sqrt(bc2));
+    s.eps = float(eps);
+    s.alpha = float(alpha);
+    s.beta = float(1.0 - alpha);
+    return s;
+}
+
+struct AdvanceArgs {
+    trlx_adamw_sched* sched;
+    const double* lr_table;
+    int64_t n_lr, sync_every;
+    const trlx_grad_norm_record* rec;  // NULL: none
+    int skip_nonfinite;
+    double beta1, beta2, eps, weight_decay, alpha;
+};
+
+// One wave, one lane at work: the counter, the rate and the scalars of the update that the
+// following k_adamw launches of this stream apply.
+__global__ __launch_bounds__(kWave) void k_adamw_advance(AdvanceArgs a) {
+    if (threadIdx.x != 0) return;
+    trlx_adamw_sched* sc = a.sched;
+    if (a.skip_nonfinite && a.rec && a.rec->nonfinite) {
+        sc->apply = 0;
+        sc->sync = 0;
+        sc->skipped = sc->skipped + 1;
+        return;
+    }
+    const int64_t step = sc->step + 1;
+    const int64_t at = (step < a.n_lr ? step : a.n_lr) - 1;
+    const double lr = a.lr_table[at < 0 ? 0 : at];  // a counter loaded below 0 still reads inside the table
+    const AdamwScalars s = adamw_sched_scalars(step, lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.alpha);
+    sc->step = step;
+    sc->apply = 1;
+    sc->sync = (a.sync_every > 0 && step % a.sync_every == 0) ? 1 : 0;
+    sc->decay = s.decay;
+    sc->w1 = s.w1;
+    sc->b2 = s.b2;
+    sc->w2 = s.w2;
+    sc->neg_step = s.neg_step;
+    sc->sqrt_bc2 = s.sqrt_bc2;
+    sc->eps = s.eps;
+    sc->alpha = s.alpha;
+    sc->beta = s.beta;
+    sc->pad = 0.f;
+    sc->lr = lr;
 }
 
 // ------------------------------------------------------------------ global gradient norm
@@ -363,18 +444,23 @@ __global__ __launch_bounds__(kAdamwThreads) void k_grad_scale(GradTable t, const
 using namespace trlx;
 
 static int adamw_launch(const AdamwTable& t, int p_dtype, int g_dtype, const trlx_grad_norm_record* rec,
-                        hipStream_t stream) {
+                        const trlx_adamw_sched* sched, hipStream_t stream) {
     const dim3 grid{unsigned(t.blk0[t.count])}, block(kAdamwThreads);
-#define TRLX_ADAMW_LAUNCH(PT, GT)                                                                \
-    do {                                                                                         \
-        if (rec) hipLaunchKernelGGL((k_adamw<PT, GT, true>), grid, block, 0, stream, t, rec);    \
-        else hipLaunchKernelGGL((k_adamw<PT, GT, false>), grid, block, 0, stream, t, rec);       \
+#define TRLX_ADAMW_LAUNCH_1(PT, GT, CLIP, DEV) \
+    hipLaunchKernelGGL((k_adamw<PT, GT, CLIP, DEV>), grid, block, 0, stream, t, rec, sched)
+#define TRLX_ADAMW_LAUNCH(PT, GT)                                      \
+    do {                                                               \
+        if (rec && sched) TRLX_ADAMW_LAUNCH_1(PT, GT, true, true);     \
+        else if (rec) TRLX_ADAMW_LAUNCH_1(PT, GT, true, false);        \
+        else if (sched) TRLX_ADAMW_LAUNCH_1(PT, GT, false, true);      \
+        else TRLX_ADAMW_LAUNCH_1(PT, GT, false, false);                \
     } while (0)
     if (p_dtype == TRLX_BF16 && g_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(BF16T, BF16T);
     else if (p_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(BF16T, F32T);
     else if (g_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(F32T, BF16T);
     else TRLX_ADAMW_LAUNCH(F32T, F32T);
 #undef TRLX_ADAMW_LAUNCH
+#undef TRLX_ADAMW_LAUNCH_1
     return check_launch("k_adamw");
 }
 
@@ -394,18 +480,36 @@ static bool disjoint(uintptr_t a, uintptr_t a_bytes, uintptr_t b, uintptr_t b_by
     return a + a_bytes <= b || b + b_bytes <= a;
 }
 
-// rec: NULL for the plain step, the clip record (already checked non-NULL and aligned) otherwise
-static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_record* rec, void* stream) {
+// rec: NULL for the plain step, the clip record (already checked non-NULL and aligned) otherwise.
+// sched: NULL for the by-value scalars, the schedule record (checked likewise) otherwise: the
+// scalar fields of args are then neither read nor validated.
+static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_record* rec,
+                           const trlx_adamw_sched* sched, void* stream) {
     TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_adamw_args");
     const trlx_adamw_args& a = *args;
     TRLX_REQUIRE(a.p_dtype == TRLX_F32 || a.p_dtype == TRLX_BF16, TRLX_ERR_DTYPE, "adamw parameter dtype %d", a.p_dtype);
     TRLX_REQUIRE(a.g_dtype == TRLX_F32 || a.g_dtype == TRLX_BF16, TRLX_ERR_DTYPE, "adamw gradient dtype %d", a.g_dtype);
     TRLX_REQUIRE(a.count >= 0 && (a.count == 0 || (a.p && a.g && a.m && a.v && a.numel)), TRLX_ERR_ARG,
                  "bad adamw tensor list");
-    TRLX_REQUIRE(a.step >= 1, TRLX_ERR_ARG, "adamw step %lld (the first update is step 1)", (long long)a.step);
-    TRLX_REQUIRE(a.lr == a.lr && a.beta1 == a.beta1 && a.beta2 == a.beta2 && a.eps == a.eps &&
-                     a.weight_decay == a.weight_decay,
+    TRLX_REQUIRE(sched || a.step >= 1, TRLX_ERR_ARG, "adamw step %lld (the first update is step 1)", (long long)a.step);
+    TRLX_REQUIRE(sched || (a.lr == a.lr && a.beta1 == a.beta1 && a.beta2 == a.beta2 && a.eps == a.eps &&
+                           a.weight_decay == a.weight_decay),
                  TRLX_ERR_ARG, "adamw: a NaN hyper-parameter");
+    TRLX_REQUIRE(!(sched && rec) || disjoint(reinterpret_cast<uintptr_t>(sched), sizeof(*sched),
+                                             reinterpret_cast<uintptr_t>(rec), sizeof(*rec)),
+                 TRLX_ERR_ARG, "adamw: the schedule record overlaps the clip record");
+    // the table the record's advance reads, named so that the step can keep its tensors off it
+    const uintptr_t lt = sched ? reinterpret_cast<uintptr_t>(a.lr_table) : 0;
+    const uintptr_t lt_bytes = lt ? uintptr_t(a.n_lr) * 8u : 0;
+    if (lt) {
+        TRLX_REQUIRE((lt & 7u) == 0, TRLX_ERR_ARG, "the lr_table is not aligned to 8 bytes");
+        TRLX_REQUIRE(a.n_lr >= 1 && a.n_lr <= (int64_t(1) << 40), TRLX_ERR_ARG,
+                     "adamw: n_lr %lld (at least one rate)", (long long)a.n_lr);
+        TRLX_REQUIRE(disjoint(lt, lt_bytes, reinterpret_cast<uintptr_t>(sched), sizeof(*sched)), TRLX_ERR_ARG,
+                     "adamw: the schedule record overlaps the lr_table");
+        TRLX_REQUIRE(!rec || disjoint(lt, lt_bytes, reinterpret_cast<uintptr_t>(rec), sizeof(*rec)), TRLX_ERR_ARG,
+                     "adamw: the lr_table overlaps the clip record");
+    }
     const int p_es = a.p_dtype == TRLX_BF16 ? 2 : 4, g_es = a.g_dtype == TRLX_BF16 ? 2 : 4;
     static const char* const kNames[6] = {"p", "g", "m", "v", "master", "target"};
     for (int64_t i = 0; i < a.count; ++i) {  // validate everything before the first launch
@@ -415,7 +519,7 @@ static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_rec
         TRLX_REQUIRE(e.p && e.g && e.m && e.v, TRLX_ERR_ARG, "adamw tensor %lld: NULL pointer", (long long)i);
         TRLX_REQUIRE(!(e.master && a.p_dtype != TRLX_BF16), TRLX_ERR_ARG,
                      "adamw tensor %lld: a master is for a bf16 parameter", (long long)i);
-        TRLX_REQUIRE(!e.target || a.alpha == a.alpha, TRLX_ERR_ARG, "adamw: alpha is NaN");
+        TRLX_REQUIRE(!e.target || sched || a.alpha == a.alpha, TRLX_ERR_ARG, "adamw: alpha is NaN");
         TRLX_REQUIRE(e.n <= int64_t(TRLX_ADAMW_CHUNK) * kAdamwMaxGrid, TRLX_ERR_SHAPE,
                      "adamw tensor %lld too large (%lld elements)", (long long)i, (long long)e.n);
         const uintptr_t ptr[6] = {reinterpret_cast<uintptr_t>(e.p),      reinterpret_cast<uintptr_t>(e.g),
@@ -436,8 +540,16 @@ static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_rec
             TRLX_REQUIRE(!ptr[x] || disjoint(reinterpret_cast<uintptr_t>(rec), sizeof(*rec), ptr[x],
                                              uintptr_t(e.n) * uintptr_t(es[x])),
                          TRLX_ERR_ARG, "adamw tensor %lld: the clip record overlaps %s", (long long)i, kNames[x]);
+        for (int x = 0; sched && x < 6; ++x)
+            TRLX_REQUIRE(!ptr[x] || disjoint(reinterpret_cast<uintptr_t>(sched), sizeof(*sched), ptr[x],
+                                             uintptr_t(e.n) * uintptr_t(es[x])),
+                         TRLX_ERR_ARG, "adamw tensor %lld: the schedule record overlaps %s", (long long)i, kNames[x]);
+        for (int x = 0; lt && x < 6; ++x)
+            TRLX_REQUIRE(!ptr[x] || disjoint(lt, lt_bytes, ptr[x], uintptr_t(e.n) * uintptr_t(es[x])), TRLX_ERR_ARG,
+                         "adamw tensor %lld: the lr_table overlaps %s", (long long)i, kNames[x]);
     }
-    // the scalars, formed in double as torch forms them, rounded to fp32 once
+    // the scalars, formed in double as torch forms them, rounded to fp32 once (with a schedule
+    // record the kernel reads its own: these are formed from ignored fields and never used)
     const double bc1 = 1.0 - pow(a.beta1, double(a.step)), bc2 = 1.0 - pow(a.beta2, double(a.step));
     AdamwTable t;
     t.s.decay = float(1.0 - a.lr * a.weight_decay);
@@ -456,7 +568,7 @@ static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_rec
         if (e.n == 0) continue;  // zero-length tensors are skipped
         const int64_t blocks = AdamwSplit(e, p_es, g_es).blocks;
         if (t.count == TRLX_ADAMW_MAX_TENSORS || t.blk0[t.count] + blocks > kAdamwMaxGrid) {
-            const int rc = adamw_launch(t, a.p_dtype, a.g_dtype, rec, (hipStream_t)stream);
+            const int rc = adamw_launch(t, a.p_dtype, a.g_dtype, rec, sched, (hipStream_t)stream);
             if (rc) return rc;
             t.count = 0;
         }
@@ -464,11 +576,11 @@ static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_rec
         t.blk0[t.count + 1] = int(t.blk0[t.count] + blocks);
         ++t.count;
     }
-    return t.count ? adamw_launch(t, a.p_dtype, a.g_dtype, rec, (hipStream_t)stream) : TRLX_OK;
+    return t.count ? adamw_launch(t, a.p_dtype, a.g_dtype, rec, sched, (hipStream_t)stream) : TRLX_OK;
 }
 
 extern "C" int trlx_adamw_step(const trlx_adamw_args* args, void* stream) {
-    return adamw_step_impl(args, nullptr, stream);
+    return adamw_step_impl(args, nullptr, nullptr, stream);
 }
 
 static int check_record(const void* record) {
@@ -482,7 +594,80 @@ extern "C" int trlx_adamw_step_clipped(const trlx_adamw_args* args, const void* 
     TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_adamw_args");
     const int rc = check_record(record);
     if (rc) return rc;
-    return adamw_step_impl(args, static_cast<const trlx_grad_norm_record*>(record), stream);
+    return adamw_step_impl(args, static_cast<const trlx_grad_norm_record*>(record), nullptr, stream);
+}
+
+static int check_sched(const void* sched) {
+    TRLX_REQUIRE(sched, TRLX_ERR_ARG, "NULL schedule record");
+    TRLX_REQUIRE((reinterpret_cast<uintptr_t>(sched) & 7u) == 0, TRLX_ERR_ARG,
+                 "the schedule record is not aligned to 8 bytes");
+    return TRLX_OK;
+}
+
+extern "C" int trlx_adamw_step_dev(const trlx_adamw_args* args, const void* sched, void* stream) {
+    TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_adamw_args");
+    const int rc = check_sched(sched);
+    if (rc) return rc;
+    return adamw_step_impl(args, nullptr, static_cast<const trlx_adamw_sched*>(sched), stream);
+}
+
+extern "C" int trlx_adamw_step_clipped_dev(const trlx_adamw_args* args, const void* grad_record, const void* sched,
+                                           void* stream) {
+    TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_adamw_args");
+    int rc = check_record(grad_record);
+    if (rc) return rc;
+    rc = check_sched(sched);
+    if (rc) return rc;
+    return adamw_step_impl(args, static_cast<const trlx_grad_norm_record*>(grad_record),
+                           static_cast<const trlx_adamw_sched*>(sched), stream);
+}
+
+extern "C" int trlx_adamw_sched_scalars_host(int64_t step, double lr, double beta1, double beta2, double eps,
+                                             double weight_decay, double alpha, float* out) {
+    TRLX_REQUIRE(out, TRLX_ERR_ARG, "NULL output of the schedule scalars");
+    TRLX_REQUIRE(step >= 1, TRLX_ERR_ARG, "adamw step %lld (the first update is step 1)", (long long)step);
+    const AdamwScalars s = adamw_sched_scalars(step, lr, beta1, beta2, eps, weight_decay, alpha);
+    const float v[9] = {s.decay, s.w1, s.b2, s.w2, s.neg_step, s.sqrt_bc2, s.eps, s.alpha, s.beta};
+    for (int i = 0; i < 9; ++i) out[i] = v[i];
+    return TRLX_OK;
+}
+
+extern "C" int trlx_adamw_advance(const trlx_adamw_advance_args* args, void* stream) {
+    TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_adamw_advance_args");
+    const trlx_adamw_advance_args& a = *args;
+    int rc = check_sched(a.sched);
+    if (rc) return rc;
+    TRLX_REQUIRE(a.lr_table, TRLX_ERR_ARG, "NULL lr_table");
+    TRLX_REQUIRE((reinterpret_cast<uintptr_t>(a.lr_table) & 7u) == 0, TRLX_ERR_ARG,
+                 "the lr_table is not aligned to 8 bytes");
+    TRLX_REQUIRE(a.n_lr >= 1, TRLX_ERR_ARG, "adamw advance: n_lr %lld (at least one rate)", (long long)a.n_lr);
+    TRLX_REQUIRE(a.n_lr <= (int64_t(1) << 40), TRLX_ERR_ARG, "adamw advance: n_lr %lld too large", (long long)a.n_lr);
+    TRLX_REQUIRE(a.sync_every >= 0, TRLX_ERR_ARG, "adamw advance: sync_every %lld (0: never)", (long long)a.sync_every);
+    TRLX_REQUIRE(a.beta1 == a.beta1 && a.beta2 == a.beta2 && a.eps == a.eps && a.weight_decay == a.weight_decay &&
+                     a.alpha == a.alpha,
+                 TRLX_ERR_ARG, "adamw advance: a NaN hyper-parameter");
+    if (a.grad_record) {
+        rc = check_record(a.grad_record);
+        if (rc) return rc;
+    }
+    const uintptr_t sc = reinterpret_cast<uintptr_t>(a.sched), lt = reinterpret_cast<uintptr_t>(a.lr_table),
+                    gr = reinterpret_cast<uintptr_t>(a.grad_record), lt_bytes = uintptr_t(a.n_lr) * 8u;
+    TRLX_REQUIRE(disjoint(sc, sizeof(trlx_adamw_sched), lt, lt_bytes), TRLX_ERR_ARG,
+                 "adamw advance: the schedule record overlaps the lr_table");
+    TRLX_REQUIRE(!gr || disjoint(sc, sizeof(trlx_adamw_sched), gr, sizeof(trlx_grad_norm_record)), TRLX_ERR_ARG,
+                 "adamw advance: the schedule record overlaps the grad-norm record");
+    TRLX_REQUIRE(!gr || disjoint(lt, lt_bytes, gr, sizeof(trlx_grad_norm_record)), TRLX_ERR_ARG,
+                 "adamw advance: the lr_table overlaps the grad-norm record");
+    AdvanceArgs k;
+    k.sched = static_cast<trlx_adamw_sched*>(a.sched);
+    k.lr_table = static_cast<const double*>(a.lr_table);
+    k.n_lr = a.n_lr;
+    k.sync_every = a.sync_every;
+    k.rec = static_cast<const trlx_grad_norm_record*>(a.grad_record);
+    k.skip_nonfinite = a.skip_nonfinite;
+    k.beta1 = a.beta1, k.beta2 = a.beta2, k.eps = a.eps, k.weight_decay = a.weight_decay, k.alpha = a.alpha;
+    hipLaunchKernelGGL(k_adamw_advance, dim3(1), dim3(kWave), 0, (hipStream_t)stream, k);
+    return check_launch("k_adamw_advance");
 }
 
 // workgroups of k_grad_sumsq for n elements, whatever the dtype and the alignment: at most

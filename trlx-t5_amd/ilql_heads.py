@@ -198,7 +198,9 @@ class ILQLHeads(nn.Module):
         synced by polyak_update.  For the updates on which post_backward_callback syncs
         (every steps_for_target_q_sync); the others call opt.step().  max_grad_norm= is passed
         on to FusedAdamW.step (the global-norm clip folded into the same update; left out, the
-        optimizer's own max_grad_norm holds)."""
+        optimizer's own max_grad_norm holds).  With FusedAdamW(capturable=True,
+        sync_every=cfg.steps_for_target_q_sync) call this on every update: the device decides
+        which ones sync, which replaces the reference's modulo on the host."""
         step_kw = {} if max_grad_norm is UNSET else {"max_grad_norm": max_grad_norm}
         targets = [p.data for h in self.target_q_heads for p in h.parameters()]
         sources = [p.data for h in self.q_heads for p in h.parameters()]

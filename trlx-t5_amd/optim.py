@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from .ilql_heads import UNSET as _UNSET, check_polyak_pairs, polyak_update
 
-__all__ = ["FusedAdamW", "adamw_step", "clip_grad_norm_"]
+__all__ = ["FusedAdamW", "adamw_step", "clip_grad_norm_", "schedule_table"]
 
 _DTYPES = (torch.float32, torch.bfloat16)
 
@@ -177,9 +177,12 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     return record[0]
 
 
-def _launch(entries, step, lr, beta1, beta2, eps, weight_decay, alpha, record=None):
+def _launch(entries, step, lr, beta1, beta2, eps, weight_decay, alpha, record=None, sched=None, table=None):
     """entries: (p, g, m, v, master or None, target or None), validated.  One trlx_adamw_step per
-    (parameter dtype, gradient dtype, device); with a clip record trlx_adamw_step_clipped."""
+    (parameter dtype, gradient dtype, device); with a clip record trlx_adamw_step_clipped.
+    sched (a device schedule record): the _dev entries, which read every scalar from it and
+    ignore step ... alpha; table: the fp64 rates that record's advance reads, named so that the
+    library can refuse tensors that overlap it."""
     groups = {}
     for e in entries:
         groups.setdefault((e[0].dtype, e[1].dtype, e[0].device), []).append(e)
@@ -196,11 +199,18 @@ def _launch(entries, step, lr, beta1, beta2, eps, weight_decay, alpha, record=No
         a.numel = (ctypes.c_int64 * n)(*[e[0].numel() for e in es])
         a.step, a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = int(step), lr, beta1, beta2, eps, weight_decay
         a.alpha = alpha
+        if table is not None:
+            a.lr_table, a.n_lr = table.data_ptr(), table.numel()
         with torch.cuda.device(dev):
-            if record is None:
-                _lib.call("trlx_adamw_step", ctypes.byref(a), _lib.stream_of(es[0][0]))
+            stream = _lib.stream_of(es[0][0])
+            if sched is not None and record is None:
+                _lib.call("trlx_adamw_step_dev", ctypes.byref(a), sched.data_ptr(), stream)
+            elif sched is not None:
+                _lib.call("trlx_adamw_step_clipped_dev", ctypes.byref(a), record.data_ptr(), sched.data_ptr(), stream)
+            elif record is None:
+                _lib.call("trlx_adamw_step", ctypes.byref(a), stream)
             else:
-                _lib.call("trlx_adamw_step_clipped", ctypes.byref(a), record.data_ptr(), _lib.stream_of(es[0][0]))
+                _lib.call("trlx_adamw_step_clipped", ctypes.byref(a), record.data_ptr(), stream)
 
 
 def _check_hyper(lr, betas, eps, weight_decay):
@@ -267,6 +277,65 @@ def adamw_step(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], ex
         polyak_update(rest_t, rest_s, alpha)
 
 
+def schedule_table(make_scheduler, n_steps, lr):
+    """The learning rates a torch scheduler sets for updates 1 .. n_steps, as a float64 CPU tensor
+    for FusedAdamW(capturable=True, lr_schedule=...): make_scheduler(optimizer) -> scheduler (for
+    example lambda o: CosineAnnealingLR(o, T, eta_min=...)) is run on a throw-away one-parameter
+    torch.optim.SGD of learning rate `lr`, so the table is torch's own schedule bit for bit, for
+    any scheduler, and the device needs no cos."""
+    n_steps = int(n_steps)
+    if n_steps < 1:
+        raise ValueError(f"n_steps must be >= 1, got {n_steps}")
+    opt = torch.optim.SGD([torch.zeros(1, requires_grad=True)], lr=float(lr))
+    sched = make_scheduler(opt)
+    rates = []
+    for _ in range(n_steps):
+        rates.append(float(opt.param_groups[0]["lr"]))
+        opt.step()
+        sched.step()
+    return torch.tensor(rates, dtype=torch.float64)
+
+
+SCHED_WORDS = ctypes.sizeof(_lib.AdamwSched) // 8  # the schedule record as an int64 tensor
+
+
+def _lr_rates(schedule, what="lr_schedule"):
+    rates = torch.as_tensor(schedule, dtype=torch.float64).detach().cpu().reshape(-1).clone()
+    if rates.numel() < 1:
+        raise ValueError(f"{what} must hold at least one learning rate")
+    if not bool(torch.isfinite(rates).all()) or bool((rates < 0).any()):
+        raise ValueError(f"{what} must hold finite learning rates >= 0")
+    return rates
+
+
+def _is_table(x):
+    return isinstance(x, (list, tuple)) or (isinstance(x, torch.Tensor) and x.dim() >= 1)
+
+
+def _check_schedule(schedule, n_groups):
+    """lr_schedule as validated rates: ("shared", rates) or ("per_group", [rates, ...]).  One
+    table for every group: a sequence of numbers (0-d tensors count as numbers) or a 1-D tensor.
+    One table per group: a sequence of sequences / 1-D tensors, or a 2-D tensor."""
+    if isinstance(schedule, torch.Tensor):
+        if schedule.dim() > 2:
+            raise ValueError(f"lr_schedule: a tensor of {schedule.dim()} dimensions (1: one table, 2: one per group)")
+        per_group = schedule.dim() == 2
+    elif isinstance(schedule, (list, tuple)):
+        kinds = {_is_table(x) for x in schedule}
+        if len(kinds) > 1:
+            raise ValueError("lr_schedule mixes learning rates and tables: give one table, or one table per group")
+        per_group = kinds == {True}
+    else:
+        raise ValueError(f"lr_schedule must be a sequence or a tensor of learning rates, got {type(schedule).__name__}")
+    if not per_group:
+        if isinstance(schedule, (list, tuple)):
+            schedule = [float(x) for x in schedule]
+        return "shared", _lr_rates(schedule)
+    if len(schedule) != n_groups:
+        raise ValueError(f"lr_schedule holds {len(schedule)} tables for {n_groups} param groups")
+    return "per_group", [_lr_rates(t, f"lr_schedule[{i}]") for i, t in enumerate(schedule)]
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW on the fused kernel.  Same constructor arguments (lr, betas, eps,
     weight_decay), param_groups and state keys (step: a CPU scalar tensor, exp_avg, exp_avg_sq),
@@ -283,15 +352,55 @@ class FusedAdamW(torch.optim.Optimizer):
     it reads it), so code that inspects .grad after the step sees the raw gradients.  It is an
     attribute of the optimizer, not a key of defaults / param_groups: the state_dict stays
     torch.optim.AdamW's.  After a clipped step, grad_norm and clip_coef are 0-d fp32 device
-    views of the record (None before); reading them is the caller's only host sync."""
+    views of the record (None before); reading them is the caller's only host sync.
+
+    capturable=True (keyword only) keeps the step counter, the learning rate and the seven
+    scalars of the update in a small device record per param group (trlx_adamw_sched), so that
+    step() reads nothing on the host and one captured step() replays correctly under
+    torch.cuda.graph: per group one trlx_adamw_advance launch, then the launches of the update,
+    which read the record.  No host sync in step(), no allocation after the first call.
+      state[p]["step"]  a 0-d int64 device view of the group's counter (torch's keys, as its own
+                        capturable=True keeps a device step); load_state_dict takes a CPU or
+                        device step, requires the parameters of a group to agree (ValueError)
+                        and writes the value into the record.
+      grad is None      ValueError: one counter per group cannot express per-parameter steps.
+      lr_schedule       None: the rate is group["lr"], copied to the device only when it changed
+                        since the last call (a host comparison; change it outside a capture).
+                        Otherwise the per-update rates, entry k-1 for update k, the last entry
+                        holding afterwards: a sequence of numbers or a 1-D tensor for every group,
+                        or one such table per group (a sequence of them, or a 2-D tensor);
+                        validated by the constructor (ValueError).  schedule_table() bakes any torch
+                        scheduler into one.  group["lr"] is then not read.
+      skip_nonfinite    an update whose global gradient norm is inf or NaN is skipped on the
+                        device, as DeepSpeed's optimizer skips it: no parameter, state or target
+                        is written, the counter and the lr index do not advance, skipped_steps
+                        counts it.  Without max_grad_norm the norm is still taken (recorded,
+                        nothing clipped).
+      sync_every        step(polyak=) syncs the targets only on updates whose number is a
+                        multiple of it, decided on the device (0: every call syncs, as without
+                        capturable); every source must then be stepped in the call (ValueError).
+                        The same holds with skip_nonfinite: a source outside the step would be
+                        synced by the host even on an update the device skipped.
+      applied_steps, skipped_steps, last_lr
+                        0-d device views of the record (int64, int64, float64): the view itself
+                        with one param group, a list of one view per group with several.
+    The bias corrections come from a product chain instead of pow() (include/trlx_t5_amd.h,
+    trlx_adamw_advance): the fp32 scalars were those of the default mode bit for bit on every
+    step number measured (1..10000), which is not a guarantee.  skip_nonfinite,
+    sync_every or lr_schedule without capturable raise ValueError."""
 
     max_grad_norm = None
     grad_norm = None
     clip_coef = None
     _clip_buffers = None  # (record, workspace), allocated by the first clipped step
 
+    capturable = False
+    skip_nonfinite = False
+    sync_every = 0
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *,
-                 maximize=False, master_weights=False, max_grad_norm=None):
+                 maximize=False, master_weights=False, max_grad_norm=None, capturable=False, lr_schedule=None,
+                 skip_nonfinite=False, sync_every=0):
         if isinstance(lr, torch.Tensor):
             lr = float(lr)
         _check_hyper(lr, betas, eps, weight_decay)
@@ -301,8 +410,19 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError("FusedAdamW does not support maximize")
         # the keys of torch.optim.AdamW's groups, so the two state_dicts have one structure
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
-                        foreach=None, capturable=False, differentiable=False, fused=None,
+                        foreach=None, capturable=bool(capturable), differentiable=False, fused=None,
                         decoupled_weight_decay=True)
+        if int(sync_every) != sync_every or sync_every < 0:
+            raise ValueError(f"sync_every must be an integer >= 0, got {sync_every}")
+        if not capturable:
+            for name, given in (("skip_nonfinite", skip_nonfinite), ("sync_every", sync_every),
+                                ("lr_schedule", lr_schedule is not None)):
+                if given:
+                    raise ValueError(f"{name} is decided on the device: it needs capturable=True")
+        self.capturable, self.skip_nonfinite, self.sync_every = bool(capturable), bool(skip_nonfinite), int(sync_every)
+        self._lr_schedule = None  # set below, validated against the param groups
+        self._sched = {}         # group index -> {"record", "table", "lr_host"}, made by the first step
+        self._pending_step = {}  # group index -> a loaded step not yet written to a record
         self.master_weights = bool(master_weights)
         if max_grad_norm is not None:
             self.max_grad_norm = _check_max_norm(max_grad_norm, "max_grad_norm")
@@ -311,6 +431,8 @@ class FusedAdamW(torch.optim.Optimizer):
             for p in group["params"]:
                 if p.is_complex():
                     raise ValueError("FusedAdamW does not support complex parameters")
+        if lr_schedule is not None:
+            self._lr_schedule = _check_schedule(lr_schedule, len(self.param_groups))
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -328,11 +450,81 @@ class FusedAdamW(torch.optim.Optimizer):
             for k in ("exp_avg", "exp_avg_sq", "master"):
                 if k in saved[pid]:
                     self.state[p][k] = saved[pid][k].to(device=p.device, dtype=torch.float32, copy=True)
+        if self.capturable:
+            self._load_steps()
 
-    def _init_state(self, p):
+    def _load_steps(self):
+        """Capturable mode after a load: one step per group, written into the group's record."""
+        loaded = {}
+        for gi, group in enumerate(self.param_groups):
+            group["capturable"] = True
+            steps = {int(float(self.state[p]["step"])) for p in group["params"]
+                     if p in self.state and "step" in self.state[p]}
+            if len(steps) > 1:
+                raise ValueError(f"param group {gi}: the loaded parameters disagree on step ({sorted(steps)}); "
+                                 "capturable mode keeps one counter per group")
+            if steps:
+                loaded[gi] = steps.pop()
+        for gi, step in loaded.items():
+            group = self.param_groups[gi]
+            self._pending_step[gi] = step
+            if group["params"] and all(p.is_cuda for p in group["params"]):
+                view = self._sched_of(gi, group)["record"][0]
+                for p in group["params"]:
+                    if p in self.state and "step" in self.state[p]:
+                        self.state[p]["step"] = view
+
+    def _group_rates(self, gi):
+        """The validated rates of group gi (None: follow group["lr"])."""
+        if self._lr_schedule is None:
+            return None
+        kind, rates = self._lr_schedule
+        if kind == "shared":
+            return rates
+        if gi >= len(rates):  # a group added after the constructor
+            raise ValueError(f"lr_schedule holds {len(rates)} tables for {len(self.param_groups)} param groups")
+        return rates[gi]
+
+    def _sched_of(self, gi, group):
+        """The group's device schedule record and lr table, allocated once."""
+        sc = self._sched.get(gi)
+        if sc is None:
+            devs = {p.device for p in group["params"]}
+            if len(devs) != 1:
+                raise ValueError(f"param group {gi}: capturable mode needs the group's parameters on one device")
+            dev = devs.pop()
+            rates = self._group_rates(gi)
+            record = torch.zeros(SCHED_WORDS, dtype=torch.int64, device=dev)
+            if rates is None:
+                lr_host = float(group["lr"])
+                table = torch.tensor([lr_host], dtype=torch.float64).to(dev)
+            else:
+                lr_host, table = None, rates.to(dev)
+            sc = self._sched[gi] = dict(record=record, table=table, lr_host=lr_host)
+        if gi in self._pending_step:
+            sc["record"][0] = self._pending_step.pop(gi)
+        return sc
+
+    def _views(self, pick):
+        out = [pick(self._sched_of(gi, g)["record"]) for gi, g in enumerate(self.param_groups)]
+        return out[0] if len(out) == 1 else out
+
+    @property
+    def applied_steps(self):
+        return self._views(lambda r: r[0]) if self.capturable else None
+
+    @property
+    def skipped_steps(self):
+        return self._views(lambda r: r[1]) if self.capturable else None
+
+    @property
+    def last_lr(self):
+        return self._views(lambda r: r.view(torch.float64)[_lib.AdamwSched.lr.offset // 8]) if self.capturable else None
+
+    def _init_state(self, p, step_view=None):
         state = self.state[p]
         if "step" not in state:
-            state["step"] = torch.tensor(0.0, dtype=torch.float32)
+            state["step"] = torch.tensor(0.0, dtype=torch.float32) if step_view is None else step_view
             state["exp_avg"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
             state["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
         if self.master_weights and p.dtype == torch.bfloat16 and "master" not in state:
@@ -366,6 +558,9 @@ class FusedAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self.capturable:
+            self._step_capturable(polyak, max_grad_norm)
+            return loss
         work = []  # (group, p, state), everything validated before any state changes
         for group in self.param_groups:
             if group.get("amsgrad") or group.get("maximize"):
@@ -401,3 +596,74 @@ class FusedAdamW(torch.optim.Optimizer):
         if rest_t:
             polyak_update(rest_t, rest_s, alpha)
         return loss
+
+    def _step_capturable(self, polyak, max_grad_norm):
+        """step() with the counter, the rate and the scalars on the device: nothing is read on
+        the host, and after the first call nothing is allocated."""
+        groups = [(gi, g) for gi, g in enumerate(self.param_groups) if g["params"]]
+        for gi, group in groups:  # every refusal before any state changes
+            if group.get("amsgrad") or group.get("maximize"):
+                raise ValueError("FusedAdamW does not support amsgrad / maximize")
+            _check_hyper(group["lr"], group["betas"], group["eps"], group["weight_decay"])
+            for p in group["params"]:
+                if p.grad is None:
+                    raise ValueError(f"param group {gi}: a parameter has no gradient; capturable mode keeps one "
+                                     "step counter per group and cannot skip a single parameter")
+                if p.grad.is_sparse:
+                    raise ValueError("FusedAdamW does not support sparse gradients")
+                if p.is_complex():
+                    raise ValueError("FusedAdamW does not support complex parameters")
+        if polyak is not None and (self.sync_every > 0 or self.skip_nonfinite):
+            stepped = {_key(p) for _, g in groups for p in g["params"] if p.numel()}
+            for s in polyak[1]:
+                if _key(s) in stepped:
+                    continue
+                if self.sync_every > 0:
+                    raise ValueError("sync_every > 0: every polyak source must be a parameter stepped in this call "
+                                     "(the cadence is decided on the device; a source outside the step would need "
+                                     "a host branch)")
+                raise ValueError("skip_nonfinite: every polyak source must be a parameter stepped in this call "
+                                 "(whether the update is skipped is decided on the device; a source outside the "
+                                 "step would be synced by the host even on a skipped update)")
+        work = []  # (group index, p, state)
+        for gi, group in groups:
+            for p in group["params"]:
+                _lib.require_cuda(p, p.grad)
+            view = self._sched_of(gi, group)["record"][0]
+            for p in group["params"]:
+                state = self._init_state(p, view)
+                _check_entry(len(work), p, p.grad, state["exp_avg"], state["exp_avg_sq"], state.get("master"))
+                work.append((gi, p, state))
+        targets, alpha, rest_t, rest_s = _fold([p for _, p, _ in work], polyak)
+        if rest_t and (self.sync_every > 0 or self.skip_nonfinite):  # a source listed twice
+            raise ValueError("sync_every > 0 / skip_nonfinite: a polyak source can be synced into one target only")
+        record = None
+        if (max_grad_norm is not None or self.skip_nonfinite) and work:
+            grads = [p.grad for _, p, _ in work]
+            _check_grads(grads)
+            record, workspace = self._clip_record(grads)
+            _grad_norm(grads, float("inf") if max_grad_norm is None else max_grad_norm, record, workspace, 0)
+        sync_every = self.sync_every if self.sync_every > 0 else int(polyak is not None)
+        for gi, group in groups:
+            sc = self._sched_of(gi, group)
+            lr, b1, b2, eps, wd = _check_hyper(group["lr"], group["betas"], group["eps"], group["weight_decay"])
+            if sc["lr_host"] is not None and sc["lr_host"] != lr:  # no schedule table: follow group["lr"]
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("group['lr'] changed inside a graph capture: change it outside, or give "
+                                       "lr_schedule")
+                sc["table"].copy_(torch.tensor([lr], dtype=torch.float64))
+                sc["lr_host"] = lr
+            a = _lib.AdamwAdvanceArgs()
+            a.sched, a.lr_table, a.n_lr = sc["record"].data_ptr(), sc["table"].data_ptr(), sc["table"].numel()
+            a.beta1, a.beta2, a.eps, a.weight_decay, a.alpha = b1, b2, eps, wd, alpha
+            a.sync_every = sync_every
+            a.grad_record = record.data_ptr() if (record is not None and self.skip_nonfinite) else None
+            a.skip_nonfinite = int(self.skip_nonfinite)
+            with torch.cuda.device(sc["record"].device):
+                _lib.call("trlx_adamw_advance", ctypes.byref(a), _lib.stream_of(sc["record"]))
+            entries = [(p, p.grad, st["exp_avg"], st["exp_avg_sq"], st.get("master"), t)
+                       for (g2, p, st), t in zip(work, targets) if g2 == gi]
+            _launch(entries, 0, 0.0, b1, b2, eps, wd, alpha, record if max_grad_norm is not None else None,
+                    sched=sc["record"], table=sc["table"])
+        if rest_t:
+            polyak_update(rest_t, rest_s, alpha)
