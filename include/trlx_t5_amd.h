@@ -154,10 +154,17 @@ int trlx_kl_penalty_rewards(const void* lp, const void* ref_lp, int in_dtype,
  * trlx_gae_num_blocks(B, Teff) tells how many partial records are written.  With
  * stats != NULL the last block to finish also reduces them (fixed order) into stats[4];
  * `ticket` is then a device uint32 that must be 0 before the first call (the kernel
- * re-arms it). */
+ * re-arms it).
+ * gamma and lam are doubles (here and in every entry that takes them): the reference
+ * multiplies the two Python floats and the product meets fp32 tensors, so the kernels use
+ * fl32(gamma) and fl32(gamma*lam), each rounded once; fp32 arguments would round the factors
+ * before the product and move it by an ulp for e.g. (0.99, 0.99).
+ * One workgroup scans up to 16 rows staged in LDS; the rows per block shrink with Teff so
+ * that the launch's whole LDS (dynamic + static) stays within 64 KiB, and a Teff whose single
+ * row does not fit (Teff > 8172) is refused with TRLX_ERR_SHAPE. */
 int64_t trlx_gae_num_blocks(int64_t B, int64_t Teff);
 int trlx_gae_scan(const void* values, const void* rewards, int dtype, int64_t B, int64_t T,
-                  int64_t Teff, float gamma, float lam,
+                  int64_t Teff, double gamma, double lam,
                   const float* lp, const float* ref_lp, float neg_beta, const float* scores,
                   const int64_t* lengths, const int64_t* mask,
                   float* adv_raw, void* ret, int ret_dtype, void* rew_out, int rew_dtype,
@@ -216,15 +223,15 @@ int64_t trlx_ppo_workspace_bytes(int64_t B, int64_t T);
 int trlx_ppo_experience_fused(const void* logits, const void* ref_logits, int dtype, int64_t B, int64_t T,
                               int64_t V, int64_t sb, int64_t st, const int64_t* labels, int64_t lb,
                               int64_t lt, const void* values, int v_dtype, const float* scores,
-                              const int64_t* lengths, const int64_t* mask, float kl_coef, float gamma,
-                              float lam, float* lp, float* ref_lp, float* rewards, float* adv_raw,
+                              const int64_t* lengths, const int64_t* mask, float kl_coef, double gamma,
+                              double lam, float* lp, float* ref_lp, float* rewards, float* adv_raw,
                               void* ret, int ret_dtype, double* stats, void* workspace, void* stream);
 /* The two launches of each fused entry point, separately (same arguments):
  *   experience = trlx_lsm_gather_fwd_ragged(policy, ref -> fp32 lp, ref_lp) + trlx_ppo_rollout_gae
  *   loss       = trlx_ppo_loss_rows + trlx_ppo_rollout_loss  */
 int trlx_ppo_rollout_gae(int64_t B, int64_t T, const float* lp, const float* ref_lp, const void* values,
                          int v_dtype, const float* scores, const int64_t* lengths, const int64_t* mask,
-                         float kl_coef, float gamma, float lam, float* rewards, float* adv_raw, void* ret,
+                         float kl_coef, double gamma, double lam, float* rewards, float* adv_raw, void* ret,
                          int ret_dtype, double* stats, void* workspace, void* stream);
 int trlx_ppo_loss_rows(const void* logits, int dtype, int64_t B, int64_t T, int64_t V, int64_t sb, int64_t st,
                        const int64_t* labels, int64_t lb, int64_t lt, const void* old_lp, int old_dtype,
@@ -1020,7 +1027,7 @@ int trlx_kl_ctl_update(const trlx_kl_ctl* kl, const float* approx_kl, void* stre
  *                               block that writes the stats. */
 int trlx_ppo_rollout_gae_ctl(int64_t B, int64_t T, const float* lp, const float* ref_lp, const void* values,
                              int v_dtype, const float* scores, const int64_t* lengths, const int64_t* mask,
-                             const trlx_score_ctl* ctl, float gamma, float lam, float* rewards, float* adv_raw,
+                             const trlx_score_ctl* ctl, double gamma, double lam, float* rewards, float* adv_raw,
                              void* ret, int ret_dtype, double* stats, void* workspace, void* stream);
 int trlx_ppo_rollout_loss_ctl(int64_t B, int64_t T, const double* stats, float vf_coef, float* loss,
                               float* loss_stats, void* workspace, const trlx_kl_ctl* kl, void* stream);
@@ -1064,7 +1071,7 @@ int trlx_lsm_gather_fwd_loss_tail(const void* x0, const void* x1, int dtype, int
  *       loss tail takes stats8 + 3 as its `stats` (it reads Σ mask at stats[3]). */
 int trlx_ppo_rollout_gae_split(int64_t B, int64_t T, const float* lp, const float* ref_lp, const void* values,
                                int v_dtype, const float* scores, const int64_t* lengths, const int64_t* mask,
-                               const trlx_score_ctl* ctl, float kl_coef, float gamma, float lam, float* adv0,
+                               const trlx_score_ctl* ctl, float kl_coef, double gamma, double lam, float* adv0,
                                float* adv_kl, float* rew_kl, float* rew_score, double* stats8,
                                const double* prev_stats8, float* prev_coef, int prev_unbiased, int mom_lag,
                                void* workspace, void* stream, void* done_event);
@@ -1096,7 +1103,8 @@ typedef struct {
     const int64_t* lengths;           /* [B] or NULL */
     const int64_t* mask;              /* [B,T] or NULL */
     const trlx_score_ctl* ctl;        /* or NULL */
-    float kl_coef, gamma, lam;
+    float kl_coef;
+    double gamma, lam;                /* doubles: see trlx_gae_scan */
     float* adv0;
     float* adv_kl;
     float* rew_kl;

@@ -204,8 +204,8 @@ def kl_penalty_rewards(logprobs, ref_logprobs, kl_coef, scores=None, lengths=Non
     pad = torch.arange(T, device=rewards.device)[None, :] >= lengths[:, None]
     rewards = rewards.masked_fill(pad, 0)
     if scores is not None:
-        rows = torch.arange(rewards.shape[0], device=rewards.device)
-        rewards[rows, lengths - 1] += scores
+        rows = torch.arange(rewards.shape[0], device=rewards.device)[lengths > 0]  # an empty row has no last column
+        rewards[rows, lengths[rows] - 1] += scores[rows]
     return rewards
 
 

@@ -98,7 +98,8 @@ static double row_logprob(const uint16_t* x, int64_t V, int64_t y, std::vector<d
 
 int main() {
     const int64_t B = 6, T = 13, V = 1031;
-    const float beta = 0.05f, gamma = 1.0f, lam = 0.95f, clip = 0.2f, clipv = 0.2f, vf_coef = 1.0f;
+    const float beta = 0.05f, clip = 0.2f, clipv = 0.2f, vf_coef = 1.0f;
+    const double gamma = 1.0, lam = 0.95;  // doubles in the ABI: the library rounds gamma*lam to fp32 once
     const int64_t N = B * T;
     std::mt19937_64 rng(1234);
     std::normal_distribution<float> nrm(0.0f, 1.0f);
@@ -156,7 +157,7 @@ int main() {
         for (int64_t t = T - 1; t >= 0; --t) {
             const double nv = t + 1 < T ? old_values[b * T + t + 1] : 0.0;
             const double delta = hrew[b * T + t] + gamma * nv - old_values[b * T + t];
-            A = delta + double(gamma) * double(lam) * A;
+            A = delta + gamma * lam * A;
             hA[b * T + t] = A;
             hret[b * T + t] = A + old_values[b * T + t];
         }

@@ -152,7 +152,7 @@ class GaeSplitArgs(ctypes.Structure):
     """Mirror of trlx_gae_split_args (include/trlx_t5_amd.h)."""
     _fields_ = [("B", _c_i64), ("T", _c_i64), ("lp", _c_vp), ("ref_lp", _c_vp), ("values", _c_vp), ("v_dtype", _c_int),
                 ("scores", _c_vp), ("lengths", _c_vp), ("mask", _c_vp), ("ctl", ctypes.POINTER(ScoreCtl)),
-                ("kl_coef", _c_f), ("gamma", _c_f), ("lam", _c_f), ("adv0", _c_vp), ("adv_kl", _c_vp),
+                ("kl_coef", _c_f), ("gamma", _c_d), ("lam", _c_d), ("adv0", _c_vp), ("adv_kl", _c_vp),
                 ("rew_kl", _c_vp), ("rew_score", _c_vp), ("stats8", _c_vp), ("mom_lag", _c_int),
                 ("workspace", _c_vp)]
 
@@ -176,7 +176,7 @@ SIGNATURES = {
     "trlx_kl_penalty_rewards": (_c_int, [_c_vp, _c_vp, _c_int, _c_i64, _c_i64, _c_f, _c_vp, _c_vp,
                                          _c_vp, _c_int, _c_vp]),
     "trlx_gae_num_blocks": (_c_i64, [_c_i64, _c_i64]),
-    "trlx_gae_scan": (_c_int, [_c_vp, _c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_f, _c_f, _c_vp, _c_vp,
+    "trlx_gae_scan": (_c_int, [_c_vp, _c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_d, _c_d, _c_vp, _c_vp,
                                _c_f, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_vp,
                                _c_vp, _c_vp, _c_vp]),
     "trlx_moments_num_blocks": (_c_i64, [_c_i64]),
@@ -194,8 +194,8 @@ SIGNATURES = {
     "trlx_ppo_loss_finalize": (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp, _c_d, _c_f, _c_vp, _c_vp, _c_vp]),
     "trlx_scale_by": (_c_int, [_c_vp, _c_vp, _c_int, _c_i64, _c_vp, _c_vp]),
     "trlx_ppo_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
-    "trlx_ppo_rollout_gae": (_c_int, [_c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_f, _c_f,
-                                      _c_f, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    "trlx_ppo_rollout_gae": (_c_int, [_c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_f, _c_d,
+                                      _c_d, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
     "trlx_ppo_loss_rows": (_c_int, [_c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_i64,
                                     _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_int,
                                     _c_vp, _c_int, _c_f, _c_f, _c_f, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp, _c_vp,
@@ -203,7 +203,7 @@ SIGNATURES = {
     "trlx_ppo_rollout_loss": (_c_int, [_c_i64, _c_i64, _c_vp, _c_f, _c_vp, _c_vp, _c_vp, _c_vp]),
     "trlx_ppo_experience_fused": (_c_int, [_c_vp, _c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64,
                                            _c_vp, _c_i64, _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_f,
-                                           _c_f, _c_f, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp,
+                                           _c_d, _c_d, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp,
                                            _c_vp, _c_vp]),
     "trlx_ppo_loss_fused": (_c_int, [_c_vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64,
                                      _c_i64, _c_vp, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int,
@@ -266,11 +266,11 @@ SIGNATURES = {
     "trlx_score_ctl_update": (_c_int, [_c_vp, _c_int, _c_i64, _score_ctl_p, _c_vp, _c_int, _c_vp]),
     "trlx_kl_ctl_update": (_c_int, [_kl_ctl_p, _c_vp, _c_vp]),
     "trlx_ppo_rollout_gae_ctl": (_c_int, [_c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp,
-                                          _score_ctl_p, _c_f, _c_f, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
+                                          _score_ctl_p, _c_d, _c_d, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp,
                                           _c_vp]),
     "trlx_ppo_rollout_loss_ctl": (_c_int, [_c_i64, _c_i64, _c_vp, _c_f, _c_vp, _c_vp, _c_vp, _kl_ctl_p, _c_vp]),
     "trlx_ppo_rollout_gae_split": (_c_int, [_c_i64, _c_i64, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp,
-                                            _score_ctl_p, _c_f, _c_f, _c_f, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                            _score_ctl_p, _c_f, _c_d, _c_d, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                             _c_vp, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp]),
     "trlx_score_moments_merge": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp]),
     "trlx_ppo_whiten_coef": (_c_int, [_c_vp, _c_int, _c_vp, _c_f, _c_vp, _c_vp]),

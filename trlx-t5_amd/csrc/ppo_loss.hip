@@ -27,6 +27,9 @@ constexpr int kLossThreads = 256;
 constexpr int kLossPerBlock = kLossThreads * 2;  // many short blocks: latency, not bandwidth, bound
 constexpr int kSlots = TRLX_PPO_PARTIAL_SLOTS;
 
+// x when x is NaN, else y
+__device__ __forceinline__ float nan_or(float x, float y) { return x != x ? x : y; }
+
 // Loss and the 13 stats from the fixed-order totals of the records (ppo_models.py:162-198;
 // the divisions by N are torch.mean, var is unbiased).  `tot` lives in threads k < kSlots
 // (block_sum_multi layout); thread 0 gathers them through `sh`.
@@ -66,13 +69,18 @@ __global__ __launch_bounds__(kLossThreads) void k_ppo_loss_elem(LossArgs a) {
         const float m = a.mask ? float(a.mask[i]) : 1.0f;
         // value loss (ppo_models.py:155-163)
         const float vlo = ov - a.cv, vhi = ov + a.cv;
-        const float vc = fminf(fmaxf(v, vlo), vhi);
+        // torch.clamp and torch.max return NaN when an operand is NaN; fminf / fmaxf return the
+        // other operand and would report a finite loss for a NaN input
+        const float vc = nan_or(v, nan_or(vlo, nan_or(vhi, fminf(fmaxf(v, vlo), vhi))));
         const float e1 = v - R, e2 = vc - R;
         const float vl1 = mul_rn(e1, e1), vl2 = mul_rn(e2, e2);
-        const float vmax = fmaxf(vl1, vl2);
+        const float vmax = nan_or(vl1, nan_or(vl2, fmaxf(vl1, vl2)));
         // policy loss (ppo_models.py:165-178)
         PolicyTerms pt;
         const float g = ppo_policy_dlp(lp, olp, A, m, inv_msum, a.c, pt);
+        // pg1 = -A·ratio is NaN whenever the clamped term is (NaN ratio or advantage; 0·inf)
+        const float pg1 = mul_rn(-A, pt.ratio);
+        const float pgmax = nan_or(pg1, pt.pgmax);
         if (a.dlp) st_any(a.dlp, a.g_dtype, i, g);
         if (a.dv) {
             const float u = mul_rn(uv, m);
@@ -92,7 +100,7 @@ __global__ __launch_bounds__(kLossThreads) void k_ppo_loss_elem(LossArgs a) {
         acc[0] += double(mul_rn(vmax, m));
         acc[1] += vl2 > vl1 ? 1.0 : 0.0;
         acc[2] += double((pt.ratio - 1.0f) - pt.lr);
-        acc[3] += double(mul_rn(pt.pgmax, m));
+        acc[3] += double(mul_rn(pgmax, m));
         acc[4] += pt.pgclip ? 1.0 : 0.0;
         acc[5] += double(ov);
         acc[6] += double(ov) * double(ov);

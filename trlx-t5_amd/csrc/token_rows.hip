@@ -60,11 +60,16 @@ struct GaeArgs {
 
 constexpr int kGaeThreads = 256;
 constexpr int kGaeMaxRows = 16;      // rows per block: many small blocks, short staging loops
-constexpr int kGaeLdsFloats = 8192;  // per array (32 KB)
+constexpr int kGaeLdsBytes = 64 * 1024;  // the whole launch: dynamic (two staged arrays) + static
+// k_gae's static LDS as the compiler reports it (`make resources`, "LDS Size [bytes/block]" with
+// no dynamic part): red[] 128 B + publish_record_last's s_last 4 B, padded to the 16-B
+// alignment of the dynamic array behind them.  Not below that report.
+constexpr int kGaeStaticLdsBytes = 144;
 
 __global__ __launch_bounds__(kGaeThreads) void k_gae(GaeArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ double red[(kGaeThreads / kWave) * TRLX_MOMENT_SLOTS];
+    static_assert(sizeof(red) + sizeof(int) <= kGaeStaticLdsBytes, "static LDS grew: update kGaeStaticLdsBytes");
     float* sv = lds;                        // values, then returns
     float* sr = lds + a.rpb * a.stride;     // rewards, then advantages
     const int tid = threadIdx.x;
@@ -135,12 +140,20 @@ __global__ __launch_bounds__(kGaeThreads) void k_gae(GaeArgs a) {
     }
 }
 
-static void gae_geometry(int64_t Teff, int& rpb, int& stride) {
-    stride = int((Teff + 1) | 1);
-    int64_t r = kGaeLdsFloats / stride;
+// The largest rpb <= kGaeMaxRows whose two staged arrays plus the static part fit kGaeLdsBytes.
+// Returns false when not even one row fits (rpb = 1 then, for trlx_gae_num_blocks).
+static bool gae_geometry(int64_t Teff, int& rpb, int& stride) {
+    if (Teff < 1) Teff = 1;
+    if (Teff > kGaeLdsBytes) Teff = kGaeLdsBytes;  // far past the limit already; keeps the products small
+    const int64_t st = (Teff + 1) | 1;
+    const int64_t row_bytes = 2 * st * int64_t(sizeof(float));
+    int64_t r = (kGaeLdsBytes - kGaeStaticLdsBytes) / row_bytes;
+    const bool fits = r >= 1;
     if (r > kGaeMaxRows) r = kGaeMaxRows;
     if (r < 1) r = 1;
     rpb = int(r);
+    stride = fits ? int(st) : 0;
+    return fits;
 }
 
 // ------------------------------------------------------------------ A3 moments
@@ -225,7 +238,7 @@ extern "C" int64_t trlx_gae_num_blocks(int64_t B, int64_t Teff) {
 }
 
 extern "C" int trlx_gae_scan(const void* values, const void* rewards, int dtype, int64_t B,
-                             int64_t T, int64_t Teff, float gamma, float lam, const float* lp,
+                             int64_t T, int64_t Teff, double gamma, double lam, const float* lp,
                              const float* ref_lp, float neg_beta, const float* scores,
                              const int64_t* lengths, const int64_t* mask, float* adv_raw, void* ret,
                              int ret_dtype, void* rew_out, int rew_dtype, double* partials,
@@ -238,15 +251,15 @@ extern "C" int trlx_gae_scan(const void* values, const void* rewards, int dtype,
     TRLX_REQUIRE(!lp || Teff == T, TRLX_ERR_SHAPE, "fused KL reward needs response_length == T");
     GaeArgs a = {};
     a.values = values; a.rewards = rewards; a.dtype = dtype; a.B = int(B); a.T = int(T); a.Teff = int(Teff);
-    a.gamma = gamma;
-    a.gl = float(double(gamma) * double(lam));  // python float product, then fp32 (torch scalar)
+    a.gamma = float(gamma);
+    a.gl = float(gamma * lam);  // the Python float product rounded to fp32 once (torch scalar)
     a.lp = lp; a.ref_lp = ref_lp; a.neg_beta = neg_beta; a.scores = scores; a.lengths = lengths;
     a.mask = mask; a.adv = adv_raw; a.ret = ret; a.ret_dtype = ret_dtype; a.rew_out = rew_out;
     a.rew_dtype = rew_dtype; a.partials = partials; a.stats = stats; a.ticket = ticket;
-    gae_geometry(Teff, a.rpb, a.stride);
+    TRLX_REQUIRE(gae_geometry(Teff, a.rpb, a.stride), TRLX_ERR_SHAPE, "response length %lld too long",
+                 (long long)Teff);
     const unsigned grid = unsigned((B + a.rpb - 1) / a.rpb);
-    const size_t lds = size_t(2) * a.rpb * a.stride * sizeof(float);
-    TRLX_REQUIRE(lds <= 64 * 1024, TRLX_ERR_SHAPE, "response length %lld too long", (long long)Teff);
+    const size_t lds = size_t(2) * a.rpb * a.stride * sizeof(float);  // + static <= 64 KiB (gae_geometry)
     hipLaunchKernelGGL(k_gae, dim3(grid), dim3(kGaeThreads), lds, (hipStream_t)stream, a);
     return check_launch("k_gae");
 }
@@ -257,7 +270,8 @@ extern "C" int64_t trlx_moments_num_blocks(int64_t n) {
 
 extern "C" int trlx_moments_partial(const void* x, int dtype, int64_t n, double* partials,
                                     void* stream) {
-    TRLX_REQUIRE(x && partials, TRLX_ERR_ARG, "NULL x/partials");
+    TRLX_REQUIRE(n >= 0, TRLX_ERR_SHAPE, "negative element count %lld", (long long)n);
+    TRLX_REQUIRE((x || n == 0) && partials, TRLX_ERR_ARG, "NULL x/partials");  // an empty tensor has no address
     TRLX_REQUIRE(dtype == TRLX_F32 || dtype == TRLX_BF16 || dtype == 2, TRLX_ERR_DTYPE, "dtype %d", dtype);
     const int64_t nb = trlx_moments_num_blocks(n);
     hipLaunchKernelGGL(k_moments_partial, dim3(unsigned(nb)), dim3(kMomThreads), 0, (hipStream_t)stream,
@@ -274,8 +288,9 @@ extern "C" int trlx_moments_finalize(const double* partials, int64_t nblk, doubl
 
 extern "C" int trlx_whiten_apply(const void* x, int dtype, int64_t n, const double* stats, int unbiased,
                                  int shift_mean, void* out, int out_dtype, void* stream) {
+    if (n == 0) return TRLX_OK;  // before the pointer checks: an empty tensor has no address
+    TRLX_REQUIRE(n > 0, TRLX_ERR_SHAPE, "negative element count %lld", (long long)n);
     TRLX_REQUIRE(x && stats && out, TRLX_ERR_ARG, "NULL x/stats/out");
-    if (n == 0) return TRLX_OK;
     hipLaunchKernelGGL(k_whiten_apply, dim3(elementwise_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream,
                        x, dtype, n, stats, unbiased, shift_mean, out, out_dtype);
     return check_launch("k_whiten_apply");

@@ -1125,7 +1125,7 @@ struct SplitGae {
 
 static int fill_gae(GaeRolloutArgs& e, int64_t B, int64_t T, const float* lp, const float* ref_lp, const void* values,
                     int v_dtype, const float* scores, const int64_t* lengths, const int64_t* mask, float kl_coef,
-                    const trlx_score_ctl* ctl, float gamma, float lam, float* rewards, float* adv_raw, void* ret,
+                    const trlx_score_ctl* ctl, double gamma, double lam, float* rewards, float* adv_raw, void* ret,
                     int ret_dtype, double* stats, void* workspace, const SplitGae* sp) {
     TRLX_REQUIRE(B > 0 && T > 0 && B * T < (1LL << 31), TRLX_ERR_SHAPE, "bad rollout batch %lld x %lld",
                  (long long)B, (long long)T);
@@ -1134,8 +1134,9 @@ static int fill_gae(GaeRolloutArgs& e, int64_t B, int64_t T, const float* lp, co
     e = {};
     carve_workspace(workspace, B, T, &e.ws);
     e.B = int(B); e.T = int(T); e.lp = lp; e.ref_lp = ref_lp; e.values = values; e.v_dtype = v_dtype;
-    e.scores = scores; e.lengths = lengths; e.mask = mask; e.neg_beta = -kl_coef; e.gamma = gamma;
-    e.gl = float(double(gamma) * double(lam));  // python float product, then fp32 (torch scalar)
+    e.scores = scores; e.lengths = lengths; e.mask = mask; e.neg_beta = -kl_coef;
+    e.gamma = float(gamma);
+    e.gl = float(gamma * lam);  // the Python float product rounded to fp32 once (torch scalar)
     e.rewards = rewards; e.adv = adv_raw; e.ret = ret; e.ret_dtype = ret_dtype; e.stats = stats;
     if (ctl) {
         TRLX_REQUIRE(scores && ctl->state_in && ctl->state_out, TRLX_ERR_ARG,
@@ -1165,7 +1166,7 @@ static int fill_gae(GaeRolloutArgs& e, int64_t B, int64_t T, const float* lp, co
 
 static int rollout_gae_impl(int64_t B, int64_t T, const float* lp, const float* ref_lp, const void* values,
                             int v_dtype, const float* scores, const int64_t* lengths, const int64_t* mask,
-                            float kl_coef, const trlx_score_ctl* ctl, float gamma, float lam, float* rewards,
+                            float kl_coef, const trlx_score_ctl* ctl, double gamma, double lam, float* rewards,
                             float* adv_raw, void* ret, int ret_dtype, double* stats, void* workspace, void* stream,
                             const SplitGae* sp = nullptr) {
     GaeRolloutArgs e;
@@ -1185,7 +1186,7 @@ static int rollout_gae_impl(int64_t B, int64_t T, const float* lp, const float* 
 
 extern "C" int trlx_ppo_rollout_gae(int64_t B, int64_t T, const float* lp, const float* ref_lp, const void* values,
                                     int v_dtype, const float* scores, const int64_t* lengths, const int64_t* mask,
-                                    float kl_coef, float gamma, float lam, float* rewards, float* adv_raw, void* ret,
+                                    float kl_coef, double gamma, double lam, float* rewards, float* adv_raw, void* ret,
                                     int ret_dtype, double* stats, void* workspace, void* stream) {
     return rollout_gae_impl(B, T, lp, ref_lp, values, v_dtype, scores, lengths, mask, kl_coef, nullptr, gamma, lam,
                             rewards, adv_raw, ret, ret_dtype, stats, workspace, stream);
@@ -1194,7 +1195,7 @@ extern "C" int trlx_ppo_rollout_gae(int64_t B, int64_t T, const float* lp, const
 extern "C" int trlx_ppo_rollout_gae_ctl(int64_t B, int64_t T, const float* lp, const float* ref_lp,
                                         const void* values, int v_dtype, const float* scores,
                                         const int64_t* lengths, const int64_t* mask, const trlx_score_ctl* ctl,
-                                        float gamma, float lam, float* rewards, float* adv_raw, void* ret,
+                                        double gamma, double lam, float* rewards, float* adv_raw, void* ret,
                                         int ret_dtype, double* stats, void* workspace, void* stream) {
     TRLX_REQUIRE(ctl, TRLX_ERR_ARG, "NULL trlx_score_ctl");
     return rollout_gae_impl(B, T, lp, ref_lp, values, v_dtype, scores, lengths, mask, 0.0f, ctl, gamma, lam,
@@ -1204,7 +1205,7 @@ extern "C" int trlx_ppo_rollout_gae_ctl(int64_t B, int64_t T, const float* lp, c
 extern "C" int trlx_ppo_rollout_gae_split(int64_t B, int64_t T, const float* lp, const float* ref_lp,
                                           const void* values, int v_dtype, const float* scores,
                                           const int64_t* lengths, const int64_t* mask, const trlx_score_ctl* ctl,
-                                          float kl_coef, float gamma, float lam, float* adv0, float* adv_kl,
+                                          float kl_coef, double gamma, double lam, float* adv0, float* adv_kl,
                                           float* rew_kl, float* rew_score, double* stats8, const double* prev_stats8,
                                           float* prev_coef, int prev_unbiased, int mom_lag, void* workspace,
                                           void* stream, void* done_event) {
@@ -1225,7 +1226,7 @@ extern "C" int trlx_ppo_experience_fused(const void* logits, const void* ref_log
                                          int64_t T, int64_t V, int64_t sb, int64_t st, const int64_t* labels,
                                          int64_t lb, int64_t lt, const void* values, int v_dtype,
                                          const float* scores, const int64_t* lengths, const int64_t* mask,
-                                         float kl_coef, float gamma, float lam, float* lp, float* ref_lp,
+                                         float kl_coef, double gamma, double lam, float* lp, float* ref_lp,
                                          float* rewards, float* adv_raw, void* ret, int ret_dtype,
                                          double* stats, void* workspace, void* stream) {
     TRLX_REQUIRE(ref_logits && workspace, TRLX_ERR_ARG, "NULL reference logits / workspace");
