@@ -2,10 +2,10 @@
 """Price the parts of the fused lm_head loss forward's steady-state step (diagnostic only).
 
 Each library under abl/ is the product built with -DLL_ABLATE=<bits> (csrc/lmhead_loss.hip:
-1 softmax, 2 group-sum exchange, 4 next-tile DMA, 8 O product, 16 S product dropped; the
-results of such a build are wrong).  One subprocess per library (TRLX_T5_AMD_LIB), each timing
-trlx_lmhead_logprobs_fwd_saved (forward + combine) and trlx_lmhead_logprobs_bwd (combine + dW)
-at the C2 shape with HIP events, median of --iters.
+32 the saved-P global store, 64 the saved-P LDS transpose, 2048 the LDS-DMA of tile t+2
+dropped; the results of such a build are wrong).  One subprocess per library
+(TRLX_T5_AMD_LIB), each timing trlx_lmhead_logprobs_fwd_saved (forward + combine) and
+trlx_lmhead_logprobs_bwd (combine + dW) at the C2 shape with HIP events, median of --iters.
 
   python tools/lmloss_ablate.py [--libs base,abl/lib_abl1.so,...] [--iters 20]
   (LL_TUNE=key=value,... sets library tunings in each child; LL_STAMPS=1 with a -DLL_STAMP=1 build)

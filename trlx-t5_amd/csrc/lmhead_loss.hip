@@ -33,7 +33,6 @@
 // (recompute) or 128 (saved P) vocab rows, each wave's rows over the whole H or half of it.
 // The streamed operand (W tiles forward, h tiles in dW) is staged by LDS-DMA into ONE swizzled
 // image read both by rows and transposed (ds_read_b64_tr_b16), conflict-free.
-#define TRLX_ROW_TAILS_NO_KERNELS
 #include "ppo_token.h"
 #include "row_order.h"
 
@@ -48,14 +47,13 @@ typedef float f32x16_t __attribute__((ext_vector_type(16)));
 constexpr int kLLRows = 32;            // rows of a staged tile: vocab rows (forward) / tokens (dW)
 constexpr int kLLMaxSplits = 8;        // vocab splits of the forward (workspace sizing)
 constexpr int kLLTokBlock = 64;        // tokens per forward workgroup (LlGeom: NG = 2 groups of 32)
-constexpr float kLLOverflow = 60.0f;
+constexpr float kLLOverflow = 60.0f;   // logit - offset bound of the fixed-offset softmax (e^60)
 // byte span bound of the hidden / weight buffer resources (below the 0x7ffff000 sentinel)
 constexpr int64_t kLLMaxSpan = 0x7fff0000;
 // Diagnostic builds only (-DLL_ABLATE=bits, never the shipped library): drop parts of the
-// forward's steady-state step to price them — 1 softmax, 2 group-sum exchange, 4 next DMA,
-// 8 O product, 16 S product; saved-P stores: 32 no global store, 64 no LDS transpose; the
-// saved-P dW kernel: 128 no P loads, 256 no h DMA, 512 dS kept from the first tile.  Results
-// are wrong in such a build.
+// forward's steady-state step to price them — 32 the saved-P global store, 64 the saved-P LDS
+// transpose (P stored in the wrong layout), 2048 the LDS-DMA of tile t+2.  Results are wrong in
+// such a build.
 #ifndef LL_ABLATE
 #define LL_ABLATE 0
 #endif
@@ -78,7 +76,7 @@ __device__ unsigned long long g_ll_stamps[1 << 16];
 #define LL_TS(v) \
     do {         \
     } while (0)
-#endif   // logit - offset bound of the fixed-offset softmax (e^60)
+#endif
 
 enum LmLossMode { kLLPpo = 0, kLLFwd = 1, kLLBwd = 2 };
 
@@ -286,25 +284,12 @@ __device__ __forceinline__ bf16x8_t ll16_tr_frag(const char* tile, const int* tr
 // 16hv + c of the tile for tokens 8g..8g+7 of the 32-token tile (k_lmloss_dwp's k slots: slot j
 // of lane group g = token 8g + j).  Lane groups g = 2·half, 2·half + 1 come from the forward
 // wave holding the tile's tokens 16·half..16·half+15, so every forward lane stores one whole
-// 16-B chunk (512 contiguous bytes per wave and dW wave).  The transpose runs through a
-// per-wave 16 x 32 LDS image (token rows of kLLPRow bytes): two ds_read_b64_tr_b16 give lane
-// (g, c) column 16·(g >> 1) + c, token rows 8·(g & 1) + 0..3 and + 4..7 (T10).
-constexpr int kLLPRow = 72;
-__device__ __forceinline__ s16x8_t ll_p_stage(char* pscr, bf16x8_t pb, int lane) {
-    typedef __attribute__((address_space(3))) s16x4_t lds_s4;
-    const int g = lane >> 4, c = lane & 15, q = (lane >> 2) & 3, p = lane & 3;
-    const s16x8_t v = __builtin_bit_cast(s16x8_t, pb);
-    *reinterpret_cast<s16x4_t*>(pscr + kLLPRow * c + 8 * g) = s16x4_t{v[0], v[1], v[2], v[3]};
-    *reinterpret_cast<s16x4_t*>(pscr + kLLPRow * c + 32 + 8 * g) = s16x4_t{v[4], v[5], v[6], v[7]};
-    const char* rd = pscr + kLLPRow * (8 * (g & 1) + q) + 32 * (g >> 1) + 8 * p;
-    const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)rd);
-    const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(rd + 4 * kLLPRow));
-    return s16x8_t{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-}
-// The same transpose read straight from the wave's O-exchange slot (the 16 B of P a lane wrote
-// at slot + 16·lane, LL_FWD_OXCH): the 8-B chunk (token R, lane group g', block mb) that the image
-// above holds at kLLPRow·R + 8g' + 32mb sits at 16·(16g' + R) + 8mb, so the two tr reads take
-// those addresses and no image is written (4-way bank conflicts on 2 reads a tile instead).
+// 16-B chunk (512 contiguous bytes per wave and dW wave).  The transpose is read straight from
+// the wave's O-exchange slot (the 16 B of P a lane wrote at slot + 16·lane, see ll_fwd16_block):
+// the 8-B chunk (token R, lane group g', block mb) sits at 16·(16g' + R) + 8mb, and two
+// ds_read_b64_tr_b16 give lane (g, c) vocab row 16·(g >> 1) + c, tokens 8·(g & 1) + 0..3 and
+// + 4..7 (T10; 4-way bank conflicts on these 2 reads a tile, cheaper than writing a padded
+// per-wave transpose image first).
 __device__ __forceinline__ s16x8_t ll_p_stage_slot(const char* slot, int lane) {
     typedef __attribute__((address_space(3))) s16x4_t lds_s4;
     const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
@@ -370,18 +355,37 @@ __device__ __forceinline__ uint16_t* ll_p_elem(const LmLossArgs& a, int v, int m
 
 // ------------------------------------------------------------------ forward, 16x16x32 form
 // A workgroup = 64 tokens (four blocks of 16, one softmax per wave: block w) x one vocab split;
-// h fragments 96 registers, O 192 at H = 768.  Without the two splits below (LL_FWD_SPAIR,
-// LL_FWD_OXCH — both on by default) a wave computes S and O of its own block over the whole H,
-// the k_lmloss_dw layout with the roles swapped.  Per 32-row W tile, on v_mfma_f32_16x16x32_bf16:
+// h fragments 96 registers, O 192 at H = 768.  Per 32-row W tile, on v_mfma_f32_16x16x32_bf16:
 //   S[v][t] = Σ_d W[v][d]·h[t][d]     2 vocab blocks x H/32 k-steps (W rows the A operand, the
 //                                     h fragments the B operand): lane (g, c) ends with vocab
 //                                     rows 16mb + 4g + r of token c
 //   P = 2^(S·log2e − offset·log2e)    8 values a lane; the token's offset is the first tile's
-//                                     max over its 4 lanes (g), fixed for the split, as ll_fwd_block
+//                                     max over its 4 lanes (g), fixed for the split (a wave whose
+//                                     later logits pass it by kLLOverflow flags the block, and
+//                                     the RESTART launch reruns it with the true max)
 //   Oᵀ[d][t] += Σ_v W[v][d]·P[v][t]   H/16 column blocks x one permuted k-step (W read
-//                                     transposed: the A operand; the lane's own 8 P values: B)
+//                                     transposed: the A operand; 8 P values of a token: B)
+// Both products are split over the waves so that every W fragment read from LDS feeds several
+// MFMAs:
+//   S over the hidden halves of a wave pair: wave w = (hidden half w & 1, token pair w >> 1)
+//     accumulates partial S over its half for BOTH token blocks of the pair (h fragments: 2
+//     blocks x H/2 = the same 96 registers), so each W row fragment feeds two MFMAs and a wave
+//     reads half the tile by rows; the partner's partial of the wave's own block comes through
+//     LDS (written in the O loop, read after the next step's first barrier)
+//   O over the hidden quarters of the four waves (the O exchange): wave w accumulates d blocks
+//     16i + 4w + j (i < H/256, j < 4) for all 64 tokens of the workgroup, each transposed W
+//     fragment feeding four MFMAs (one per token block), so a wave reads a quarter of the tile
+//     transposed (12 KB at H = 768) plus the four waves' P (1 KB each, written to the wave's
+//     exchange slot after the softmax, read after a mid-step barrier)
 // Software-pipelined one tile deep over a 3-stage ring: S(t+1) beside softmax(t) and tile t+2's
-// DMA, one barrier, O(t) (DESIGN.md §3 "The forward at HEAD").
+// DMA, the exchange barrier, O(t) (DESIGN.md §3 "The forward at HEAD").
+// The forms without the S pair split or without the O exchange, and the fills of tile t+2 from
+// the O loop (LDS-DMA pieces there, or register-staged) were measured slower and removed (git
+// history keeps them; profiles/r05f_fwd_oxch.txt and DESIGN.md §3 list the measurements).
+//
+// The schedule's knobs (numbers only; the defaults are what ships).  Tile t+2's DMA pieces: every
+// LL_FWD_PIECE_GAP-th gap of the S loop from gap LL_FWD_PIECE_OFF; LL_FWD_PSTAGE_GAP: the gap of
+// the saved-P transpose (at H = 768's 48 gaps; scaled at other H)
 #ifndef LL_FWD_PIECE_GAP
 #define LL_FWD_PIECE_GAP 2
 #endif
@@ -398,44 +402,22 @@ __device__ __forceinline__ uint16_t* ll_p_elem(const LmLossArgs& a, int v, int m
 #ifndef LL_FWD_SMS
 #define LL_FWD_SMS 3
 #endif
-// O exchange (default): the O product splits the hidden columns over the four waves instead of
-// the tokens — wave w accumulates d blocks 16i + 4w + j (i < H/256, j < 4) for all 64 tokens of
-// the workgroup, each transposed W fragment feeding four MFMAs (one per token block) — so a wave
-// reads a quarter of the tile transposed (12 instead of 48 KB at H = 768) plus the four waves'
-// P (1 KB each, written to LDS after the softmax, read after a mid-step barrier)
-#ifndef LL_FWD_OXCH
-#define LL_FWD_OXCH 1
-#endif
 // W row fragments in flight in the S loop
 #ifndef LL_FWD_PF
 #define LL_FWD_PF 4
 #endif
-// S split over the hidden halves of a wave pair (needs the O exchange): wave w = (hidden half
-// w & 1, token pair w >> 1) accumulates partial S over its half for BOTH token blocks of the
-// pair (h fragments: 2 blocks x H/2 = the same 96 registers), so each W row fragment feeds two
-// MFMAs and a wave reads half the tile by rows; the partner's partial of the wave's own block
-// comes through LDS (written in the O loop, read after the next step's barrier)
-#ifndef LL_FWD_SPAIR
-#define LL_FWD_SPAIR 1
-#endif
-// How tile t+2 reaches LDS in step t: 0 = LDS-DMA pieces in the S loop's gaps; 1 = LDS-DMA
-// pieces in the O exchange loop's gaps; 2 = register-staged (buffer loads in the S loop's gaps,
-// ds_write_b128 in the O exchange loop's) — 1 and 2 measured slower (profiles/r05f_fwd_oxch.txt)
-#ifndef LL_FWD_FILL
-#define LL_FWD_FILL 0
-#endif
-// MFMAs carried across a barrier (O exchange + S pair split): the last LL_FWD_DEFO W^T fragments of
-// O(t) (4 MFMAs each) issue after step t+1's first barrier, the last LL_FWD_DEFS MFMAs of S(t+1)
-// after step t's exchange barrier, behind the LDS reads each barrier releases (the W rows of tile
-// t+1 / the exchanged P), so the matrix pipe runs while those reads are in flight
+// MFMAs carried across a barrier: the last LL_FWD_DEFO W^T fragments of O(t) (4 MFMAs each) issue
+// after step t+1's first barrier, the last LL_FWD_DEFS MFMAs of S(t+1) after step t's exchange
+// barrier, behind the LDS reads each barrier releases (the W rows of tile t+1 / the exchanged P),
+// so the matrix pipe runs while those reads are in flight
 #ifndef LL_FWD_DEFO
 #define LL_FWD_DEFO 1
 #endif
 #ifndef LL_FWD_DEFS
 #define LL_FWD_DEFS 4
 #endif
-// O exchange: W^T fragments in flight in the O loop (2 reads each; the first ones read in the S
-// loop's last gaps)
+// W^T fragments in flight in the O loop (2 reads each; the first ones read in the S loop's last
+// gaps)
 #ifndef LL_FWD_PFX
 #define LL_FWD_PFX 2
 #endif
@@ -443,69 +425,51 @@ __device__ __forceinline__ uint16_t* ll_p_elem(const LmLossArgs& a, int v, int m
 #ifndef LL_FWD_XRG
 #define LL_FWD_XRG 4
 #endif
-// SAVEP with the O exchange: the saved-P transpose read from the exchange slot (ll_p_stage_slot)
-#ifndef LL_FWD_PSLOT
-#define LL_FWD_PSLOT 1
-#endif
 template <class G, bool RESTART, bool SAVEP>
 __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, int lin, int ntb, int nsplit,
                                                int nv) {
     constexpr int H = G::H, KS = H / 32, DB = H / 16, NI = G::NI, kStage = G::kStage;
     constexpr int NG = 2 * KS;  // S-phase gaps
-    // tile t+2's DMA pieces: every kPG-th gap of the step's S + O sequence from gap kPO
+    // tile t+2's DMA pieces: piece i in gap kPO + kPG·i of the S loop
     constexpr int kPG = LL_FWD_PIECE_GAP, kPO = LL_FWD_PIECE_OFF;
     static_assert(kPO >= 0, "the DMA piece offset (the first piece's gap)");
-    // piece i of tile t+2 in gap kPO + kPG·i
     auto piece_at = [](int k) { return k >= kPO && (k - kPO) % kPG == 0 && (k - kPO) / kPG < NI; };
-    // SAVEP: the gap (of the S + O sequence) that stages P through LDS (after the pack at 11;
-    // with LL_FWD_SPAIR the O loop's first gap instead)
     // softmax(t) in the S loop's gaps: the token max at kSM0, the offset / overflow flag two gaps
     // later, the exps one every kSMS gaps from kSM0 + 3 (the 8th with the row sum and the bf16 pack
-    // at kSMP), P(t) to the exchange slot at kSMP + 1
+    // at kSMP), P(t) to the exchange slot at kSMP + 1; SAVEP: its transpose read at kPS
     // (the macros are for H = 768's 48 gaps; scaled to the S loop's gaps at other H)
     constexpr int kSM0 = LL_FWD_SM0 * NG / 48, kSMS = LL_FWD_SMS * NG / 48 > 0 ? LL_FWD_SMS * NG / 48 : 1;
     constexpr int kSMP = kSM0 + 3 + 7 * kSMS;
     constexpr int kPS = LL_FWD_PSTAGE_GAP * NG / 48 > kSMP + 1 ? LL_FWD_PSTAGE_GAP * NG / 48 : kSMP + 2;
     static_assert(kSMS >= 1 && kSMP + 1 < 2 * KS, "the softmax gaps inside the S loop");
-    static_assert(kPS > 11 && kPS < NG + DB, "the P staging gap");
+    static_assert(kPS > kSMP + 1, "the saved-P transpose after the exchange slot's write");
     static_assert(NG >= 20, "the P-save gaps");
-    constexpr bool OX = LL_FWD_OXCH;
-    constexpr int OI = DB / 16, OF = 4 * OI;  // OX: the wave's 4-block d groups / its W^T fragments
-    static_assert(!OX || (DB % 16 == 0 && G::kWaves == 4 && kLLTokBlock == 64), "O exchange geometry");
-    static_assert(!OX || (kPG * (NI - 1) + kPO < NG && kPS < NG), "O exchange: the pieces and the P staging in the S loop");
-    constexpr int kFill = LL_FWD_FILL;
-    static_assert(kFill == 0 || (OX && OF == NI), "fills in the O exchange loop: one piece per gap");
-    constexpr bool SP = LL_FWD_SPAIR;
-    constexpr int KH = KS / 2;  // SP: k-steps of a hidden half
-    static_assert(!SP || (OX && KH % 4 == 0 && kFill == 0), "S pair split: the O exchange, whole 128-column segments");
+    constexpr int OI = DB / 16, OF = 4 * OI;  // the wave's 4-block d groups / its W^T fragments
+    static_assert(DB % 16 == 0 && G::kWaves == 4 && kLLTokBlock == 64, "O exchange geometry");
+    static_assert(kPG * (NI - 1) + kPO < NG && kPS < NG, "the pieces and the P staging in the S loop");
+    constexpr int KH = KS / 2;  // k-steps of a hidden half
+    static_assert(KH % 4 == 0, "S pair split: whole 128-column segments per hidden half");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // SAVEP: this wave's P transpose image (the exchange region, unused by this form) and its
-    // place in the dW layout (ll_p_stage / ll_p_store)
-    char* pscr = smem + 3 * kStage + wave * 4096;
-    // OX: this wave's P for the exchange (past the transpose image) and the lane's read of token
-    // block tb's (+ 4096·tb)
-    char* xch = pscr + 2048 + 16 * (lane & 63);
+    // this wave's 4 KB of the exchange region: the partial S of the partner's block (2 KB), then
+    // the wave's P (1 KB)
+    char* xown = smem + 3 * kStage + wave * 4096;
+    // this lane's P in the wave's slot, and its read of token block tb's (+ 4096·tb)
+    char* xch = xown + 2048 + 16 * (lane & 63);
     const char* xrd = smem + 3 * kStage + 2048 + 16 * (lane & 63);
-    constexpr bool PSL = OX && LL_FWD_PSLOT;  // the saved-P transpose from the exchange slot
-    static_assert(!PSL || kPS > kSMP + 1, "the saved-P transpose after the exchange slot's write");
-    auto p_stage = [&](const bf16x8_t& pbv) __attribute__((always_inline)) {
-        if constexpr (PSL)
-            return ll_p_stage_slot(pscr + 2048, lane);
-        else
-            return ll_p_stage(pscr, pbv, lane);
-    };
+    // SAVEP: P(t) transposed for the dW layout, read back from the wave's slot
+    auto p_stage = [&]() __attribute__((always_inline)) { return ll_p_stage_slot(xown + 2048, lane); };
     const int g = lane >> 4, c = lane & 15;
     const int split = lin / ntb, mt = lin - split * ntb;
     const int tm = mt * kLLTokBlock + wave * 16 + c;  // this lane's token (compact index)
-    const int ptt = 2 * mt + (wave >> 1), phalf = wave & 1;
+    const int ptt = 2 * mt + (wave >> 1), phalf = wave & 1;  // SAVEP: its place in the dW layout (ll_p_store)
     const bool valid = tm < nv;
     const int tc = valid ? tm : nv - 1;
     const int row = a.rows ? a.rows[tc] : tc;
-    // B operand of S: lane (g, c) -> h[token c][32ks + 8g .. +7]; SP: hf[ks] own token block,
-    // hf[KH + ks] the partner's (wave ^ 1), columns (H/2)(wave & 1) + 32ks + 8g
+    // B operand of S: lane (g, c) -> h[token c][(H/2)(wave & 1) + 32ks + 8g .. +7]; hf[ks] the
+    // wave's own token block, hf[KH + ks] the partner's (wave ^ 1)
     bf16x8_t hf[KS];
-    if constexpr (SP) {
+    {
         const int tmp = mt * kLLTokBlock + (wave ^ 1) * 16 + c;
         const int tcp = tmp < nv ? tmp : nv - 1;
         const int rowp = a.rows ? a.rows[tcp] : tcp;
@@ -516,15 +480,12 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
             hf[ks] = *reinterpret_cast<const bf16x8_t*>(hp + 32 * ks);
             hf[KH + ks] = *reinterpret_cast<const bf16x8_t*>(hq + 32 * ks);
         }
-    } else {
-        const uint16_t* hp = a.h + int64_t(row) * a.ldh + 8 * g;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) hf[ks] = *reinterpret_cast<const bf16x8_t*>(hp + 32 * ks);
     }
-    // SP: this wave's half of the W rows (rb + the half's segments) and the partner's partial S
+    // this wave's half of the W rows (the row read's base + the half's segments) and the
+    // partner's partial S: read from its region, written to this wave's
     const int rbh = ll16_rb(lane) + KS * 1024 * (wave & 1);
     const char* sxr = smem + 3 * kStage + (wave ^ 1) * 4096 + 16 * (lane & 63);
-    char* sxw = pscr + 16 * (lane & 63);
+    char* sxw = xown + 16 * (lane & 63);
     const int nvt = (a.V + kLLRows - 1) / kLLRows;
     const int t0 = ll_split_t0(split, nvt, nsplit, a.sgran), t1 = ll_split_t0(split + 1, nvt, nsplit, a.sgran);
     // one buffer resource per W tile: its rows [32t, min(V, 32t + 32)), none past the split — rows
@@ -535,15 +496,9 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
         ll16_piece(slot, i, ll_tile_rsrc(a.w, int(a.ldw), t, t < t1 ? a.V : 0), ll_piece_row(i, lane) * int(a.ldw) * 2,
                    lane);
     };
-    auto load_piece = [&](int t, int k) __attribute__((always_inline)) {
-        const int i = wave + G::kWaves * k;
-        return __builtin_amdgcn_raw_buffer_load_b128(ll_tile_rsrc(a.w, int(a.ldw), t, t < t1 ? a.V : 0),
-                                                     ll16_piece_src(i, ll_piece_row(i, lane) * int(a.ldw) * 2, lane), 0, 0);
-    };
-    const int rb = ll16_rb(lane);
-    const int trb[2] = {ll16_trb(lane, 0), ll16_trb(lane, 1)};
-    // OX: W^T fragment (i, j) = d block 16i + 4·wave + j: ll16_tr_frag's offset with the wave's
+    // W^T fragment (i, j) = d block 16i + 4·wave + j: ll16_tr_frag's offset with the wave's
     // part folded into the lane bases (a multiple of 256 B: the conflict-free banking unchanged)
+    const int trb[2] = {ll16_trb(lane, 0), ll16_trb(lane, 1)};
     const int trx[2] = {trb[0] + 8192 * (wave >> 1) + 1024 * (wave & 1), trb[1] + 8192 * (wave >> 1) + 1024 * (wave & 1)};
     auto ox_frag = [&](const char* tile, int f) __attribute__((always_inline)) {
         typedef __attribute__((address_space(3))) s16x4_t lds_s4;
@@ -557,14 +512,14 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
     float mfix = -INFINITY, mtrue = -INFINITY, lrun = 0.0f;
     if (RESTART) mfix = a.mlpart[int64_t(split) * a.N + tc].x;  // the true max pass 0 found
     bool bad = false;
-    f32x4_t O[DB];  // Oᵀ[16nb + 4g + r][token c]; OX: O[4f + tb] = Oᵀ[d block of fragment f][token block tb]
+    f32x4_t O[DB];  // O[4f + tb] = Oᵀ[d block of fragment f, rows 4g + r][token c of token block tb]
 #pragma unroll
     for (int nb = 0; nb < DB; ++nb) O[nb] = f32x4_t{};
-    // OX: O(t) over the wave's d groups for the four token blocks, after the exchange barrier
+    // O(t) over the wave's d groups for the four token blocks, after the exchange barrier
     // (the first PFX fragments come in tf: read before the exchange barrier, they depend on the
     // tile only)
     constexpr int PFX = LL_FWD_PFX;
-    constexpr int DEFO = OX && SP ? LL_FWD_DEFO : 0, DEFS = OX && SP ? LL_FWD_DEFS : 0;
+    constexpr int DEFO = LL_FWD_DEFO, DEFS = LL_FWD_DEFS;
     static_assert(DEFO >= 0 && DEFO < OF - PFX && DEFS >= 0 && DEFS <= 8, "carried MFMAs");
     // the exchanged P of the four token blocks (held past the step for the carried O fragments)
     bf16x8_t px[4], tfd[DEFO > 0 ? DEFO : 1];
@@ -581,8 +536,9 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
                 O[4 * (OF - DEFO + i) + tb] =
                     __builtin_amdgcn_mfma_f32_16x16x32_bf16(tfd[i], px[tb], O[4 * (OF - DEFO + i) + tb], 0, 0, 0);
     };
-    // NF: the fragments done here (OF, or OF − DEFO with the rest carried); pre: after the P reads
-    auto ox_product = [&](const char* tile, bf16x8_t (&tf)[OF], int gbase, auto&& gap, auto&& pre, auto nf_tag)
+    // NF: the fragments done here (OF, or OF − DEFO with the rest carried); gap(f): work placed
+    // after fragment f's MFMAs; pre: after the P reads
+    auto ox_product = [&](const char* tile, bf16x8_t (&tf)[OF], auto&& gap, auto&& pre, auto nf_tag)
                           __attribute__((always_inline)) {
         constexpr int NF = decltype(nf_tag)::value;
 #pragma unroll
@@ -599,12 +555,12 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
             } else {
                 tfd[f - NF] = tf[f];
             }
-            gap(gbase + f);
+            gap(f);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    f32x4_t s[2];  // S of the tile whose softmax comes next (SP: the wave's partial of its own block)
-    f32x4_t so[2];  // SP: the partial of the partner's block (to the exchange)
+    f32x4_t s[2];  // S of the tile whose softmax comes next: the wave's partial of its own block
+    f32x4_t so[2];  // the partial of the partner's block (to the exchange)
     float x[8], pr[8], m4 = 0.0f, nm = 0.0f, ls = 0.0f;
     // softmax of tile t in chunks (chunk k of 12): 0 = the lane's max + the token max over its
     // four lanes, 1 = offset / overflow flag, 2..9 = one exp each, 10 = the row sum
@@ -636,19 +592,15 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
             lrun += ls;
         }
     };
-    auto s_mfma = [&](const char* tile, bf16x8_t* af, int k) __attribute__((always_inline)) {
-        if constexpr (SP) {  // gap k: fragment k/2 = (k-step k/4, block (k/2)&1), token block k&1
-            const int fa = k >> 1, mb = fa & 1, ks = fa >> 1;
-            if (k & 1)
-                so[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[fa], hf[KH + ks], so[mb], 0, 0, 0);
-            else
-                s[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[fa], hf[ks], s[mb], 0, 0, 0);
-        } else {
-            const int mb = k / KS, ks = k % KS;
-            s[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[k], hf[ks], s[mb], 0, 0, 0);
-        }
+    // gap k of the S loop: fragment k/2 = (k-step k/4, block (k/2)&1), token block k&1
+    auto s_mfma = [&](bf16x8_t* af, int k) __attribute__((always_inline)) {
+        const int fa = k >> 1, mb = fa & 1, ks = fa >> 1;
+        if (k & 1)
+            so[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[fa], hf[KH + ks], so[mb], 0, 0, 0);
+        else
+            s[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[fa], hf[ks], s[mb], 0, 0, 0);
     };
-    // SP: W row fragment fa of a tile (rows 16(fa&1) + c, the half's k-step fa>>1)
+    // W row fragment fa of a tile (rows 16(fa&1) + c, the half's k-step fa>>1)
     auto sp_frag = [&](const char* tile, int fa) __attribute__((always_inline)) {
         return ll16_row_frag(tile, rbh, fa & 1, fa >> 1);
     };
@@ -659,16 +611,15 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
 #if LL_STAMP
     unsigned long long stamp[8] = {};
 #endif
-    // step t (t + 1 < t1): restrict LDS regions (alias scopes, as ll_fwd_block)
+    // step t (t + 1 < t1): the three stages as __restrict__ LDS regions (alias scopes: the reads
+    // of tiles t and t+1 and the DMA into t+2 do not order against each other)
     auto step = [&](const char* __restrict__ cur, const char* __restrict__ nx, char* __restrict__ fut, int t)
                     __attribute__((always_inline)) {
         unsigned long long ts0 = 0, ts1 = 0, ts2 = 0, ts2b = 0, ts3 = 0;
         LL_TS(ts0);
         // this wave's pieces of tile t+1 (SAVEP: the previous step's P store, issued after
         // them, may still fly — it has this step to land)
-        if (kFill == 2 && t > t0) {
-            // the wave's own ds_writes of tile t+1 (the barrier's lgkmcnt); the P store may fly
-        } else if (SAVEP && t > t0) {
+        if (SAVEP && t > t0) {
             __builtin_amdgcn_s_waitcnt(ll_vmcnt(1));
         } else {
             __builtin_amdgcn_s_waitcnt(ll_vmcnt(0));
@@ -676,19 +627,14 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
         ll_lds_barrier();  // every wave's; every wave is done with tile t-1
         LL_TS(ts1);
         constexpr int PF = LL_FWD_PF;  // W row fragments in flight (LDS latency under a saturated array)
-        bf16x8_t af[NG];
+        bf16x8_t af[KS];
         f32x4_t xr[2];
-        if constexpr (SP) {
-            xr[0] = *reinterpret_cast<const f32x4_t*>(sxr);  // the partner's partial of S(t)
-            xr[1] = *reinterpret_cast<const f32x4_t*>(sxr + 1024);
+        xr[0] = *reinterpret_cast<const f32x4_t*>(sxr);  // the partner's partial of S(t)
+        xr[1] = *reinterpret_cast<const f32x4_t*>(sxr + 1024);
 #pragma unroll
-            for (int k = 0; k < PF; ++k) af[k] = sp_frag(nx, k);
-        } else {
+        for (int k = 0; k < PF; ++k) af[k] = sp_frag(nx, k);
 #pragma unroll
-            for (int k = 0; k < PF; ++k) af[k] = ll16_row_frag(nx, rb, k / KS, k % KS);
-        }
-#pragma unroll
-        for (int e = 0; e < 8; ++e)  // S(t) for the softmax (SP: + the partner's, at gap LL_FWD_XRG); S(t+1) anew
+        for (int e = 0; e < 8; ++e)  // S(t) for the softmax (+ the partner's, at gap LL_FWD_XRG); S(t+1) anew
             x[e] = s[e >> 2][e & 3];
         if constexpr (DEFO > 0) {
             __builtin_amdgcn_sched_barrier(0);
@@ -701,25 +647,20 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
         so[1] = f32x4_t{};
         bf16x8_t pb;
         s16x8_t pt;
-        vec4u ldv[NI];  // kFill 2: tile t+2's 16-B chunks of this lane
-        bf16x8_t tfx[OF];  // OX: tile t's transposed fragments (the first PFX in the S loop's last gaps)
+        bf16x8_t tfx[OF];  // tile t's transposed fragments (the first PFX in the S loop's last gaps)
 #pragma unroll
         for (int k = 0; k < NG; ++k) {
-            if (SP) {
-                if (!(k & 1) && (k >> 1) + PF < KS) af[(k >> 1) + PF] = sp_frag(nx, (k >> 1) + PF);
-            } else if (k + PF < NG) {
-                af[k + PF] = ll16_row_frag(nx, rb, (k + PF) / KS, (k + PF) % KS);
-            }
-            if (SP && k == LL_FWD_XRG) {
+            if (!(k & 1) && (k >> 1) + PF < KS) af[(k >> 1) + PF] = sp_frag(nx, (k >> 1) + PF);
+            if (k == LL_FWD_XRG) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) x[e] += xr[e >> 2][e & 3];
             }
-            if (k < NG - DEFS) s_mfma(nx, af, k);
-            if (SAVEP && (!SP || PSL) && k == kPS) {
+            if (k < NG - DEFS) s_mfma(af, k);
+            if (SAVEP && k == kPS) {
                 if (kLLAblate & 64) {  // diagnostic: no LDS round trip (wrong layout)
                     pt = __builtin_bit_cast(s16x8_t, pb);
                 } else {
-                    pt = p_stage(pb);  // PSL: after the slot write at gap 12
+                    pt = p_stage();  // after the slot write at kSMP + 1
                 }
             }
             if (k == kSM0) {  // the lane's max + token max (no mask inside the loop: the last tile's own path)
@@ -732,57 +673,35 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
                 sm_chunk(9, t, std::false_type{});
                 sm_chunk(10, t, std::false_type{});
                 pb = pack8(pr);
-            } else if (OX && k == kSMP + 1) {
+            } else if (k == kSMP + 1) {
                 *reinterpret_cast<bf16x8_t*>(xch) = pb;  // the exchange: read after the S loop's barrier
             }
 #pragma unroll
             for (int e = 0; e < 7; ++e)
                 if (k == kSM0 + 3 + kSMS * e) sm_chunk(2 + e, t, std::false_type{});
-            if (kFill == 0 && piece_at(k) && !(kLLAblate & 2048)) issue_piece(t + 2, fut, (k - kPO) / kPG);
-            if (kFill == 2 && piece_at(k)) ldv[(k - kPO) / kPG] = load_piece(t + 2, (k - kPO) / kPG);
-            if (OX && k >= NG - PFX) tfx[k - (NG - PFX)] = ox_frag(cur, k - (NG - PFX));
+            if (piece_at(k) && !(kLLAblate & 2048)) issue_piece(t + 2, fut, (k - kPO) / kPG);
+            if (k >= NG - PFX) tfx[k - (NG - PFX)] = ox_frag(cur, k - (NG - PFX));
             __builtin_amdgcn_sched_barrier(0);
         }
         LL_TS(ts2);
-        if constexpr (OX) {
-            ll_lds_barrier();  // every wave's P(t) in the exchange
-            LL_TS(ts2b);
-            ox_product(cur, tfx, NG, [&](int gk) __attribute__((always_inline)) {
-                const int f = gk - NG;
-                // SP: P(t) through the transpose image, then S(t+1)'s partner partial into the
-                // same region (the partner read the last one before the exchange barrier)
-                if (SP && SAVEP && !PSL && f == 0) pt = ll_p_stage(pscr, pb, lane);
-                if (SP && f == 1) sx_write();
-                if (kFill == 1 && !(kLLAblate & 2048)) issue_piece(t + 2, fut, f);
-                if (kFill == 2) *reinterpret_cast<vec4u*>(fut + (wave + G::kWaves * f) * 1024 + 16 * lane) = ldv[f];
-            }, [&]() __attribute__((always_inline)) {
+        ll_lds_barrier();  // every wave's P(t) in the exchange
+        LL_TS(ts2b);
+        ox_product(cur, tfx, [&](int f) __attribute__((always_inline)) {
+            // S(t+1)'s partial of the partner's block into the wave's region (the partner read
+            // the last one before the exchange barrier)
+            if (f == 1) sx_write();
+        }, [&]() __attribute__((always_inline)) {
 #pragma unroll
-                for (int k = NG - DEFS; k < NG; ++k) s_mfma(nx, af, k);  // S(t+1)'s last, behind the P reads
-            }, std::integral_constant<int, OF - DEFO>{});
-        } else {
-        // ---- O(t): tr reads of tile t's W (cur) | MFMA
-        constexpr int PFO = 4;
-        bf16x8_t tf[DB];
-#pragma unroll
-        for (int nb = 0; nb < PFO; ++nb) tf[nb] = ll16_tr_frag(cur, trb, nb);
-#pragma unroll
-        for (int nb = 0; nb < DB; ++nb) {
-            if (nb + PFO < DB) tf[nb + PFO] = ll16_tr_frag(cur, trb, nb + PFO);
-            O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tf[nb], pb, O[nb], 0, 0, 0);
-            if (SAVEP && NG + nb == kPS) pt = ll_p_stage(pscr, pb, lane);
-            const int gk = NG + nb;
-            if (piece_at(gk)) issue_piece(t + 2, fut, (gk - kPO) / kPG);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        }
-        static_assert(kPG * (NI - 1) + kPO < NG + DB, "every DMA piece before the P store (the step's counted wait)");
+            for (int k = NG - DEFS; k < NG; ++k) s_mfma(af, k);  // S(t+1)'s last, behind the P reads
+        }, std::integral_constant<int, OF - DEFO>{});
+        // every DMA piece is issued before the P store: the next step's counted wait (vmcnt(1))
         if (SAVEP && !(kLLAblate & 32)) ll_p_store(a, pt, t, ptt, phalf, lane);  // after the O loop
         LL_TS(ts3);
 #if LL_STAMP
         stamp[0] += ts1 - ts0;
         stamp[1] += ts2 - ts1;
         stamp[2] += ts3 - ts2;
-        if (OX) stamp[3] += ts2b - ts2;
+        stamp[3] += ts2b - ts2;
         stamp[6] += 1;
 #endif
         (void)ts0, (void)ts1, (void)ts2, (void)ts2b, (void)ts3;
@@ -799,23 +718,15 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
         ll_lds_barrier();
         s[0] = f32x4_t{};
         s[1] = f32x4_t{};
-        if constexpr (SP) {
-            so[0] = f32x4_t{};
-            so[1] = f32x4_t{};
+        so[0] = f32x4_t{};
+        so[1] = f32x4_t{};
 #pragma unroll
-            for (int fa = 0; fa < KS; ++fa) {
-                const bf16x8_t f = sp_frag(c0, fa);
-                s[fa & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f, hf[fa >> 1], s[fa & 1], 0, 0, 0);
-                so[fa & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f, hf[KH + (fa >> 1)], so[fa & 1], 0, 0, 0);
-            }
-            sx_write();
-        } else {
-#pragma unroll
-            for (int k = 0; k < NG; ++k) {
-                const bf16x8_t af = ll16_row_frag(c0, rb, k / KS, k % KS);
-                s[k / KS] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, hf[k % KS], s[k / KS], 0, 0, 0);
-            }
+        for (int fa = 0; fa < KS; ++fa) {  // S(t0)
+            const bf16x8_t f = sp_frag(c0, fa);
+            s[fa & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f, hf[fa >> 1], s[fa & 1], 0, 0, 0);
+            so[fa & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f, hf[KH + (fa >> 1)], so[fa & 1], 0, 0, 0);
         }
+        sx_write();
         for (int t = t0; t + 1 < t1; ++t) {
             step(c0, c1, c2, t);
             char* cc = c0;
@@ -825,34 +736,24 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
         }
         o_carried();  // the last step's carried O fragments
         // the last tile: its (masked) softmax and O product
-        if constexpr (SP) {
-            ll_lds_barrier();  // the partner's partial of the last tile; every wave done with the P exchange
-            s[0] += *reinterpret_cast<const f32x4_t*>(sxr);
-            s[1] += *reinterpret_cast<const f32x4_t*>(sxr + 1024);
-        }
+        ll_lds_barrier();  // the partner's partial of the last tile; every wave done with the P exchange
+        s[0] += *reinterpret_cast<const f32x4_t*>(sxr);
+        s[1] += *reinterpret_cast<const f32x4_t*>(sxr + 1024);
 #pragma unroll
         for (int k = 0; k < 11; ++k) sm_chunk(k, t1 - 1, std::true_type{});
-        const bf16x8_t pb = pack8(pr);
-        if constexpr (OX) {
-            if (!SP) ll_lds_barrier();  // every wave is done reading the exchange of the previous tile
-            *reinterpret_cast<bf16x8_t*>(xch) = pb;
-            ll_lds_barrier();
-            bf16x8_t tfx[OF];
+        *reinterpret_cast<bf16x8_t*>(xch) = pack8(pr);
+        ll_lds_barrier();
+        bf16x8_t tfx[OF];
 #pragma unroll
-            for (int f = 0; f < PFX; ++f) tfx[f] = ox_frag(c0, f);
-            ox_product(c0, tfx, 0, [](int) {}, []() {}, std::integral_constant<int, OF>{});
-        } else {
-#pragma unroll
-            for (int nb = 0; nb < DB; ++nb)
-                O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ll16_tr_frag(c0, trb, nb), pb, O[nb], 0, 0, 0);
-        }
-        if (SAVEP) ll_p_store(a, p_stage(pb), t1 - 1, ptt, phalf, lane);
+        for (int f = 0; f < PFX; ++f) tfx[f] = ox_frag(c0, f);
+        ox_product(c0, tfx, [](int) {}, []() {}, std::integral_constant<int, OF>{});
+        if (SAVEP) ll_p_store(a, p_stage(), t1 - 1, ptt, phalf, lane);
     }
 #if LL_STAMP
     if (!RESTART && lane == 0 && lin * 4 + wave < (1 << 12))
         for (int k = 0; k < 8; ++k) g_ll_stamps[(lin * 4 + wave) * 8 + k] = stamp[k];
 #endif
-    // per-wave overflow flag (ll_fwd_block); the token's true max and Σ over its four lanes
+    // per-wave overflow flag (read by the RESTART launch); the token's true max and Σ over its four lanes
     bool any = false;
     if (!RESTART) {
         any = __any(bad);
@@ -861,25 +762,18 @@ __device__ __forceinline__ void ll_fwd16_block(const LmLossArgs& a, char* smem, 
     const float mt4 = ll_rows_max(mtrue);
     const float mrun = any ? mt4 : mfix;
     const float lt = ll_rows_sum(lrun);
-    if constexpr (OX) {
-        // Oᵀ of token block tb, d = 16(16i + 4·wave + j) + 4g + r
+    // Oᵀ of token block tb, d = 16(16i + 4·wave + j) + 4g + r
 #pragma unroll
-        for (int tb = 0; tb < 4; ++tb) {
-            const int tmb = mt * kLLTokBlock + 16 * tb + c;
-            if (tmb < nv) {
-                float* op = a.opart + (int64_t(split) * a.N + tmb) * a.H + 64 * wave + 4 * g;
+    for (int tb = 0; tb < 4; ++tb) {
+        const int tmb = mt * kLLTokBlock + 16 * tb + c;
+        if (tmb < nv) {
+            float* op = a.opart + (int64_t(split) * a.N + tmb) * a.H + 64 * wave + 4 * g;
 #pragma unroll
-                for (int f = 0; f < OF; ++f)
-                    *reinterpret_cast<f32x4_t*>(op + 256 * (f >> 2) + 16 * (f & 3)) = O[4 * f + tb];
-            }
+            for (int f = 0; f < OF; ++f)
+                *reinterpret_cast<f32x4_t*>(op + 256 * (f >> 2) + 16 * (f & 3)) = O[4 * f + tb];
         }
-        if (valid && g == 0) a.mlpart[int64_t(split) * a.N + tm] = make_float2(mrun, lt);
-    } else if (valid) {
-        float* op = a.opart + (int64_t(split) * a.N + tm) * a.H + 4 * g;
-#pragma unroll
-        for (int nb = 0; nb < DB; ++nb) *reinterpret_cast<f32x4_t*>(op + 16 * nb) = O[nb];
-        if (g == 0) a.mlpart[int64_t(split) * a.N + tm] = make_float2(mrun, lt);
     }
+    if (valid && g == 0) a.mlpart[int64_t(split) * a.N + tm] = make_float2(mrun, lt);
 }
 
 // The first launch: one (token block, split) per workgroup; the split count follows the live

@@ -5,6 +5,7 @@
 //   k_rollout_gae   KL-penalised rewards + GAE (lane-parallel suffix scan) + the
 //                   whitening moments {Σ A, Σ A², n, Σ mask}
 //   k_rollout_loss  fp64 sums of the per-token PPO loss terms -> loss + 13 stats
+//                   (loss_tail_block here; the kernel itself is in vocab_rows.hip)
 // Each block publishes one fp64 record; the block that arrives last reduces them in fixed
 // order (common.h publish_record_last: write-through `sc1` records + one returned atomic,
 // no fences), so each is ONE launch of ~B/4 blocks.  An earlier version folded this work
@@ -224,18 +225,6 @@ __global__ __launch_bounds__(kRolloutThreads) void k_rollout_gae(GaeRolloutArgs 
     gae_block<SPLIT>(e, int(blockIdx.x), int(gridDim.x), red);
 }
 
-// The split-beta whitening coefficients as a launch of its own (one thread): the serial
-// split schedule, and the last batch of a pipelined sequence (nothing left to fold it into).
-// (The two non-template kernels of this header are defined in the one translation unit that
-// launches them, vocab_rows.hip; other includers define TRLX_ROW_TAILS_NO_KERNELS.)
-#ifndef TRLX_ROW_TAILS_NO_KERNELS
-__global__ void k_whiten_coef(const double* stats, int unbiased, const double* ctl_state, float host_beta,
-                              float* coef) {
-    if (threadIdx.x == 0)
-        whiten_coef_split(stats, unbiased, ctl_state ? float(ctl_state[TRLX_CTL_KL_COEF]) : host_beta, coef);
-}
-#endif
-
 // ------------------------------------------------------------------ loss sums per rollout
 struct LossRolloutArgs {
     int B, T;
@@ -350,12 +339,5 @@ __device__ __forceinline__ void loss_tail_block(const LossRolloutArgs& L, int bl
         }
     }
 }
-
-#ifndef TRLX_ROW_TAILS_NO_KERNELS
-__global__ __launch_bounds__(kRolloutThreads) void k_rollout_loss(LossRolloutArgs L) {
-    __shared__ double red[kRolloutsPerBlock * 16];
-    loss_tail_block(L, int(blockIdx.x), int(gridDim.x), red);
-}
-#endif
 
 }  // namespace trlx

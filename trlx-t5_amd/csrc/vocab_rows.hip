@@ -89,6 +89,21 @@ struct RowArgs {
     int* order_ws;            // host: int32 [B·T] scratch for the order (NULL: natural order)
 };
 
+// ------------------------------------------------------------------ rollout tails as launches
+// The split-beta whitening coefficients as a launch of its own (one thread): the serial
+// split schedule, and the last batch of a pipelined sequence (nothing left to fold it into).
+__global__ void k_whiten_coef(const double* stats, int unbiased, const double* ctl_state, float host_beta,
+                              float* coef) {
+    if (threadIdx.x == 0)
+        whiten_coef_split(stats, unbiased, ctl_state ? float(ctl_state[TRLX_CTL_KL_COEF]) : host_beta, coef);
+}
+
+// The loss tail (row_tails.h loss_tail_block) when it is not folded into the next rows launch.
+__global__ __launch_bounds__(kRolloutThreads) void k_rollout_loss(LossRolloutArgs L) {
+    __shared__ double red[kRolloutsPerBlock * 16];
+    loss_tail_block(L, int(blockIdx.x), int(gridDim.x), red);
+}
+
 // ------------------------------------------------------------------ shared row pieces
 template <class DT>
 struct Row {
