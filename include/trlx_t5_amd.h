@@ -544,6 +544,38 @@ int trlx_adamw_step_dev(const trlx_adamw_args* args, const void* sched, void* st
 int trlx_adamw_step_clipped_dev(const trlx_adamw_args* args, const void* grad_record, const void* sched,
                                 void* stream);
 
+/* ---------------------------------------------------------------- AdamW with a bf16 state
+ * trlx_adamw_step_ex is every launch form above behind one entry, with the dtype of m and v
+ * chosen by the caller: grad_record NULL = unclipped (else as trlx_adamw_step_clipped), sched
+ * NULL = the scalars of `args` (else as the _dev entries).  trlx_adamw_args is unchanged.
+ * state_dtype = TRLX_F32: bit for bit trlx_adamw_step / _clipped / _dev / _clipped_dev.
+ * state_dtype = TRLX_BF16: m and v are bf16 arrays — what torch.optim.AdamW keeps for a bf16
+ * parameter (state = zeros_like(p)), the optimizer the reference trains its bf16 models with.
+ * p and g are bf16 too and there is no master.  Per element, the same fp32 scalars, every op a
+ * separately rounded fp32 op (no fma) whose result is rounded to bf16 (round-to-nearest-even)
+ * wherever torch's _single_tensor_adam writes a bf16 tensor, bf(x) below:
+ *   p = bf(p * (1 - lr*wd))                                              mul_
+ *   m = bf(m + (1-b1) * (g - m))                                         lerp_
+ *   v = bf(v * b2);  v = bf(v + (1-b2) * (g * g))                        mul_, addcmul_
+ *   d = bf(sqrt(v));  d = bf(d / sqrt(bc2));  d = bf(d + eps)            sqrt, div, add_
+ *   p = bf(p + (-(lr/bc1)) * (m / d))                                    addcdiv_
+ * The products and the quotient inside lerp_, addcmul_ and addcdiv_ stay fp32.  With a clip
+ * record g is first bf(g * bf(coef)), as in trlx_adamw_step_clipped with a bf16 g; a target is
+ * updated from the stored p exactly as trlx_polyak_update's bf16 form does.  A bf16 v stops
+ * moving once (1-b2) * g*g falls below half an ulp of v — torch's bf16 AdamW does the same.
+ * All four arrays are 2-byte: one 16-byte vector per array per group of 8 elements wherever
+ * p, g, m, v (and target) share a 16-byte phase, element accesses otherwise, same result bits.
+ * HBM traffic per parameter: 14 B (read p, g, m, v, write p, m, v), 16 B clipped (the norm
+ * reads g once more), 18 B with a target (+ read and write of the target); the fp32-state step
+ * on bf16 p and g moves 22 B.
+ * Refused before anything is launched: a state_dtype other than TRLX_F32 / TRLX_BF16, or
+ * TRLX_BF16 with a p_dtype or g_dtype that is not TRLX_BF16 (TRLX_ERR_DTYPE); TRLX_BF16 with a
+ * non-NULL master in a live entry, m or v not aligned to 2 bytes, a record or sched not aligned
+ * to 8 bytes (TRLX_ERR_ARG); and everything the four entries above refuse, the overlap checks
+ * taking m and v at their 2-byte extents. */
+int trlx_adamw_step_ex(const trlx_adamw_args* args, int state_dtype, const void* grad_record, const void* sched,
+                       void* stream);
+
 /* ---------------------------------------------------------------- fused bf16 value head
  * The PPO value head — replaces `make_head(n_embd, 1)` (ppo_models.py:216-222: Linear(H, 2H),
  * ReLU, Linear(2H, 1), all bf16) and its use at :618,:641:

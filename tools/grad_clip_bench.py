@@ -30,8 +30,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch  # noqa: E402
 import __graft_entry__  # noqa: E402
 
-NEW_ENTRIES = ("trlx_grad_norm_workspace_bytes", "trlx_grad_norm", "trlx_adamw_step_clipped")
-if os.environ.get("GRAD_CLIP_BENCH_OLD_LIB"):  # a child on the parent's library: it has no clip entries
+NEW_ENTRIES = ("trlx_grad_norm_workspace_bytes", "trlx_grad_norm", "trlx_adamw_step_clipped", "trlx_adamw_step_ex")
+if os.environ.get("GRAD_CLIP_BENCH_OLD_LIB"):  # a child on the parent's library: it may lack the newer entries
     import importlib.util
     _spec = importlib.util.spec_from_file_location("trlx_t5_amd._lib", os.path.join(__graft_entry__.PKG_DIR, "_lib.py"))
     _mod = importlib.util.module_from_spec(_spec)

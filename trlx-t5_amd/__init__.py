@@ -18,6 +18,8 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
       into the same pass (ILQLHeads.step_and_sync)   trlx/model/accelerate_base_model.py:94-106,263-265
       FusedAdamW(capturable=True, lr_schedule=, skip_nonfinite=, sync_every=), schedule_table —
       step counter, learning rate, non-finite skip and sync cadence on the device (graph capture)
+      FusedAdamW(state_dtype="param") — torch's own state layout: bf16 exp_avg / exp_avg_sq for a
+      bf16 parameter, every op rounded to bf16 as torch.optim.AdamW rounds it (trlx_adamw_step_ex)
   clip_grad_norm_ — the global-L2-norm clip (DeepSpeed `gradient_clipping: 1.0`), stand-alone
       or folded into the step through a device record     configs/deepspeed_configs/default_configs.yml
   ppo_sample_step — one rollout token of generate(**gen_kwargs): min length, temperature,

@@ -309,6 +309,7 @@ SIGNATURES = {
                                                ctypes.POINTER(_c_f)]),
     "trlx_adamw_step_dev": (_c_int, [_adamw_p, _c_vp, _c_vp]),
     "trlx_adamw_step_clipped_dev": (_c_int, [_adamw_p, _c_vp, _c_vp, _c_vp]),
+    "trlx_adamw_step_ex": (_c_int, [_adamw_p, _c_int, _c_vp, _c_vp, _c_vp]),
     "trlx_value_head_splits": (_c_int, [_c_i64, _c_i64]),
     "trlx_value_head_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),
     "trlx_value_head_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i64]),

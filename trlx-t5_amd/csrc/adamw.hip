@@ -4,7 +4,10 @@
 //   k_adamw   torch.optim.AdamW's _single_tensor_adam (decoupled decay) over a by-value table of
 //             tensors in one launch: every op of the update is a separately rounded fp32 op in
 //             torch's order.  p fp32 or bf16 (with or without an fp32 master), g fp32 or bf16,
-//             m and v fp32.  An entry with a target also writes k_polyak's
+//             m and v fp32 (ST = F32T).  ST = BF16T (trlx_adamw_step_ex, bf16 p and g, no master):
+//             m and v are bf16 and every op of the update is rounded to bf16, as torch's own
+//             AdamW leaves a bf16 parameter — 14 B per parameter, every array one 16-B vector
+//             per group of 8.  An entry with a target also writes k_polyak's
 //             target <- alpha·p_new + (1 - alpha)·target from the p just formed, so the sync never
 //             re-reads the parameters.  HBM-bound: 28 B per fp32 parameter (read p, g, m, v, write
 //             p, m, v), 36 B with the fold.  The clipped instantiation (trlx_adamw_step_clipped)
@@ -33,8 +36,8 @@ constexpr int64_t kAdamwMaxGrid = 1LL << 30;
 struct AdamwEntry {
     void* p;
     const void* g;
-    float* m;
-    float* v;
+    void* m;        // fp32, or bf16 with a bf16 state
+    void* v;
     float* master;  // NULL: none
     void* target;   // NULL: none
     int64_t n;
@@ -53,15 +56,16 @@ struct AdamwTable {
 // Host and device derive the split from the same rule.  A pointer of element size es reaches a
 // 16-B boundary after h elements with h = ((16 - addr % 16) % 16) / es modulo 16 / es: the bf16
 // pointers must agree modulo 8, the fp32 pointers modulo 4, and the two kinds modulo 4.
+// s_es: the element size of m and v.
 struct AdamwSplit {
     bool vec;
     int64_t head, ngrp, tail0, blocks;
-    __host__ __device__ AdamwSplit(const AdamwEntry& e, int p_es, int g_es) {
+    __host__ __device__ AdamwSplit(const AdamwEntry& e, int p_es, int g_es, int s_es) {
         const int G = (p_es == 2 || g_es == 2) ? 8 : 4;
         const uintptr_t a[6] = {reinterpret_cast<uintptr_t>(e.p),      reinterpret_cast<uintptr_t>(e.g),
                                 reinterpret_cast<uintptr_t>(e.m),      reinterpret_cast<uintptr_t>(e.v),
                                 reinterpret_cast<uintptr_t>(e.master), reinterpret_cast<uintptr_t>(e.target)};
-        const int es[6] = {p_es, g_es, 4, 4, 4, p_es};
+        const int es[6] = {p_es, g_es, s_es, s_es, 4, p_es};
         int h8 = -1, h4 = -1;
         vec = true;
         for (int i = 0; i < 6; ++i) {
@@ -71,7 +75,9 @@ struct AdamwSplit {
             if (slot < 0) slot = h;
             else if (slot != h) vec = false;
         }
-        if (h8 >= 0 && (h8 & 3) != h4) vec = false;  // m and v are always there: h4 >= 0
+        // an fp32 state: m and v are always there, h4 >= 0; a bf16 state without a master has no
+        // 4-byte array at all (h4 < 0)
+        if (h8 >= 0 && (s_es == 4 || h4 >= 0) && (h8 & 3) != h4) vec = false;
         blocks = (e.n + TRLX_ADAMW_CHUNK - 1) / TRLX_ADAMW_CHUNK;
         if (vec) {
             head = h8 >= 0 ? h8 : h4;
@@ -88,12 +94,31 @@ struct AdamwSplit {
 
 // torch's _single_tensor_adam, one element: mul_, lerp_ (weight < 0.5: a + w·(b - a)), mul_ then
 // addcmul_, sqrt / div / add_, addcdiv_ — correctly rounded sqrt and divisions, no contraction.
-__device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, const AdamwScalars& s) {
+template <class ST>
+__device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, const AdamwScalars& s);
+template <>
+__device__ __forceinline__ void adamw_one<F32T>(float& p, float g, float& m, float& v, const AdamwScalars& s) {
     p = mul_rn(p, s.decay);
     m = add_rn(m, mul_rn(s.w1, __fsub_rn(g, m)));
     v = add_rn(mul_rn(v, s.b2), mul_rn(s.w2, mul_rn(g, g)));
     const float denom = add_rn(__fdiv_rn(__fsqrt_rn(v), s.sqrt_bc2), s.eps);
     p = add_rn(p, mul_rn(s.neg_step, __fdiv_rn(m, denom)));
+}
+
+// The same ops on bf16 tensors (p, g, m, v all bf16-representable on entry): torch computes each
+// op in fp32 and rounds its result to bf16, so every line below ends in one rounding; inside
+// lerp_, addcmul_ and addcdiv_ the products and the quotient stay fp32.
+__device__ __forceinline__ float bf_rn(float x) { return bf2f(f2bf(x)); }
+template <>
+__device__ __forceinline__ void adamw_one<BF16T>(float& p, float g, float& m, float& v, const AdamwScalars& s) {
+    p = bf_rn(mul_rn(p, s.decay));
+    m = bf_rn(add_rn(m, mul_rn(s.w1, __fsub_rn(g, m))));
+    v = bf_rn(mul_rn(v, s.b2));
+    v = bf_rn(add_rn(v, mul_rn(s.w2, mul_rn(g, g))));
+    float d = bf_rn(__fsqrt_rn(v));
+    d = bf_rn(__fdiv_rn(d, s.sqrt_bc2));
+    d = bf_rn(add_rn(d, s.eps));
+    p = bf_rn(add_rn(p, mul_rn(s.neg_step, __fdiv_rn(m, d))));
 }
 
 // k_polyak's rounding (ilql_heads.hip polyak_one): the products and, for bf16, each
@@ -121,15 +146,15 @@ __device__ __forceinline__ float as_stored<BF16T>(float x) { return bf2f(f2bf(x)
 // One element through scalar accesses (the head, the tail and tensors of mixed phase).
 // CLIP: the gradient is g·coef as a store of dtype GT would leave it (k_grad_scale's value);
 // coef arrives already rounded to GT.
-template <class PT, class GT, bool CLIP>
+template <class PT, class GT, class ST, bool CLIP>
 __device__ __forceinline__ void adamw_elem(const AdamwEntry& e, int64_t k, const AdamwScalars& s, float coef) {
     float p = e.master ? e.master[k] : PT::load1(e.p, k);
-    float m = e.m[k], v = e.v[k];
+    float m = ST::load1(e.m, k), v = ST::load1(e.v, k);
     float g = GT::load1(e.g, k);
     if (CLIP) g = as_stored<GT>(mul_rn(g, coef));
-    adamw_one(p, g, m, v, s);
-    e.m[k] = m;
-    e.v[k] = v;
+    adamw_one<ST>(p, g, m, v, s);
+    ST::store1(e.m, k, m);
+    ST::store1(e.v, k, v);
     if (e.master) e.master[k] = p;
     PT::store1(e.p, k, p);
     if (e.target) PT::store1(e.target, k, adamw_sync_one<PT>(as_stored<PT>(p), PT::load1(e.target, k), s));
@@ -166,11 +191,13 @@ __device__ __forceinline__ void store_group(void* base, int64_t grp, const float
 // of the by-value table: uniform loads from a kernel-argument pointer, so they sit in SGPRs as
 // t.s does.  apply == 0: the workgroup leaves before its first load of a tensor; sync == 0: the
 // entry is taken without its target (the split stays the host's, which counted the target).
-template <class PT, class GT, bool CLIP = false, bool DEV = false>
+// ST: the dtype of m and v; BF16T comes with PT = GT = BF16T and no master only.
+template <class PT, class GT, class ST = F32T, bool CLIP = false, bool DEV = false>
 __global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t, const trlx_grad_norm_record* rec,
                                                          const trlx_adamw_sched* __restrict__ sched) {
     typedef typename PT::elem_t PE;
     typedef typename GT::elem_t GE;
+    typedef typename ST::elem_t SE;
     constexpr int G = (PT::kEPV == 8 || GT::kEPV == 8) ? 8 : 4;
     constexpr int kGroups = TRLX_ADAMW_CHUNK / G;  // groups per workgroup
     if (DEV && sched->apply == 0) return;  // a skipped update: block-uniform
@@ -178,7 +205,7 @@ __global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t, const trl
     while (i + 1 < t.count && int(blockIdx.x) >= t.blk0[i + 1]) ++i;  // block-uniform
     const int64_t j = int(blockIdx.x) - t.blk0[i];
     AdamwEntry e = t.e[i];
-    const AdamwSplit sp(e, int(sizeof(PE)), int(sizeof(GE)));
+    const AdamwSplit sp(e, int(sizeof(PE)), int(sizeof(GE)), int(sizeof(SE)));
     if (DEV && sched->sync == 0) e.target = nullptr;
     const AdamwScalars s = DEV ? AdamwScalars{sched->decay, sched->w1, sched->b2, sched->w2, sched->neg_step,
                                               sched->sqrt_bc2, sched->eps, sched->alpha, sched->beta}
@@ -190,13 +217,13 @@ __global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t, const trl
     if (!sp.vec) {
         const int64_t k1 = min(e.n, (j + 1) * int64_t(TRLX_ADAMW_CHUNK));
         for (int64_t k = j * int64_t(TRLX_ADAMW_CHUNK) + tid; k < k1; k += kAdamwThreads)
-            adamw_elem<PT, GT, CLIP>(e, k, s, coef);
+            adamw_elem<PT, GT, ST, CLIP>(e, k, s, coef);
         return;
     }
     // every array from its first 16-B boundary (element sp.head)
     PE* pb = static_cast<PE*>(e.p) + sp.head;
     const GE* gb = static_cast<const GE*>(e.g) + sp.head;
-    float *mb = e.m + sp.head, *vb = e.v + sp.head;
+    SE *mb = static_cast<SE*>(e.m) + sp.head, *vb = static_cast<SE*>(e.v) + sp.head;
     float* wb = e.master ? e.master + sp.head : nullptr;
     PE* tb = e.target ? static_cast<PE*>(e.target) + sp.head : nullptr;
     const int64_t g1 = min(sp.ngrp, (j + 1) * kGroups);
@@ -206,16 +233,16 @@ __global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t, const trl
         if (wb) load_group<F32T, G, false>(wb, q, p);
         else load_group<PT, G, false>(pb, q, p);
         load_group<GT, G, true>(gb, q, g);
-        load_group<F32T, G, false>(mb, q, m);
-        load_group<F32T, G, false>(vb, q, v);
+        load_group<ST, G, false>(mb, q, m);
+        load_group<ST, G, false>(vb, q, v);
         if (CLIP) {
 #pragma unroll
             for (int k = 0; k < G; ++k) g[k] = as_stored<GT>(mul_rn(g[k], coef));
         }
 #pragma unroll
-        for (int k = 0; k < G; ++k) adamw_one(p[k], g[k], m[k], v[k], s);
-        store_group<F32T, G>(mb, q, m);
-        store_group<F32T, G>(vb, q, v);
+        for (int k = 0; k < G; ++k) adamw_one<ST>(p[k], g[k], m[k], v[k], s);
+        store_group<ST, G>(mb, q, m);
+        store_group<ST, G>(vb, q, v);
         if (wb) store_group<F32T, G>(wb, q, p);
         store_group<PT, G>(pb, q, p);
         if (tb) {
@@ -230,7 +257,7 @@ __global__ __launch_bounds__(kAdamwThreads) void k_adamw(AdamwTable t, const trl
         int64_t k = -1;
         if (tid < sp.head) k = tid;
         else if (tid - sp.head < e.n - sp.tail0) k = sp.tail0 + (tid - sp.head);
-        if (k >= 0) adamw_elem<PT, GT, CLIP>(e, k, s, coef);
+        if (k >= 0) adamw_elem<PT, GT, ST, CLIP>(e, k, s, coef);
     }
 }
 
@@ -443,22 +470,23 @@ __global__ __launch_bounds__(kAdamwThreads) void k_grad_scale(GradTable t, const
 
 using namespace trlx;
 
-static int adamw_launch(const AdamwTable& t, int p_dtype, int g_dtype, const trlx_grad_norm_record* rec,
+static int adamw_launch(const AdamwTable& t, int p_dtype, int g_dtype, int s_dtype, const trlx_grad_norm_record* rec,
                         const trlx_adamw_sched* sched, hipStream_t stream) {
     const dim3 grid{unsigned(t.blk0[t.count])}, block(kAdamwThreads);
-#define TRLX_ADAMW_LAUNCH_1(PT, GT, CLIP, DEV) \
-    hipLaunchKernelGGL((k_adamw<PT, GT, CLIP, DEV>), grid, block, 0, stream, t, rec, sched)
-#define TRLX_ADAMW_LAUNCH(PT, GT)                                      \
-    do {                                                               \
-        if (rec && sched) TRLX_ADAMW_LAUNCH_1(PT, GT, true, true);     \
-        else if (rec) TRLX_ADAMW_LAUNCH_1(PT, GT, true, false);        \
-        else if (sched) TRLX_ADAMW_LAUNCH_1(PT, GT, false, true);      \
-        else TRLX_ADAMW_LAUNCH_1(PT, GT, false, false);                \
+#define TRLX_ADAMW_LAUNCH_1(PT, GT, ST, CLIP, DEV) \
+    hipLaunchKernelGGL((k_adamw<PT, GT, ST, CLIP, DEV>), grid, block, 0, stream, t, rec, sched)
+#define TRLX_ADAMW_LAUNCH(PT, GT, ST)                                      \
+    do {                                                                   \
+        if (rec && sched) TRLX_ADAMW_LAUNCH_1(PT, GT, ST, true, true);     \
+        else if (rec) TRLX_ADAMW_LAUNCH_1(PT, GT, ST, true, false);        \
+        else if (sched) TRLX_ADAMW_LAUNCH_1(PT, GT, ST, false, true);      \
+        else TRLX_ADAMW_LAUNCH_1(PT, GT, ST, false, false);                \
     } while (0)
-    if (p_dtype == TRLX_BF16 && g_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(BF16T, BF16T);
-    else if (p_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(BF16T, F32T);
-    else if (g_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(F32T, BF16T);
-    else TRLX_ADAMW_LAUNCH(F32T, F32T);
+    if (s_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(BF16T, BF16T, BF16T);  // the caller checked p and g
+    else if (p_dtype == TRLX_BF16 && g_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(BF16T, BF16T, F32T);
+    else if (p_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(BF16T, F32T, F32T);
+    else if (g_dtype == TRLX_BF16) TRLX_ADAMW_LAUNCH(F32T, BF16T, F32T);
+    else TRLX_ADAMW_LAUNCH(F32T, F32T, F32T);
 #undef TRLX_ADAMW_LAUNCH
 #undef TRLX_ADAMW_LAUNCH_1
     return check_launch("k_adamw");
@@ -468,8 +496,8 @@ static AdamwEntry adamw_entry(const trlx_adamw_args& a, int64_t i) {
     AdamwEntry e;
     e.p = a.p[i];
     e.g = a.g[i];
-    e.m = static_cast<float*>(a.m[i]);
-    e.v = static_cast<float*>(a.v[i]);
+    e.m = a.m[i];
+    e.v = a.v[i];
     e.master = a.master ? static_cast<float*>(a.master[i]) : nullptr;
     e.target = a.target ? a.target[i] : nullptr;
     e.n = a.numel[i];
@@ -482,13 +510,17 @@ static bool disjoint(uintptr_t a, uintptr_t a_bytes, uintptr_t b, uintptr_t b_by
 
 // rec: NULL for the plain step, the clip record (already checked non-NULL and aligned) otherwise.
 // sched: NULL for the by-value scalars, the schedule record (checked likewise) otherwise: the
-// scalar fields of args are then neither read nor validated.
-static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_record* rec,
+// scalar fields of args are then neither read nor validated.  s_dtype: the dtype of m and v.
+static int adamw_step_impl(const trlx_adamw_args* args, int s_dtype, const trlx_grad_norm_record* rec,
                            const trlx_adamw_sched* sched, void* stream) {
     TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_adamw_args");
     const trlx_adamw_args& a = *args;
+    TRLX_REQUIRE(s_dtype == TRLX_F32 || s_dtype == TRLX_BF16, TRLX_ERR_DTYPE, "adamw state dtype %d", s_dtype);
     TRLX_REQUIRE(a.p_dtype == TRLX_F32 || a.p_dtype == TRLX_BF16, TRLX_ERR_DTYPE, "adamw parameter dtype %d", a.p_dtype);
     TRLX_REQUIRE(a.g_dtype == TRLX_F32 || a.g_dtype == TRLX_BF16, TRLX_ERR_DTYPE, "adamw gradient dtype %d", a.g_dtype);
+    TRLX_REQUIRE(s_dtype != TRLX_BF16 || (a.p_dtype == TRLX_BF16 && a.g_dtype == TRLX_BF16), TRLX_ERR_DTYPE,
+                 "adamw: a bf16 state takes bf16 parameters and gradients (p_dtype %d, g_dtype %d)", a.p_dtype,
+                 a.g_dtype);
     TRLX_REQUIRE(a.count >= 0 && (a.count == 0 || (a.p && a.g && a.m && a.v && a.numel)), TRLX_ERR_ARG,
                  "bad adamw tensor list");
     TRLX_REQUIRE(sched || a.step >= 1, TRLX_ERR_ARG, "adamw step %lld (the first update is step 1)", (long long)a.step);
@@ -511,6 +543,7 @@ static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_rec
                      "adamw: the lr_table overlaps the clip record");
     }
     const int p_es = a.p_dtype == TRLX_BF16 ? 2 : 4, g_es = a.g_dtype == TRLX_BF16 ? 2 : 4;
+    const int s_es = s_dtype == TRLX_BF16 ? 2 : 4;
     static const char* const kNames[6] = {"p", "g", "m", "v", "master", "target"};
     for (int64_t i = 0; i < a.count; ++i) {  // validate everything before the first launch
         const AdamwEntry e = adamw_entry(a, i);
@@ -519,13 +552,15 @@ static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_rec
         TRLX_REQUIRE(e.p && e.g && e.m && e.v, TRLX_ERR_ARG, "adamw tensor %lld: NULL pointer", (long long)i);
         TRLX_REQUIRE(!(e.master && a.p_dtype != TRLX_BF16), TRLX_ERR_ARG,
                      "adamw tensor %lld: a master is for a bf16 parameter", (long long)i);
+        TRLX_REQUIRE(!(e.master && s_dtype == TRLX_BF16), TRLX_ERR_ARG,
+                     "adamw tensor %lld: a bf16 state takes no master", (long long)i);
         TRLX_REQUIRE(!e.target || sched || a.alpha == a.alpha, TRLX_ERR_ARG, "adamw: alpha is NaN");
         TRLX_REQUIRE(e.n <= int64_t(TRLX_ADAMW_CHUNK) * kAdamwMaxGrid, TRLX_ERR_SHAPE,
                      "adamw tensor %lld too large (%lld elements)", (long long)i, (long long)e.n);
         const uintptr_t ptr[6] = {reinterpret_cast<uintptr_t>(e.p),      reinterpret_cast<uintptr_t>(e.g),
                                   reinterpret_cast<uintptr_t>(e.m),      reinterpret_cast<uintptr_t>(e.v),
                                   reinterpret_cast<uintptr_t>(e.master), reinterpret_cast<uintptr_t>(e.target)};
-        const int es[6] = {p_es, g_es, 4, 4, 4, p_es};
+        const int es[6] = {p_es, g_es, s_es, s_es, 4, p_es};
         for (int x = 0; x < 6; ++x)
             TRLX_REQUIRE((ptr[x] & uintptr_t(es[x] - 1)) == 0, TRLX_ERR_ARG,
                          "adamw tensor %lld: %s not aligned to the element size", (long long)i, kNames[x]);
@@ -566,9 +601,9 @@ static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_rec
     for (int64_t i = 0; i < a.count; ++i) {
         const AdamwEntry e = adamw_entry(a, i);
         if (e.n == 0) continue;  // zero-length tensors are skipped
-        const int64_t blocks = AdamwSplit(e, p_es, g_es).blocks;
+        const int64_t blocks = AdamwSplit(e, p_es, g_es, s_es).blocks;
         if (t.count == TRLX_ADAMW_MAX_TENSORS || t.blk0[t.count] + blocks > kAdamwMaxGrid) {
-            const int rc = adamw_launch(t, a.p_dtype, a.g_dtype, rec, sched, (hipStream_t)stream);
+            const int rc = adamw_launch(t, a.p_dtype, a.g_dtype, s_dtype, rec, sched, (hipStream_t)stream);
             if (rc) return rc;
             t.count = 0;
         }
@@ -576,11 +611,11 @@ static int adamw_step_impl(const trlx_adamw_args* args, const trlx_grad_norm_rec
         t.blk0[t.count + 1] = int(t.blk0[t.count] + blocks);
         ++t.count;
     }
-    return t.count ? adamw_launch(t, a.p_dtype, a.g_dtype, rec, sched, (hipStream_t)stream) : TRLX_OK;
+    return t.count ? adamw_launch(t, a.p_dtype, a.g_dtype, s_dtype, rec, sched, (hipStream_t)stream) : TRLX_OK;
 }
 
 extern "C" int trlx_adamw_step(const trlx_adamw_args* args, void* stream) {
-    return adamw_step_impl(args, nullptr, nullptr, stream);
+    return adamw_step_impl(args, TRLX_F32, nullptr, nullptr, stream);
 }
 
 static int check_record(const void* record) {
@@ -594,7 +629,7 @@ extern "C" int trlx_adamw_step_clipped(const trlx_adamw_args* args, const void* 
     TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_adamw_args");
     const int rc = check_record(record);
     if (rc) return rc;
-    return adamw_step_impl(args, static_cast<const trlx_grad_norm_record*>(record), nullptr, stream);
+    return adamw_step_impl(args, TRLX_F32, static_cast<const trlx_grad_norm_record*>(record), nullptr, stream);
 }
 
 static int check_sched(const void* sched) {
@@ -608,7 +643,7 @@ extern "C" int trlx_adamw_step_dev(const trlx_adamw_args* args, const void* sche
     TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_adamw_args");
     const int rc = check_sched(sched);
     if (rc) return rc;
-    return adamw_step_impl(args, nullptr, static_cast<const trlx_adamw_sched*>(sched), stream);
+    return adamw_step_impl(args, TRLX_F32, nullptr, static_cast<const trlx_adamw_sched*>(sched), stream);
 }
 
 extern "C" int trlx_adamw_step_clipped_dev(const trlx_adamw_args* args, const void* grad_record, const void* sched,
@@ -618,7 +653,20 @@ extern "C" int trlx_adamw_step_clipped_dev(const trlx_adamw_args* args, const vo
     if (rc) return rc;
     rc = check_sched(sched);
     if (rc) return rc;
-    return adamw_step_impl(args, static_cast<const trlx_grad_norm_record*>(grad_record),
+    return adamw_step_impl(args, TRLX_F32, static_cast<const trlx_grad_norm_record*>(grad_record),
+                           static_cast<const trlx_adamw_sched*>(sched), stream);
+}
+
+// Every launch form with the dtype of m and v chosen by the caller: grad_record NULL = unclipped,
+// sched NULL = the scalars of args.  TRLX_F32 is the four entries above.
+extern "C" int trlx_adamw_step_ex(const trlx_adamw_args* args, int state_dtype, const void* grad_record,
+                                  const void* sched, void* stream) {
+    TRLX_REQUIRE(args, TRLX_ERR_ARG, "NULL trlx_adamw_args");
+    int rc = grad_record ? check_record(grad_record) : TRLX_OK;
+    if (rc) return rc;
+    rc = sched ? check_sched(sched) : TRLX_OK;
+    if (rc) return rc;
+    return adamw_step_impl(args, state_dtype, static_cast<const trlx_grad_norm_record*>(grad_record),
                            static_cast<const trlx_adamw_sched*>(sched), stream);
 }
 

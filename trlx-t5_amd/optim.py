@@ -17,8 +17,15 @@ reference ends with (accelerate_base_model.py:94-106, 263-265):
                   record on the device and scales every gradient element as it loads it, so the
                   clip costs one more read of the gradients and .grad is never rewritten.
 
+  state_dtype="param"
+                  torch's own state layout: exp_avg and exp_avg_sq are zeros_like(p), bf16 for a
+                  bf16 parameter, and every op of the update is rounded to bf16 as torch rounds
+                  it — the optimizer the reference runs on its bf16 models, at 4 B of state per
+                  parameter instead of 8 (trlx_adamw_step_ex).
+
 Every element goes through torch's _single_tensor_adam ops in fp32, each rounded separately
-(trlx_adamw_step in include/trlx_t5_amd.h).  exp_avg and exp_avg_sq are always fp32.
+(trlx_adamw_step in include/trlx_t5_amd.h).  exp_avg and exp_avg_sq are fp32 unless the caller
+asks for bf16 ones (adamw_step with bf16 moments, FusedAdamW(state_dtype="param")).
 """
 import ctypes
 from itertools import chain
@@ -41,11 +48,20 @@ def _check_entry(i, p, g, m, v, master):
         raise ValueError(f"tensor {i}: unsupported gradient dtype {g.dtype} (float32 / bfloat16)")
     if g.layout != torch.strided:
         raise ValueError(f"tensor {i}: sparse gradients are not supported")
-    for name, t in (("exp_avg", m), ("exp_avg_sq", v), ("master", master)):
-        if t is None:
-            continue
-        if t.dtype != torch.float32:
-            raise ValueError(f"tensor {i}: {name} must be float32, got {t.dtype}")
+    for name, t in (("exp_avg", m), ("exp_avg_sq", v)):
+        if t.dtype not in _DTYPES:
+            raise ValueError(f"tensor {i}: {name} must be float32 or bfloat16, got {t.dtype}")
+    if m.dtype != v.dtype:  # one of the two is bf16: name that one
+        name, other = ("exp_avg", "exp_avg_sq") if m.dtype == torch.bfloat16 else ("exp_avg_sq", "exp_avg")
+        raise ValueError(f"tensor {i}: {name} must be float32 as {other} is (or both bfloat16), got torch.bfloat16")
+    if master is not None and master.dtype != torch.float32:
+        raise ValueError(f"tensor {i}: master must be float32, got {master.dtype}")
+    if m.dtype == torch.bfloat16:  # torch's layout for a bf16 parameter: everything bf16, no master
+        if p.dtype != torch.bfloat16 or g.dtype != torch.bfloat16:
+            raise ValueError(f"tensor {i}: bfloat16 exp_avg / exp_avg_sq need a bfloat16 parameter and gradient, "
+                             f"got {p.dtype} and {g.dtype}")
+        if master is not None:
+            raise ValueError(f"tensor {i}: bfloat16 exp_avg / exp_avg_sq take no master")
     if master is not None and p.dtype != torch.bfloat16:
         raise ValueError(f"tensor {i}: a master is for a bfloat16 parameter, this one is {p.dtype}")
     for name, t in (("grad", g), ("exp_avg", m), ("exp_avg_sq", v), ("master", master)):
@@ -179,14 +195,15 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
 
 def _launch(entries, step, lr, beta1, beta2, eps, weight_decay, alpha, record=None, sched=None, table=None):
     """entries: (p, g, m, v, master or None, target or None), validated.  One trlx_adamw_step per
-    (parameter dtype, gradient dtype, device); with a clip record trlx_adamw_step_clipped.
+    (parameter dtype, gradient dtype, state dtype, device); with a clip record
+    trlx_adamw_step_clipped; bf16 moments go through trlx_adamw_step_ex.
     sched (a device schedule record): the _dev entries, which read every scalar from it and
     ignore step ... alpha; table: the fp64 rates that record's advance reads, named so that the
     library can refuse tensors that overlap it."""
     groups = {}
     for e in entries:
-        groups.setdefault((e[0].dtype, e[1].dtype, e[0].device), []).append(e)
-    for (pd, gd, dev), es in groups.items():
+        groups.setdefault((e[0].dtype, e[1].dtype, e[2].dtype, e[0].device), []).append(e)
+    for (pd, gd, sd, dev), es in groups.items():
         n = len(es)
 
         def column(k):
@@ -203,7 +220,9 @@ def _launch(entries, step, lr, beta1, beta2, eps, weight_decay, alpha, record=No
             a.lr_table, a.n_lr = table.data_ptr(), table.numel()
         with torch.cuda.device(dev):
             stream = _lib.stream_of(es[0][0])
-            if sched is not None and record is None:
+            if sd == torch.bfloat16:
+                _lib.call("trlx_adamw_step_ex", ctypes.byref(a), _lib.BF16, _lib.ptr(record), _lib.ptr(sched), stream)
+            elif sched is not None and record is None:
                 _lib.call("trlx_adamw_step_dev", ctypes.byref(a), sched.data_ptr(), stream)
             elif sched is not None:
                 _lib.call("trlx_adamw_step_clipped_dev", ctypes.byref(a), record.data_ptr(), sched.data_ptr(), stream)
@@ -234,7 +253,9 @@ def adamw_step(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], ex
                max_grad_norm: Optional[float] = None, grad_norm_record: Optional[torch.Tensor] = None):
     """One AdamW update (decoupled decay) of every tensor, in place, `step` >= 1 being the number
     of this update (torch's state["step"] after its increment).  params: fp32 / bf16; grads:
-    fp32 / bf16; exp_avgs, exp_avg_sqs: fp32; masters: None, or per tensor None or the fp32
+    fp32 / bf16; exp_avgs, exp_avg_sqs: all fp32, or all bf16 — torch's state of a bf16 parameter:
+    params and grads are then bf16, there are no masters and every op of the update is rounded
+    to bf16 as torch.optim.AdamW rounds it; masters: None, or per tensor None or the fp32
     master of a bf16 parameter (the master is updated, the parameter is the master rounded to
     bf16).  polyak=(targets, sources, alpha): after the update, target <- alpha·source +
     (1 - alpha)·target as polyak_update writes it; a source that is one of `params` is synced
@@ -258,6 +279,9 @@ def adamw_step(params: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], ex
         raise ValueError("grad_norm_record is written by the clip: give max_grad_norm too")
     for i, e in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs, masters)):
         _check_entry(i, *e)
+        if e[2].dtype != exp_avgs[0].dtype:
+            raise ValueError(f"tensor {i}: exp_avg is {e[2].dtype} but tensor 0's is {exp_avgs[0].dtype}; the moments "
+                             "of one call are all float32 or all bfloat16")
     if polyak is not None:
         check_polyak_pairs(list(polyak[0]), list(polyak[1]))
     _lib.require_cuda(*params, *grads, *exp_avgs, *exp_avg_sqs, *masters)
@@ -340,7 +364,16 @@ class FusedAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW on the fused kernel.  Same constructor arguments (lr, betas, eps,
     weight_decay), param_groups and state keys (step: a CPU scalar tensor, exp_avg, exp_avg_sq),
     so lr schedulers drive it unchanged and a torch.optim.AdamW.state_dict() loads into it and
-    the other way round.  exp_avg and exp_avg_sq are fp32 whatever the parameter's dtype.
+    the other way round.  exp_avg and exp_avg_sq are fp32 whatever the parameter's dtype
+    (state_dtype="float32", the default).
+    state_dtype="param" (keyword only): the state is torch.zeros_like(p) as in torch.optim.AdamW —
+    bf16 moments for a bf16 parameter, updated with every op rounded to bf16 as torch rounds it
+    (include/trlx_t5_amd.h, trlx_adamw_step_ex); fp32 parameters are unaffected.  A bf16
+    parameter then needs a bf16 .grad (ValueError at step()), master_weights=True is refused by
+    the constructor (ValueError), load_state_dict takes bf16 moments as saved and rounds fp32
+    ones to bf16 once, and state_dict() loads into torch.optim.AdamW over the same parameters
+    with nothing converted.  This reproduces torch's precision, bf16 exp_avg_sq standing still
+    once (1 - beta2)·g² is below half its ulp included; it is not more accurate than fp32 state.
     master_weights=True keeps an fp32 `master` state per bf16 parameter (absent for fp32
     parameters): the master takes the update, the parameter is the master rounded to bf16.
     A parameter whose .grad is None is skipped and its step does not advance.  amsgrad,
@@ -394,13 +427,14 @@ class FusedAdamW(torch.optim.Optimizer):
     clip_coef = None
     _clip_buffers = None  # (record, workspace), allocated by the first clipped step
 
+    state_dtype = "float32"
     capturable = False
     skip_nonfinite = False
     sync_every = 0
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *,
                  maximize=False, master_weights=False, max_grad_norm=None, capturable=False, lr_schedule=None,
-                 skip_nonfinite=False, sync_every=0):
+                 skip_nonfinite=False, sync_every=0, state_dtype="float32"):
         if isinstance(lr, torch.Tensor):
             lr = float(lr)
         _check_hyper(lr, betas, eps, weight_decay)
@@ -408,6 +442,12 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError("FusedAdamW does not support amsgrad")
         if maximize:
             raise ValueError("FusedAdamW does not support maximize")
+        if state_dtype not in ("float32", "param"):
+            raise ValueError(f"state_dtype must be 'float32' or 'param', got {state_dtype!r}")
+        if master_weights and state_dtype == "param":
+            raise ValueError("state_dtype='param' keeps torch's bfloat16 state for a bfloat16 parameter; an fp32 "
+                             "master (master_weights=True) goes with state_dtype='float32'")
+        self.state_dtype = state_dtype
         # the keys of torch.optim.AdamW's groups, so the two state_dicts have one structure
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
                         foreach=None, capturable=bool(capturable), differentiable=False, fused=None,
@@ -435,10 +475,18 @@ class FusedAdamW(torch.optim.Optimizer):
             self._lr_schedule = _check_schedule(lr_schedule, len(self.param_groups))
 
     def load_state_dict(self, state_dict):
+        if self.state_dtype == "param" and any("master" in st for st in state_dict["state"].values()):
+            raise ValueError("the checkpoint holds fp32 masters; state_dtype='param' keeps none")
         super().load_state_dict(state_dict)
         for group in self.param_groups:
             if group.get("amsgrad") or group.get("maximize"):
                 raise ValueError("FusedAdamW does not support amsgrad / maximize (loaded param_groups)")
+        if self.state_dtype == "param":
+            # Optimizer.load_state_dict has cast every state tensor to its parameter's dtype, which
+            # is this layout: bf16 moments are copied as saved, fp32 ones rounded to bf16 once (RNE)
+            if self.capturable:
+                self._load_steps()
+            return
         # Optimizer.load_state_dict casts every state tensor to its parameter's dtype; exp_avg,
         # exp_avg_sq and master of a bf16 parameter are fp32 here: take them from the saved values
         saved = state_dict["state"]
@@ -525,8 +573,9 @@ class FusedAdamW(torch.optim.Optimizer):
         state = self.state[p]
         if "step" not in state:
             state["step"] = torch.tensor(0.0, dtype=torch.float32) if step_view is None else step_view
-            state["exp_avg"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
-            state["exp_avg_sq"] = torch.zeros_like(p, dtype=torch.float32, memory_format=torch.contiguous_format)
+            dtype = p.dtype if self.state_dtype == "param" else torch.float32
+            state["exp_avg"] = torch.zeros_like(p, dtype=dtype, memory_format=torch.contiguous_format)
+            state["exp_avg_sq"] = torch.zeros_like(p, dtype=dtype, memory_format=torch.contiguous_format)
         if self.master_weights and p.dtype == torch.bfloat16 and "master" not in state:
             state["master"] = p.detach().to(torch.float32, memory_format=torch.contiguous_format, copy=True)
         return state
