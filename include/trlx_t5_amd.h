@@ -923,6 +923,64 @@ typedef struct TrlxPpoSampleProcArgs {
 } TrlxPpoSampleProcArgs;
 int trlx_ppo_sample_proc(const TrlxPpoSampleProcArgs* a, void* stream);
 
+/* ---------------------------------------------------------------- T5 decode-step attention
+ * One query token per (batch row, head) over a device KV cache — replaces, per decoder layer
+ * and generated token, the body of HF's T5Attention between the q / k / v projections and the
+ * `o` projection (cache append, [B, nH, 1, t] matmul, compute_bias, mask add, fp32 softmax,
+ * second matmul) with ONE launch, one workgroup per (batch row, head).  T5's attention: no
+ * 1/sqrt(d) scaling, a bucketed relative-position bias added to the self-attention scores, an
+ * encoder key mask on the cross-attention.  Forward only (generation runs under no_grad).
+ *   q, k_new, v_new : [B, n_heads, d_kv] of `dtype` as a base pointer + a row stride in elements
+ *                     (ldq, ldk, ldv >= n_heads * d_kv; head h at offset h * d_kv): a
+ *                     [B, 1, n_heads * d_kv] projection output or a slice of a fused qkv
+ *                     projection is read in place.  With B == 1 the strides are not read.
+ *   out             : [B, n_heads * d_kv] of `dtype`, contiguous — what `o` takes.
+ * mode TRLX_T5_ATTN_SELF, kv_len = t + 1:
+ *   k, v : the cache [B, n_heads, max_len, d_kv], contiguous (HF's layout), in/out.  k_new[b, h, :]
+ *   and v_new[b, h, :] are stored to column t; no other column is written, columns above t are
+ *   never read, and key / value t are taken from the registers that hold k_new / v_new, never
+ *   read back from the cache.
+ *     score_j = q · k_j + bias_by_distance[h, t - j]          0 <= j <= t
+ *   bias_by_distance: fp32 [n_heads, max_len] or NULL (no bias); key_mask must be NULL.
+ * mode TRLX_T5_ATTN_CROSS, kv_len = max_len = S:
+ *   k, v : [B, n_heads, S, d_kv], contiguous, read only; k_new, v_new, bias_by_distance NULL; t is
+ *   not read.  key_mask: int64 [B, S] or NULL; a key with key_mask[b, j] == 0 is excluded from the
+ *   softmax and neither its key nor its value row is read (holes allowed).
+ *     score_j = q · k_j                                        key_mask[b, j] != 0
+ * out[b, h, :] = sum_j softmax(score)_j * v_j.  The dot products, the bias add, the online
+ * max / sum of the softmax and P·V are fp32; scores and probabilities are never rounded to
+ * `dtype`; the result is rounded once.  A row whose keys are all masked gives zeros (HF's additive
+ * finfo.min gives the plain average of the values there).  Fixed summation order: the result is
+ * bit-reproducible and does not depend on B or on the strides.
+ * Refused with TRLX_ERR_ARG before any launch: a dtype other than TRLX_F32 / TRLX_BF16, a d_kv
+ * other than 64 / 128, a NULL q / k / v / out (self: k_new / v_new), t outside [0, max_len), a row
+ * stride below n_heads * d_kv or not a whole number of 16-byte vectors, a q / k_new / v_new / k / v
+ * / out that is not 16-byte aligned, a pointer of the other mode that is not NULL, B, n_heads or
+ * max_len < 1. */
+#define TRLX_T5_ATTN_SELF 0
+#define TRLX_T5_ATTN_CROSS 1
+typedef struct TrlxT5DecodeAttnArgs {
+    const void* q;
+    int64_t ldq;
+    const void* k_new;                /* self only */
+    int64_t ldk;
+    const void* v_new;                /* self only */
+    int64_t ldv;
+    void* k;                          /* self: the cache, column t written; cross: read only */
+    void* v;
+    const float* bias_by_distance;    /* self only: [n_heads, max_len] fp32, or NULL */
+    const int64_t* key_mask;          /* cross only: [B, S] int64, 0 = masked, or NULL */
+    void* out;                        /* [B, n_heads * d_kv] */
+    int64_t B;
+    int64_t n_heads;
+    int64_t d_kv;                     /* 64 or 128 */
+    int64_t max_len;                  /* self: cache columns; cross: S */
+    int64_t t;                        /* self: the column of the new token, kv_len = t + 1 */
+    int dtype;                        /* TRLX_F32 / TRLX_BF16: q, k_new, v_new, k, v, out */
+    int mode;                         /* TRLX_T5_ATTN_SELF / TRLX_T5_ATTN_CROSS */
+} TrlxT5DecodeAttnArgs;
+int trlx_t5_decode_attn(const TrlxT5DecodeAttnArgs* a, void* stream);
+
 /* ---------------------------------------------------------------- §8f: device-resident rollout store
  * Row copy between padded columnar [rows, W] buffers — replaces the reference's
  * `.cpu()` of the experience tensors, per-sample PPORLElement lists and the pad_sequence

@@ -37,6 +37,10 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
   ValueHead (.values), value_head, make_value_head — the bf16 value head make_head(n_embd, 1)
       fused: values and their gradient from hidden states, the [N, 2H] activation never
       written by the forward      trlx/model/nn/ppo_models.py:216-222,:618,:641
+  t5_decode_self_attention, t5_decode_cross_attention, T5DecodeKVCache, t5_relative_bias_table —
+      one decode step of a T5 decoder layer's attention over a device KV cache in one launch:
+      cache append, scores, relative-position bias, encoder key mask, fp32 softmax, P·V
+      (HF T5Attention between the projections and `o`, under generate)
   PPORolloutStorage, PPORLElement, PPORLBatch
       trlx/pipeline/ppo_pipeline.py, trlx/data/ppo_types.py (device-resident store)
   ILQLRolloutStorage (.from_samples = make_experience, .collate, .create_loader), ILQLElement
@@ -62,6 +66,8 @@ from .ilql_store import ILQLElement, ILQLRolloutStorage
 from .value_head import ValueHead, value_head, value_head_splits
 from .value_head import make_head as make_value_head
 from .sampling import PPOLogitsProcessors, ppo_sample_step
+from .t5_decode import (T5DecodeKVCache, t5_decode_cross_attention, t5_decode_self_attention,
+                        t5_relative_bias_table)
 from .control import PPOControlState
 from .step import PPOHotPath
 from .comm import RcclComm
@@ -79,6 +85,7 @@ __all__ = [
     "RcclComm", "shift_tokens_right", "get_model_inputs",
     "ValueHead", "value_head", "value_head_splits", "make_value_head",
     "FusedAdamW", "adamw_step", "clip_grad_norm_", "schedule_table",
+    "T5DecodeKVCache", "t5_decode_self_attention", "t5_decode_cross_attention", "t5_relative_bias_table",
 ]
 
 

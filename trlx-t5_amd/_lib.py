@@ -80,6 +80,19 @@ class PpoSampleProcArgs(ctypes.Structure):
     ]
 
 
+T5_ATTN_SELF, T5_ATTN_CROSS = 0, 1
+
+
+class T5DecodeAttnArgs(ctypes.Structure):
+    """Mirror of TrlxT5DecodeAttnArgs (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("q", _c_vp), ("ldq", _c_i64), ("k_new", _c_vp), ("ldk", _c_i64), ("v_new", _c_vp), ("ldv", _c_i64),
+        ("k", _c_vp), ("v", _c_vp), ("bias_by_distance", _c_vp), ("key_mask", _c_vp), ("out", _c_vp),
+        ("B", _c_i64), ("n_heads", _c_i64), ("d_kv", _c_i64), ("max_len", _c_i64), ("t", _c_i64),
+        ("dtype", _c_int), ("mode", _c_int),
+    ]
+
+
 POLYAK_MAX_TENSORS = 16
 ADAMW_MAX_TENSORS = 32
 ADAMW_CHUNK = 8192  # elements of one tensor per workgroup
@@ -254,6 +267,7 @@ SIGNATURES = {
                                         _c_vp, _c_i64, _c_int, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp,
                                         _c_i64, _c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_int, _c_vp]),
     "trlx_ppo_sample_proc": (_c_int, [ctypes.POINTER(PpoSampleProcArgs), _c_vp]),
+    "trlx_t5_decode_attn": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp]),
     "trlx_rows_copy": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                 _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_shift_tokens_right": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp]),

@@ -1,0 +1,206 @@
+"""One decode step of a T5 decoder layer's attention over a device KV cache, fused.
+
+  t5_relative_bias_table     HF's T5Attention.compute_bias for a decoder, as a [nH, max_len] fp32
+                             table indexed by the distance t - j (built once per rollout)
+  T5DecodeKVCache            k, v: [B, nH, max_len, d_kv] (HF's cache layout)
+  t5_decode_self_attention   append k_new / v_new at column t, attend over columns 0..t with the
+                             relative-position bias: one launch
+  t5_decode_cross_attention  attend over the encoder's keys under its key mask: one launch
+
+Per layer and generated token HF's eager T5Attention spends, between the projections and `o`, a
+cache append, a [B, nH, 1, t] matmul, compute_bias (arange, bucket formula, embedding lookup,
+permute), a mask add, a softmax and a second matmul.  trlx_t5_decode_attn (csrc/t5_decode_attn.hip)
+does that in one launch with one workgroup per (batch row, head): fp32 dot products, fp32 bias add,
+online fp32 softmax, fp32 P·V, one rounding.  T5 does not scale the scores by 1/sqrt(d_kv).
+Forward only: generation runs under no_grad.
+
+Kernel shapes: bfloat16 / float32 with d_kv 64 / 128.  For any other dtype or d_kv the two
+functions evaluate the same step as torch expressions (`_torch_self_attention`,
+`_torch_cross_attention`, HF's op order).
+"""
+import ctypes
+import math
+
+import torch
+
+from . import _lib
+
+__all__ = ["t5_relative_bias_table", "T5DecodeKVCache", "t5_decode_self_attention", "t5_decode_cross_attention"]
+
+KERNEL_DTYPES = (torch.bfloat16, torch.float32)
+KERNEL_D_KV = (64, 128)
+
+
+def t5_relative_bias_table(weight, max_len, num_buckets=32, max_distance=128):
+    """table[h, d] = weight[bucket(d), h] for the distances d = t - j in [0, max_len), fp32.
+
+    weight: the decoder's relative_attention_bias.weight, [num_buckets, nH].  bucket is HF's
+    unidirectional `_relative_position_bucket`, evaluated with the same float32 torch expression on
+    the weight's device, so the buckets are HF's bit for bit: exact below num_buckets / 2, then
+    logarithmic, saturating at max_distance.  The weights are frozen while generating: build it
+    once per rollout."""
+    if weight.dim() != 2 or weight.shape[0] != num_buckets:
+        raise ValueError(f"weight must be [num_buckets = {num_buckets}, nH], got {tuple(weight.shape)}")
+    if max_len < 1:
+        raise ValueError(f"max_len = {max_len}")
+    relative_position = torch.arange(max_len, dtype=torch.long, device=weight.device)
+    max_exact = num_buckets // 2
+    is_small = relative_position < max_exact
+    if_large = max_exact + (
+        torch.log(relative_position.float() / max_exact)
+        / math.log(max_distance / max_exact)
+        * (num_buckets - max_exact)
+    ).to(torch.long)
+    if_large = torch.min(if_large, torch.full_like(if_large, num_buckets - 1))
+    buckets = torch.where(is_small, relative_position, if_large)
+    return weight.detach().float()[buckets].t().contiguous()
+
+
+class T5DecodeKVCache:
+    """The self-attention cache of one decoder layer: k, v of [B, n_heads, max_len, d_kv], zeros."""
+
+    def __init__(self, B, n_heads, d_kv, max_len, dtype, device):
+        if min(B, n_heads, d_kv, max_len) < 1:
+            raise ValueError(f"B, n_heads, d_kv, max_len = {B}, {n_heads}, {d_kv}, {max_len}")
+        self.B, self.n_heads, self.d_kv, self.max_len = int(B), int(n_heads), int(d_kv), int(max_len)
+        self.k = torch.zeros(B, n_heads, max_len, d_kv, dtype=dtype, device=device)
+        self.v = torch.zeros(B, n_heads, max_len, d_kv, dtype=dtype, device=device)
+
+    @property
+    def dtype(self):
+        return self.k.dtype
+
+    @property
+    def device(self):
+        return self.k.device
+
+
+def _rows(x, name, B, nH, d):
+    """x as (tensor, row stride): [B, nH*d], [B, 1, nH*d], [B, nH, d] or [B, nH, 1, d] whose heads sit
+    d apart with unit element stride are read in place; anything else is copied once."""
+    inner = nH * d
+    if x.dim() == 4 and tuple(x.shape) == (B, nH, 1, d):
+        x = x[:, :, 0]
+    elif x.dim() == 3 and tuple(x.shape) == (B, 1, inner):
+        x = x[:, 0]
+    if x.dim() == 3 and tuple(x.shape) == (B, nH, d):
+        ok = x.stride(2) == 1 and (nH == 1 or x.stride(1) == d)
+    elif x.dim() == 2 and tuple(x.shape) == (B, inner):
+        ok = x.stride(1) == 1
+    else:
+        raise ValueError(f"{name} must be [B, nH*d_kv], [B, 1, nH*d_kv], [B, nH, d_kv] or [B, nH, 1, d_kv] with "
+                         f"B, nH, d_kv = {B}, {nH}, {d}; got {tuple(x.shape)}")
+    ld = x.stride(0)
+    vec = 16 // x.element_size()
+    if not ok or x.data_ptr() % 16 or (B > 1 and (ld < inner or ld % vec)):
+        x = x.reshape(B, inner).contiguous()
+        ld = inner
+    return x, ld
+
+
+def _check_q(q, B, nH, d, dtype, device):
+    if not isinstance(q, torch.Tensor):
+        raise TypeError(f"expected a tensor, got {type(q).__name__}")
+    if q.dtype != dtype or q.device != device:
+        raise ValueError(f"q / k_new / v_new must be {dtype} on {device} like the keys, got {q.dtype} on {q.device}")
+
+
+def _kernel_takes(dtype, d):
+    return dtype in KERNEL_DTYPES and d in KERNEL_D_KV
+
+
+def _torch_self_attention(q, k_new, v_new, cache, t, bias_table):
+    """The same step as torch expressions, HF's op order: append, matmul, bias add, fp32 softmax
+    cast back, matmul."""
+    B, nH, d = cache.B, cache.n_heads, cache.d_kv
+    cache.k[:, :, t] = k_new.reshape(B, nH, d)
+    cache.v[:, :, t] = v_new.reshape(B, nH, d)
+    scores = torch.matmul(q.reshape(B, nH, 1, d), cache.k[:, :, :t + 1].transpose(2, 3))
+    if bias_table is not None:
+        dist = torch.arange(t, -1, -1, device=scores.device)
+        scores = scores + bias_table[:, dist].to(scores.dtype)[None, :, None, :]
+    w = torch.softmax(scores.float(), dim=-1).to(scores.dtype)
+    return torch.matmul(w, cache.v[:, :, :t + 1]).reshape(B, nH * d)
+
+
+def _torch_cross_attention(q, k_enc, v_enc, key_mask):
+    B, nH, S, d = k_enc.shape
+    scores = torch.matmul(q.reshape(B, nH, 1, d), k_enc.transpose(2, 3)).float()
+    if key_mask is not None:
+        scores = scores.masked_fill(key_mask[:, None, None, :] == 0, float("-inf"))
+    w = torch.nan_to_num(torch.softmax(scores, dim=-1), nan=0.0).to(q.dtype)   # a fully masked row: zeros
+    v = v_enc if key_mask is None else v_enc.masked_fill(key_mask[:, None, :, None] == 0, 0)
+    return torch.matmul(w, v).reshape(B, nH * d)
+
+
+def t5_decode_self_attention(q, k_new, v_new, cache, t, bias_table=None):
+    """The self-attention of decode step t: k_new / v_new go to column t of `cache`, the query
+    attends over columns 0..t with score_j = q·k_j + bias_table[h, t - j].  Returns [B, nH*d_kv].
+
+    q, k_new, v_new: the projections of this token, [B, nH*d_kv], [B, 1, nH*d_kv], [B, nH, d_kv] or
+    [B, nH, 1, d_kv] (HF's transposed view); row-strided views such as the three slices of a fused
+    [B, 3*nH*d_kv] qkv projection are read in place.  t: a host int, 0 <= t < cache.max_len.
+    bias_table: t5_relative_bias_table(...) for the layer that owns the bias, or None.
+    Runs on the current stream, no host sync; only the output is allocated."""
+    if not isinstance(cache, T5DecodeKVCache):
+        raise TypeError("cache must be a T5DecodeKVCache")
+    B, nH, d = cache.B, cache.n_heads, cache.d_kv
+    t = int(t)
+    if not 0 <= t < cache.max_len:
+        raise ValueError(f"t = {t} outside [0, max_len = {cache.max_len})")
+    for x in (q, k_new, v_new):
+        _check_q(x, B, nH, d, cache.dtype, cache.device)
+    if bias_table is not None:
+        if tuple(bias_table.shape) != (nH, cache.max_len) or bias_table.dtype != torch.float32 \
+                or bias_table.device != cache.device or not bias_table.is_contiguous():
+            raise ValueError(f"bias_table must be contiguous float32 [nH, max_len] = [{nH}, {cache.max_len}] on "
+                             f"{cache.device}, got {bias_table.dtype} {tuple(bias_table.shape)}")
+    if not _kernel_takes(cache.dtype, d):
+        return _torch_self_attention(q, k_new, v_new, cache, t, bias_table)
+    _lib.require_cuda(cache.k, q, k_new, v_new)
+    (q2, ldq), (k2, ldk), (v2, ldv) = (_rows(x, n, B, nH, d) for x, n in ((q, "q"), (k_new, "k_new"), (v_new, "v_new")))
+    out = torch.empty(B, nH * d, dtype=cache.dtype, device=cache.device)
+    args = _lib.T5DecodeAttnArgs(
+        q=q2.data_ptr(), ldq=ldq, k_new=k2.data_ptr(), ldk=ldk, v_new=v2.data_ptr(), ldv=ldv,
+        k=cache.k.data_ptr(), v=cache.v.data_ptr(), bias_by_distance=_lib.ptr(bias_table), key_mask=None,
+        out=out.data_ptr(), B=B, n_heads=nH, d_kv=d, max_len=cache.max_len, t=t,
+        dtype=_lib.dtype_code(cache.k), mode=_lib.T5_ATTN_SELF)
+    _lib.call("trlx_t5_decode_attn", ctypes.byref(args), _lib.stream_of(out))
+    return out
+
+
+def t5_decode_cross_attention(q, k_enc, v_enc, key_mask=None):
+    """The cross-attention of a decode step: score_j = q·k_enc_j over the keys with
+    key_mask[b, j] != 0.  Returns [B, nH*d_kv].
+
+    k_enc, v_enc: the encoder's projected keys / values, contiguous [B, nH, S, d_kv] (make HF's
+    transposed view contiguous once per rollout).  key_mask: int64 [B, S], 0 = masked (the
+    encoder's attention_mask; holes allowed), or None.  Masked keys are excluded from the softmax
+    and not read; a row with every key masked returns zeros, where HF's additive finfo.min mask
+    returns the plain average of the values.  q as in t5_decode_self_attention.
+    Runs on the current stream, no host sync; only the output is allocated."""
+    if k_enc.dim() != 4 or k_enc.shape != v_enc.shape or k_enc.dtype != v_enc.dtype or k_enc.device != v_enc.device:
+        raise ValueError("k_enc and v_enc must be [B, nH, S, d_kv] of one dtype on one device")
+    B, nH, S, d = k_enc.shape
+    if min(B, nH, S) < 1:
+        raise ValueError(f"k_enc holds no key: shape {tuple(k_enc.shape)}")
+    _check_q(q, B, nH, d, k_enc.dtype, k_enc.device)
+    if key_mask is not None:
+        if tuple(key_mask.shape) != (B, S) or key_mask.dtype != torch.int64 or key_mask.device != k_enc.device:
+            raise ValueError(f"key_mask must be int64 [B, S] = [{B}, {S}] on {k_enc.device}, got {key_mask.dtype} "
+                             f"{tuple(key_mask.shape)}")
+    if not _kernel_takes(k_enc.dtype, d):
+        return _torch_cross_attention(q, k_enc, v_enc, key_mask)
+    _lib.require_cuda(k_enc, q)
+    if not (k_enc.is_contiguous() and v_enc.is_contiguous()):
+        raise ValueError("k_enc and v_enc must be contiguous [B, nH, S, d_kv]: call .contiguous() once per rollout")
+    if key_mask is not None and not key_mask.is_contiguous():
+        key_mask = key_mask.contiguous()
+    q2, ldq = _rows(q, "q", B, nH, d)
+    out = torch.empty(B, nH * d, dtype=k_enc.dtype, device=k_enc.device)
+    args = _lib.T5DecodeAttnArgs(
+        q=q2.data_ptr(), ldq=ldq, k_new=None, ldk=0, v_new=None, ldv=0, k=k_enc.data_ptr(), v=v_enc.data_ptr(),
+        bias_by_distance=None, key_mask=_lib.ptr(key_mask), out=out.data_ptr(), B=B, n_heads=nH, d_kv=d,
+        max_len=S, t=0, dtype=_lib.dtype_code(k_enc), mode=_lib.T5_ATTN_CROSS)
+    _lib.call("trlx_t5_decode_attn", ctypes.byref(args), _lib.stream_of(out))
+    return out
