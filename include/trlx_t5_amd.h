@@ -981,6 +981,63 @@ typedef struct TrlxT5DecodeAttnArgs {
 } TrlxT5DecodeAttnArgs;
 int trlx_t5_decode_attn(const TrlxT5DecodeAttnArgs* a, void* stream);
 
+/* ---------------------------------------------------------------- T5 full-sequence attention
+ * Many queries against many keys under T5's rules, forward only — replaces the body of HF's
+ * T5Attention between the q / k / v projections and the `o` projection (a [B, nH, Tq, S] matmul,
+ * compute_bias, the additive mask, an fp32 softmax cast back, a second matmul) with ONE launch
+ * that never holds a [Tq, S] tensor: a flash-attention forward on gfx950 MFMA, one workgroup per
+ * (batch row, head, block of query rows).  bf16 only, d_kv 64 or 128.
+ *   score[i, j] = q_i · k_j + bias_by_offset[h, (j - i) + (Tq - 1)]        (no 1/sqrt(d) scaling)
+ *   out[b, i, h, :] = sum_j softmax_j(score[i, :]) * v_j   over the keys j that are not excluded
+ *   q        : [B, Tq, n_heads, d_kv] as a base pointer + element strides for batch, position and
+ *              head; the element stride is 1.  k, v: [B, S, n_heads, d_kv] likewise.  So a
+ *              [B, T, nH * d] projection output (strides T*nH*d, nH*d, d), a slice of a fused
+ *              [B, T, 3 * nH * d] projection and the cache layout [B, nH, S, d] (strides nH*S*d, d,
+ *              S*d) are all read in place.  The stride of a dimension of size 1 is not read.
+ *   out      : [B, Tq, n_heads, d_kv] with strides of its own; [B, Tq, nH * d] is what `o` takes.
+ *   bias_by_offset : fp32 [n_heads, Tq + S - 1], contiguous, indexed by key position minus query
+ *              position plus Tq - 1, or NULL (no bias).  Looked up inside the kernel.
+ *   key_mask : int64 [B, S], contiguous, or NULL.  A key with key_mask[b, j] == 0 is excluded; its
+ *              K and V rows are not read (they may hold anything, NaN included); a tile of keys
+ *              with no live key is skipped.
+ *   causal   : non-zero excludes the keys j > i and needs Tq == S; tiles of keys wholly above a
+ *              block's last query are not read.
+ * Both products run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; the scores, the bias add
+ * and the online max / sum are fp32 and never rounded; P is rounded to bf16 un-normalised as the
+ * P·V operand; O is rescaled in fp32 and rounded once at the end.  A query whose keys are all
+ * excluded gives zeros (HF's additive finfo.min gives the plain average of the values there).
+ * Tq and S may be any value >= 1: nothing outside [0, Tq) x [0, S) is read or written.  The
+ * summation order depends on (d_kv, Tq, S, the flags, the mask row) only: the result is
+ * bit-reproducible and does not depend on B or on the strides.
+ * Refused with TRLX_ERR_ARG before any launch, `out` untouched: a dtype other than TRLX_BF16, a
+ * d_kv other than 64 / 128, a NULL q / k / v / out, a base that is not 16-byte aligned, a stride
+ * that is negative or no multiple of 8 elements, a position or head stride below d_kv, out rows
+ * that overlap, causal with Tq != S, B, n_heads, Tq or S outside [1, 2^30], more than 2^31 - 1
+ * workgroups, an operand whose last element lies beyond 2^61 elements from its base.
+ * trlx_t5_attention_tiles reports the kernel's tile sizes (query rows per workgroup, keys per
+ * LDS tile); either pointer may be NULL. */
+typedef struct TrlxT5AttentionArgs {
+    const void* q;
+    int64_t q_stride_b, q_stride_t, q_stride_h;
+    const void* k;
+    int64_t k_stride_b, k_stride_t, k_stride_h;
+    const void* v;
+    int64_t v_stride_b, v_stride_t, v_stride_h;
+    void* out;
+    int64_t o_stride_b, o_stride_t, o_stride_h;
+    const float* bias_by_offset;      /* [n_heads, Tq + S - 1] fp32, or NULL */
+    const int64_t* key_mask;          /* [B, S] int64, 0 = excluded, or NULL */
+    int64_t B;
+    int64_t n_heads;
+    int64_t d_kv;                     /* 64 or 128 */
+    int64_t Tq;
+    int64_t S;
+    int dtype;                        /* TRLX_BF16 */
+    int causal;
+} TrlxT5AttentionArgs;
+int trlx_t5_attention(const TrlxT5AttentionArgs* a, void* stream);
+int trlx_t5_attention_tiles(int* q_tile, int* kv_tile);
+
 /* ---------------------------------------------------------------- §8f: device-resident rollout store
  * Row copy between padded columnar [rows, W] buffers — replaces the reference's
  * `.cpu()` of the experience tensors, per-sample PPORLElement lists and the pad_sequence

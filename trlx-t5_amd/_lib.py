@@ -93,6 +93,19 @@ class T5DecodeAttnArgs(ctypes.Structure):
     ]
 
 
+class T5AttentionArgs(ctypes.Structure):
+    """Mirror of TrlxT5AttentionArgs (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("q", _c_vp), ("q_stride_b", _c_i64), ("q_stride_t", _c_i64), ("q_stride_h", _c_i64),
+        ("k", _c_vp), ("k_stride_b", _c_i64), ("k_stride_t", _c_i64), ("k_stride_h", _c_i64),
+        ("v", _c_vp), ("v_stride_b", _c_i64), ("v_stride_t", _c_i64), ("v_stride_h", _c_i64),
+        ("out", _c_vp), ("o_stride_b", _c_i64), ("o_stride_t", _c_i64), ("o_stride_h", _c_i64),
+        ("bias_by_offset", _c_vp), ("key_mask", _c_vp),
+        ("B", _c_i64), ("n_heads", _c_i64), ("d_kv", _c_i64), ("Tq", _c_i64), ("S", _c_i64),
+        ("dtype", _c_int), ("causal", _c_int),
+    ]
+
+
 POLYAK_MAX_TENSORS = 16
 ADAMW_MAX_TENSORS = 32
 ADAMW_CHUNK = 8192  # elements of one tensor per workgroup
@@ -268,6 +281,8 @@ SIGNATURES = {
                                         _c_i64, _c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_int, _c_vp]),
     "trlx_ppo_sample_proc": (_c_int, [ctypes.POINTER(PpoSampleProcArgs), _c_vp]),
     "trlx_t5_decode_attn": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp]),
+    "trlx_t5_attention": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp]),
+    "trlx_t5_attention_tiles": (_c_int, [ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),
     "trlx_rows_copy": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                 _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_shift_tokens_right": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp]),
