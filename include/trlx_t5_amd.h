@@ -1038,6 +1038,90 @@ typedef struct TrlxT5AttentionArgs {
 int trlx_t5_attention(const TrlxT5AttentionArgs* a, void* stream);
 int trlx_t5_attention_tiles(int* q_tile, int* kv_tile);
 
+/* The same launch, keeping the row statistics the backward needs.  `out` is bit-identical to
+ * trlx_t5_attention's on the same arguments (the same kernel, one more store per query), and the
+ * refusals are the same, plus a NULL or misaligned `lse`.
+ *   lse : fp32 [B, n_heads, Tq], contiguous.  lse[b, h, i] = m_i + log(l_i) (natural log), m_i the
+ *         largest live score of query i and l_i = sum_j exp(score[i, j] - m_i) over its live keys,
+ *         so that exp(score[i, j] - lse) is the softmax weight.  A query with no live key gets +inf:
+ *         exp(s - lse) is then 0 for every s and the backward gives it zero gradients. */
+int trlx_t5_attention_fwd_lse(const TrlxT5AttentionArgs* a, float* lse, void* stream);
+
+/* ---------------------------------------------------------------- T5 full-sequence attention, backward
+ * The gradients of trlx_t5_attention (no dropout: the reference trains with dropout off) from
+ * q, k, v, out, lse and dout, holding nothing of size Tq x S.  bf16 only, d_kv 64 or 128, both
+ * products and their transposes on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  With
+ * s = q_i · k_j + bias (unscaled) over the keys that are not excluded:
+ *   P = exp(s - lse)      delta_i = sum_d dout_i · out_i      dP = dout · v^T      dS = P (dP - delta)
+ *   dv = P^T · dout       dk = dS^T · q                       dq = dS · k
+ *   dbias[h, (j - i) + Tq - 1] = sum over b and the live (i, j) of dS[b, h, i, j]
+ * P and dS are fp32 and rounded to bf16 only as MFMA operands; dq, dk, dv are rounded once.
+ * Three launches: delta (a row kernel), dk / dv (one workgroup per batch row, head and block of
+ * keys, walking the queries), dq (one workgroup per batch row, head and block of queries, walking
+ * the keys; it also sums dbias).  The scores are recomputed in both walks: dq, dk and dv use no
+ * global atomics, their summation order depends on (d_kv, Tq, S, the flags, the mask row) only, so
+ * they are bit-reproducible run to run and do not depend on B or on the strides.
+ *   q, k, v, out, dout : as in TrlxT5AttentionArgs, base pointer + element strides for batch,
+ *              position and head, read in place (dout: [B, Tq, n_heads, d_kv]).
+ *   dq, dk, dv : written with three strides of their own each, shaped like q, k, v; e.g. the three
+ *              slices of one fused [B, T, 3 * nH * d] gradient buffer.
+ *   lse      : trlx_t5_attention_fwd_lse's, fp32 [B, n_heads, Tq], contiguous.
+ *   bias_by_offset, key_mask, causal : the forward's.  The K and V rows of excluded keys are not
+ *              read; their dk and dv rows are written as exact zeros.  Tiles with no live key and
+ *              tiles above the causal diagonal are skipped.  dq of a query with no live key is
+ *              exact zeros.  Nothing outside [0, Tq) x [0, S) is read or written, Tq, S >= 1.
+ *   dbias    : fp32 [n_heads, Tq + S - 1], contiguous, or NULL (not computed, nothing paid: the
+ *              bias belongs to a frozen layer).  The call zeroes it, then accumulates with LDS and
+ *              global fp32 atomics: dbias is NOT bit-reproducible (dq, dk, dv are the same bits
+ *              with and without it).  It may be given without bias_by_offset (the bias is 0 then).
+ *   workspace : trlx_t5_attention_bwd_workspace_bytes(B, n_heads, Tq) bytes (delta, fp32
+ *              [B, n_heads, Tq]; it does not grow with S), 4-byte aligned; -1 for sizes out of range.
+ * Refused with TRLX_ERR_ARG before any launch, every output untouched: the forward's list (for
+ * out as a read operand), a NULL dout / lse / dq / dk / dv, a misaligned base, dq / dk / dv rows
+ * that overlap within one of them, a dq / dk / dv that shares an element with another of them or
+ * with q / k / v / out / dout (operands whose address ranges interleave, such as the slices of one
+ * fused buffer, are told apart exactly when their sizes and strides are equal and refused
+ * otherwise), a missing or short workspace.  dbias, lse and the workspace are the caller's to keep
+ * apart from the rest.
+ * trlx_t5_attention_bwd_tiles reports the tiles: the dq kernel's query rows per workgroup and keys
+ * per LDS tile, the dk / dv kernel's keys per workgroup and query rows per LDS tile; any pointer
+ * may be NULL.  Not built: dropout, fp32 / fp16, other d_kv, causal with a cached prefix, a double
+ * backward, a single-kernel backward with atomically accumulated dq. */
+typedef struct TrlxT5AttentionBwdArgs {
+    const void* q;
+    int64_t q_stride_b, q_stride_t, q_stride_h;
+    const void* k;
+    int64_t k_stride_b, k_stride_t, k_stride_h;
+    const void* v;
+    int64_t v_stride_b, v_stride_t, v_stride_h;
+    const void* out;
+    int64_t o_stride_b, o_stride_t, o_stride_h;
+    const void* dout;
+    int64_t do_stride_b, do_stride_t, do_stride_h;
+    void* dq;
+    int64_t dq_stride_b, dq_stride_t, dq_stride_h;
+    void* dk;
+    int64_t dk_stride_b, dk_stride_t, dk_stride_h;
+    void* dv;
+    int64_t dv_stride_b, dv_stride_t, dv_stride_h;
+    const float* lse;                 /* [B, n_heads, Tq] fp32 */
+    const float* bias_by_offset;      /* [n_heads, Tq + S - 1] fp32, or NULL */
+    const int64_t* key_mask;          /* [B, S] int64, 0 = excluded, or NULL */
+    float* dbias;                     /* [n_heads, Tq + S - 1] fp32, or NULL */
+    void* workspace;
+    int64_t workspace_bytes;
+    int64_t B;
+    int64_t n_heads;
+    int64_t d_kv;                     /* 64 or 128 */
+    int64_t Tq;
+    int64_t S;
+    int dtype;                        /* TRLX_BF16 */
+    int causal;
+} TrlxT5AttentionBwdArgs;
+int trlx_t5_attention_bwd(const TrlxT5AttentionBwdArgs* a, void* stream);
+int64_t trlx_t5_attention_bwd_workspace_bytes(int64_t B, int64_t n_heads, int64_t Tq);
+int trlx_t5_attention_bwd_tiles(int* dq_q_tile, int* dq_kv_tile, int* dkv_k_tile, int* dkv_q_tile);
+
 /* ---------------------------------------------------------------- §8f: device-resident rollout store
  * Row copy between padded columnar [rows, W] buffers — replaces the reference's
  * `.cpu()` of the experience tensors, per-sample PPORLElement lists and the pad_sequence

@@ -45,6 +45,8 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
       self-attention, teacher-forced decoder self- and cross-attention) as one flash-attention
       launch on MFMA: bias, key mask and causal rule inside, no [Tq, S] tensor
       (HF T5Attention between the projections and `o`, ppo_orchestrator.py:119-130)
+  t5_attention_train, t5_relative_bias_buckets — the same attention under autograd for the PPO
+      update: MFMA backward for dq, dk, dv and the bias table, nothing of size [Tq, S] saved
   PPORolloutStorage, PPORLElement, PPORLBatch
       trlx/pipeline/ppo_pipeline.py, trlx/data/ppo_types.py (device-resident store)
   ILQLRolloutStorage (.from_samples = make_experience, .collate, .create_loader), ILQLElement
@@ -72,7 +74,7 @@ from .value_head import make_head as make_value_head
 from .sampling import PPOLogitsProcessors, ppo_sample_step
 from .t5_decode import (T5DecodeKVCache, t5_decode_cross_attention, t5_decode_self_attention,
                         t5_relative_bias_table)
-from .t5_attention import t5_attention, t5_relative_bias_offsets
+from .t5_attention import t5_attention, t5_attention_train, t5_relative_bias_buckets, t5_relative_bias_offsets
 from .control import PPOControlState
 from .step import PPOHotPath
 from .comm import RcclComm
@@ -91,7 +93,7 @@ __all__ = [
     "ValueHead", "value_head", "value_head_splits", "make_value_head",
     "FusedAdamW", "adamw_step", "clip_grad_norm_", "schedule_table",
     "T5DecodeKVCache", "t5_decode_self_attention", "t5_decode_cross_attention", "t5_relative_bias_table",
-    "t5_attention", "t5_relative_bias_offsets",
+    "t5_attention", "t5_relative_bias_offsets", "t5_attention_train", "t5_relative_bias_buckets",
 ]
 
 

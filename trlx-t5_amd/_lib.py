@@ -106,6 +106,24 @@ class T5AttentionArgs(ctypes.Structure):
     ]
 
 
+class T5AttentionBwdArgs(ctypes.Structure):
+    """Mirror of TrlxT5AttentionBwdArgs (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("q", _c_vp), ("q_stride_b", _c_i64), ("q_stride_t", _c_i64), ("q_stride_h", _c_i64),
+        ("k", _c_vp), ("k_stride_b", _c_i64), ("k_stride_t", _c_i64), ("k_stride_h", _c_i64),
+        ("v", _c_vp), ("v_stride_b", _c_i64), ("v_stride_t", _c_i64), ("v_stride_h", _c_i64),
+        ("out", _c_vp), ("o_stride_b", _c_i64), ("o_stride_t", _c_i64), ("o_stride_h", _c_i64),
+        ("dout", _c_vp), ("do_stride_b", _c_i64), ("do_stride_t", _c_i64), ("do_stride_h", _c_i64),
+        ("dq", _c_vp), ("dq_stride_b", _c_i64), ("dq_stride_t", _c_i64), ("dq_stride_h", _c_i64),
+        ("dk", _c_vp), ("dk_stride_b", _c_i64), ("dk_stride_t", _c_i64), ("dk_stride_h", _c_i64),
+        ("dv", _c_vp), ("dv_stride_b", _c_i64), ("dv_stride_t", _c_i64), ("dv_stride_h", _c_i64),
+        ("lse", _c_vp), ("bias_by_offset", _c_vp), ("key_mask", _c_vp), ("dbias", _c_vp),
+        ("workspace", _c_vp), ("workspace_bytes", _c_i64),
+        ("B", _c_i64), ("n_heads", _c_i64), ("d_kv", _c_i64), ("Tq", _c_i64), ("S", _c_i64),
+        ("dtype", _c_int), ("causal", _c_int),
+    ]
+
+
 POLYAK_MAX_TENSORS = 16
 ADAMW_MAX_TENSORS = 32
 ADAMW_CHUNK = 8192  # elements of one tensor per workgroup
@@ -283,6 +301,10 @@ SIGNATURES = {
     "trlx_t5_decode_attn": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp]),
     "trlx_t5_attention": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp]),
     "trlx_t5_attention_tiles": (_c_int, [ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),
+    "trlx_t5_attention_fwd_lse": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp, _c_vp]),
+    "trlx_t5_attention_bwd": (_c_int, [ctypes.POINTER(T5AttentionBwdArgs), _c_vp]),
+    "trlx_t5_attention_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "trlx_t5_attention_bwd_tiles": (_c_int, [ctypes.POINTER(_c_int)] * 4),
     "trlx_rows_copy": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                 _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_shift_tokens_right": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp]),

@@ -22,7 +22,9 @@
 // skips the tiles above its own last query.
 #include <climits>
 
-#include "common.h"
+#include <type_traits>
+
+#include "t5_attention.h"
 
 namespace trlx {
 
@@ -30,12 +32,6 @@ constexpr int kTaThreads = 256;
 constexpr int kTaQTile = 128;   // query rows per workgroup (32 per wave)
 constexpr int kTaKVTile = 64;   // keys per LDS tile
 constexpr int kTaBiasWin = kTaQTile + kTaKVTile;   // offsets (key - query) a tile can meet, rounded up
-
-enum { kTaBias = 1, kTaMask = 2, kTaCausal = 4 };
-
-typedef __bf16 ta_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short ta_s16x4 __attribute__((ext_vector_type(4)));
-typedef float ta_f32x16 __attribute__((ext_vector_type(16)));
 
 struct TaArgs {
     const uint16_t* q;
@@ -48,13 +44,13 @@ struct TaArgs {
     int nH, Tq, S, nqb;
 };
 
-__device__ __forceinline__ ta_s16x4 ta_tr_read(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) ta_s16x4*)(p));
-}
+// the same arguments plus the row statistics' destination (trlx_t5_attention_fwd_lse)
+struct TaArgsLse : TaArgs {
+    float* lse;            // [B, nH, Tq] fp32
+};
 
-template <int DKV, int FLAGS>
-__global__ __launch_bounds__(kTaThreads, 2) void k_t5_attention(const TaArgs a) {
+template <int DKV, int FLAGS, bool LSE = false>
+__global__ __launch_bounds__(kTaThreads, 2) void k_t5_attention(const std::conditional_t<LSE, TaArgsLse, TaArgs> a) {
     constexpr bool BIAS = FLAGS & kTaBias, MASK = FLAGS & kTaMask, CAUSAL = FLAGS & kTaCausal;
     constexpr int CPR = DKV / 8;                            // 16-byte chunks per row
     constexpr int NC = kTaKVTile * CPR / kTaThreads;        // chunks per thread and operand
@@ -259,6 +255,9 @@ __global__ __launch_bounds__(kTaThreads, 2) void k_t5_attention(const TaArgs a) 
     // normalise, round once, stage the wave's 32 rows in LDS and store whole rows
     l += __shfl_xor(l, 32, kWave);
     const bool any = l > 0.f || l != l;   // no live key at all: zeros
+    if constexpr (LSE) {   // m + log(l), what the backward rebuilds P from; +inf makes its exp(s - lse) zero
+        if (hh == 0 && qg < a.Tq) a.lse[(int64_t(b) * a.nH + h) * a.Tq + qg] = any ? m + logf(l) : INFINITY;
+    }
     unsigned char* sO = smem + wave * 32 * OS;
 #pragma unroll
     for (int db = 0; db < DB; ++db)
@@ -284,53 +283,18 @@ __global__ __launch_bounds__(kTaThreads, 2) void k_t5_attention(const TaArgs a) 
     }
 }
 
-typedef void (*ta_kernel_t)(const TaArgs);
-template <int DKV>
-static ta_kernel_t ta_pick_flags(int flags) {
+template <int DKV, bool LSE>
+static auto ta_pick_flags(int flags) -> void (*)(const std::conditional_t<LSE, TaArgsLse, TaArgs>) {
     switch (flags) {
-        case 0: return k_t5_attention<DKV, 0>;
-        case 1: return k_t5_attention<DKV, 1>;
-        case 2: return k_t5_attention<DKV, 2>;
-        case 3: return k_t5_attention<DKV, 3>;
-        case 4: return k_t5_attention<DKV, 4>;
-        case 5: return k_t5_attention<DKV, 5>;
-        case 6: return k_t5_attention<DKV, 6>;
-        default: return k_t5_attention<DKV, 7>;
+        case 0: return k_t5_attention<DKV, 0, LSE>;
+        case 1: return k_t5_attention<DKV, 1, LSE>;
+        case 2: return k_t5_attention<DKV, 2, LSE>;
+        case 3: return k_t5_attention<DKV, 3, LSE>;
+        case 4: return k_t5_attention<DKV, 4, LSE>;
+        case 5: return k_t5_attention<DKV, 5, LSE>;
+        case 6: return k_t5_attention<DKV, 6, LSE>;
+        default: return k_t5_attention<DKV, 7, LSE>;
     }
-}
-
-static bool ta_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// one operand's strides: whole 16-byte vectors, rows of d_kv elements that do not overlap, and the
-// last element's offset (returned through *span) within the kernel's int64 arithmetic
-static bool ta_strides_ok(int64_t B, int64_t T, int64_t nH, int64_t d, int64_t sb, int64_t st, int64_t sh, bool dense,
-                          int64_t* span) {
-    const int64_t n[3] = {B, T, nH};
-    const int64_t s[3] = {sb, st, sh};
-    int64_t total = d - 1;
-    for (int i = 0; i < 3; ++i) {
-        if (n[i] == 1) continue;   // a single index has no stride to speak of
-        if (s[i] % 8 != 0 || s[i] < 0) return false;
-        if (i > 0 && s[i] < d) return false;
-        int64_t ext;
-        if (__builtin_mul_overflow(n[i] - 1, s[i], &ext) || __builtin_add_overflow(total, ext, &total)) return false;
-    }
-    if (total > (int64_t(1) << 61)) return false;
-    if (dense) {   // written: no two (b, t, h) rows may share an element
-        int order[3] = {0, 1, 2};
-        for (int i = 0; i < 3; ++i)
-            for (int j = i + 1; j < 3; ++j)
-                if (s[order[j]] < s[order[i]]) std::swap(order[i], order[j]);
-        int64_t need = d;
-        for (int i = 0; i < 3; ++i) {
-            const int x = order[i];
-            if (n[x] == 1) continue;
-            if (s[x] < need) return false;
-            need = s[x] * n[x];
-        }
-    }
-    *span = total;
-    return true;
 }
 
 }  // namespace trlx
@@ -343,8 +307,11 @@ extern "C" int trlx_t5_attention_tiles(int* q_tile, int* kv_tile) {
     return TRLX_OK;
 }
 
-extern "C" int trlx_t5_attention(const TrlxT5AttentionArgs* a, void* stream) {
+// the checks and the launch of both entries; with_lse picks the instantiations that also write lse
+static int ta_forward(const TrlxT5AttentionArgs* a, float* lse, bool with_lse, void* stream) {
     TRLX_REQUIRE(a, TRLX_ERR_ARG, "t5 attention: NULL arguments");
+    TRLX_REQUIRE(!with_lse || (lse && (reinterpret_cast<uintptr_t>(lse) & 3u) == 0), TRLX_ERR_ARG,
+                 "t5 attention: lse is NULL or not aligned to 4 bytes");
     TRLX_REQUIRE(a->dtype == TRLX_BF16, TRLX_ERR_ARG, "t5 attention: dtype %d (bf16 only)", a->dtype);
     TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128, TRLX_ERR_ARG, "t5 attention: d_kv %lld (64 and 128 only)",
                  (long long)a->d_kv);
@@ -406,7 +373,23 @@ extern "C" int trlx_t5_attention(const TrlxT5AttentionArgs* a, void* stream) {
     k.S = int(a->S);
     k.nqb = int(nqb);
     const int flags = (a->bias_by_offset ? kTaBias : 0) | (a->key_mask ? kTaMask : 0) | (a->causal ? kTaCausal : 0);
-    ta_kernel_t fn = a->d_kv == 64 ? ta_pick_flags<64>(flags) : ta_pick_flags<128>(flags);
-    hipLaunchKernelGGL(fn, dim3(unsigned(grid)), dim3(kTaThreads), 0, (hipStream_t)stream, k);
+    if (with_lse) {
+        TaArgsLse kl;
+        static_cast<TaArgs&>(kl) = k;
+        kl.lse = lse;
+        auto fn = a->d_kv == 64 ? ta_pick_flags<64, true>(flags) : ta_pick_flags<128, true>(flags);
+        hipLaunchKernelGGL(fn, dim3(unsigned(grid)), dim3(kTaThreads), 0, (hipStream_t)stream, kl);
+    } else {
+        auto fn = a->d_kv == 64 ? ta_pick_flags<64, false>(flags) : ta_pick_flags<128, false>(flags);
+        hipLaunchKernelGGL(fn, dim3(unsigned(grid)), dim3(kTaThreads), 0, (hipStream_t)stream, k);
+    }
     return check_launch("k_t5_attention");
+}
+
+extern "C" int trlx_t5_attention(const TrlxT5AttentionArgs* a, void* stream) {
+    return ta_forward(a, nullptr, false, stream);
+}
+
+extern "C" int trlx_t5_attention_fwd_lse(const TrlxT5AttentionArgs* a, float* lse, void* stream) {
+    return ta_forward(a, lse, true, stream);
 }
