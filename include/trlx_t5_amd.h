@@ -1122,6 +1122,65 @@ int trlx_t5_attention_bwd(const TrlxT5AttentionBwdArgs* a, void* stream);
 int64_t trlx_t5_attention_bwd_workspace_bytes(int64_t B, int64_t n_heads, int64_t Tq);
 int trlx_t5_attention_bwd_tiles(int* dq_q_tile, int* dq_kv_tile, int* dkv_k_tile, int* dkv_q_tile);
 
+/* ---------------------------------------------------------------- T5 feed-forward activation
+ * What sits between the projections of HF's T5LayerFF, forward and backward, one launch each:
+ *   forward   out[n, f] = act(u[n, f]) * v[n, f]        (T5DenseGatedActDense: u = wi_0(x), v = wi_1(x))
+ *             out[n, f] = act(u[n, f])                  with v NULL (T5DenseActDense)
+ *   backward  du = dy * v * act'(u)     dv = dy * act(u)     (du = dy * act'(u) with v NULL)
+ * act: TRLX_T5_ACT_RELU, TRLX_T5_ACT_GELU_NEW (0.5 u (1 + tanh(sqrt(2/pi) (u + 0.044715 u^3))), HF's
+ * `gelu_new`, what `gated-gelu` maps to; not the erf GELU) or TRLX_T5_ACT_SILU.  TRLX_F32 or TRLX_BF16,
+ * one dtype for every operand; all arithmetic in fp32, every output rounded once.  gelu_new and silu
+ * are evaluated as u * sigmoid(x) (x = u, or 2 sqrt(2/pi) (u + 0.044715 u^3)) from e = exp(-|x|):
+ * nothing cancels, every finite input gives a finite output and derivative (1 towards +inf, 0
+ * towards -inf), a NaN element gives NaN in that element only.  relu'(0) = 0.  The backward
+ * recomputes act(u); it reads dy, u and v and nothing else.
+ *   u, v, out, dy, du, dv : rows of F elements with element stride 1 and a row stride (in elements)
+ *             of their own each, ld_* >= F (checked for every N): the halves of a packed [N, 2F]
+ *             projection output are read in place, du and dv can be the halves of one [N, 2F]
+ *             gradient.  The forward takes u, v, out; the backward u, v, dy, du, dv.
+ *   du, dv  : either may be NULL (not computed, nothing paid), not both; dv needs v; with du NULL
+ *             v is not read.
+ * 16-byte accesses when every base pointer of the call is 16-byte aligned and F and every row
+ * stride are multiples of the vector width (8 bf16, 4 fp32); element accesses otherwise.  The two
+ * forms give the same bits.  No workspace, no atomics: bit-reproducible.  N == 0 is a success with
+ * no launch.
+ * Refused before any launch, every output untouched: NULL args, a NULL u / out (forward) or
+ * u / dy (backward), du and dv both NULL, dv without v (TRLX_ERR_ARG); F <= 0, N < 0, sizes past
+ * the grid (TRLX_ERR_SHAPE); a row stride below F (TRLX_ERR_STRIDE); a dtype other than the two
+ * (TRLX_ERR_DTYPE); an unknown act, a pointer not aligned to its element, a written operand that
+ * shares an element with any other operand (TRLX_ERR_ARG; operands whose address ranges interleave,
+ * such as the halves of one packed buffer, are told apart exactly when their row strides are equal
+ * and refused otherwise, the rule of trlx_t5_attention_bwd).
+ * trlx_t5_ff_act_geometry reports the vector widths and the block of columns and rows one
+ * workgroup takes; any pointer may be NULL.  Not built: the erf GELU, fp16, dropout, the
+ * projections themselves. */
+typedef enum {
+    TRLX_T5_ACT_RELU = 0,
+    TRLX_T5_ACT_GELU_NEW = 1,
+    TRLX_T5_ACT_SILU = 2,
+} trlx_t5_act;
+typedef struct TrlxT5FfActArgs {
+    const void* u;
+    int64_t ld_u;
+    const void* v;                    /* NULL = not gated */
+    int64_t ld_v;
+    void* out;                        /* forward only */
+    int64_t ld_out;
+    const void* dy;                   /* backward only */
+    int64_t ld_dy;
+    void* du;                         /* backward only, or NULL */
+    int64_t ld_du;
+    void* dv;                         /* backward only, or NULL */
+    int64_t ld_dv;
+    int64_t N;
+    int64_t F;
+    int dtype;                        /* TRLX_F32 / TRLX_BF16 */
+    int act;                          /* trlx_t5_act */
+} TrlxT5FfActArgs;
+int trlx_t5_ff_act_fwd(const TrlxT5FfActArgs* a, void* stream);
+int trlx_t5_ff_act_bwd(const TrlxT5FfActArgs* a, void* stream);
+int trlx_t5_ff_act_geometry(int* vec_bf16, int* vec_f32, int* cols_per_block, int* rows_per_block);
+
 /* ---------------------------------------------------------------- §8f: device-resident rollout store
  * Row copy between padded columnar [rows, W] buffers — replaces the reference's
  * `.cpu()` of the experience tensors, per-sample PPORLElement lists and the pad_sequence

@@ -47,6 +47,10 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
       (HF T5Attention between the projections and `o`, ppo_orchestrator.py:119-130)
   t5_attention_train, t5_relative_bias_buckets — the same attention under autograd for the PPO
       update: MFMA backward for dq, dk, dv and the bias table, nothing of size [Tq, S] saved
+  t5_ff_act, t5_ff_act_packed, T5FeedForward — the other half of a T5 layer: act(wi_0 x) * wi_1 x
+      (gelu_new / silu / relu, gated or not) in one launch between the projections, fp32 arithmetic
+      with one rounding, and a one-launch backward that saves u and v alone
+      (HF T5DenseGatedActDense / T5DenseActDense)
   PPORolloutStorage, PPORLElement, PPORLBatch
       trlx/pipeline/ppo_pipeline.py, trlx/data/ppo_types.py (device-resident store)
   ILQLRolloutStorage (.from_samples = make_experience, .collate, .create_loader), ILQLElement
@@ -75,6 +79,7 @@ from .sampling import PPOLogitsProcessors, ppo_sample_step
 from .t5_decode import (T5DecodeKVCache, t5_decode_cross_attention, t5_decode_self_attention,
                         t5_relative_bias_table)
 from .t5_attention import t5_attention, t5_attention_train, t5_relative_bias_buckets, t5_relative_bias_offsets
+from .t5_ff import T5FeedForward, t5_ff_act, t5_ff_act_packed
 from .control import PPOControlState
 from .step import PPOHotPath
 from .comm import RcclComm
@@ -94,6 +99,7 @@ __all__ = [
     "FusedAdamW", "adamw_step", "clip_grad_norm_", "schedule_table",
     "T5DecodeKVCache", "t5_decode_self_attention", "t5_decode_cross_attention", "t5_relative_bias_table",
     "t5_attention", "t5_relative_bias_offsets", "t5_attention_train", "t5_relative_bias_buckets",
+    "t5_ff_act", "t5_ff_act_packed", "T5FeedForward",
 ]
 
 

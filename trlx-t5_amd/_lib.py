@@ -124,6 +124,18 @@ class T5AttentionBwdArgs(ctypes.Structure):
     ]
 
 
+T5_ACT_RELU, T5_ACT_GELU_NEW, T5_ACT_SILU = 0, 1, 2
+
+
+class T5FfActArgs(ctypes.Structure):
+    """Mirror of TrlxT5FfActArgs (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("u", _c_vp), ("ld_u", _c_i64), ("v", _c_vp), ("ld_v", _c_i64), ("out", _c_vp), ("ld_out", _c_i64),
+        ("dy", _c_vp), ("ld_dy", _c_i64), ("du", _c_vp), ("ld_du", _c_i64), ("dv", _c_vp), ("ld_dv", _c_i64),
+        ("N", _c_i64), ("F", _c_i64), ("dtype", _c_int), ("act", _c_int),
+    ]
+
+
 POLYAK_MAX_TENSORS = 16
 ADAMW_MAX_TENSORS = 32
 ADAMW_CHUNK = 8192  # elements of one tensor per workgroup
@@ -305,6 +317,9 @@ SIGNATURES = {
     "trlx_t5_attention_bwd": (_c_int, [ctypes.POINTER(T5AttentionBwdArgs), _c_vp]),
     "trlx_t5_attention_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
     "trlx_t5_attention_bwd_tiles": (_c_int, [ctypes.POINTER(_c_int)] * 4),
+    "trlx_t5_ff_act_fwd": (_c_int, [ctypes.POINTER(T5FfActArgs), _c_vp]),
+    "trlx_t5_ff_act_bwd": (_c_int, [ctypes.POINTER(T5FfActArgs), _c_vp]),
+    "trlx_t5_ff_act_geometry": (_c_int, [ctypes.POINTER(_c_int)] * 4),
     "trlx_rows_copy": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                 _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_shift_tokens_right": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp]),
