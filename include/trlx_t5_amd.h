@@ -1181,6 +1181,87 @@ int trlx_t5_ff_act_fwd(const TrlxT5FfActArgs* a, void* stream);
 int trlx_t5_ff_act_bwd(const TrlxT5FfActArgs* a, void* stream);
 int trlx_t5_ff_act_geometry(int* vec_bf16, int* vec_f32, int* cols_per_block, int* rows_per_block);
 
+/* ---------------------------------------------------------------- T5 RMSNorm with the residual add
+ * HF's T5LayerNorm (no mean subtraction, no bias, eps inside the root) and the residual add of the
+ * sub-layer before it (T5LayerFF / T5LayerSelfAttention: hidden + sublayer(norm(hidden))):
+ *   forward   h[n, j] = residual[n, j] + x[n, j]         add form only (residual and h given); rounded once
+ *             rstd[n] = 1 / sqrt(mean_j h[n, j]^2 + eps)  fp32, from h as rounded (without residual, x is h)
+ *             y[n, j] = w[j] * (h[n, j] * rstd[n])        fp32 arithmetic, rounded once
+ *   backward  g = w dy,  hh = h rstd,  c[n] = mean_j g hh
+ *             dh[n, j] = rstd[n] (g[n, j] - hh[n, j] c[n]) + dh_in[n, j]      rounded once
+ *             dw[j]    = sum_n dy[n, j] hh[n, j]                               fp32 sum, rounded once
+ * TRLX_F32 or TRLX_BF16, one dtype for every operand, w and dw included; rstd and ws are fp32.
+ *   x, residual, h, y, dy, dh_in, dh : N rows of D elements, element stride 1 and a row stride (in
+ *             elements) of their own each, ld_* >= D (checked for every N): h[:, -1, :], a [B, 1, D]
+ *             decode slice and padded buffers are read in place.  1 <= D <= 8192 (a row stays in
+ *             registers from the sum of squares to the stores: it is read once).
+ *   forward   reads x (and residual), writes y (and h), and rstd [N] when it is not NULL: one launch.
+ *             h may be the very rows of residual or of x (same pointer, same stride): the add in
+ *             place.  Without residual, y may be the very rows of x.  h never overlaps y, and no
+ *             other overlap of a written operand with another operand is taken.
+ *   backward  reads dy, h, and w (for dh), dh_in when not NULL, rstd when not NULL (else it is
+ *             recomputed from h).  dh and dw: either may be NULL (not computed, not written), not
+ *             both.  dh: one launch.  dw: the row launch leaves one fp32 partial row per workgroup in
+ *             ws [G, D] (every element the second launch reads was written: ws needs no clearing),
+ *             a second launch adds the G rows of a column in a fixed order: no atomics,
+ *             bit-reproducible.  ws_bytes >= trlx_t5_rmsnorm_geometry's ws_bytes for (N, D); with
+ *             dw NULL ws is not looked at.  dh may be the very rows of dh_in or of dy.
+ * 16-byte accesses when every pointer of the call is 16-byte aligned and D and every row stride are
+ * multiples of the vector width (8 bf16, 4 fp32); element accesses otherwise.  The two forms give
+ * the same bits.  N == 0 is a success (dw, if asked for, is cleared).
+ * Rows: an all-zero row gives y = 0 and rstd = eps^-1/2; a row whose sum of squares overflows fp32
+ * gives rstd = 0 and y = 0 as HF's fp32 expression does; a NaN stays in its row (y, dh) and reaches dw.
+ * Refused before any launch, every output untouched: NULL args or a NULL required pointer, residual
+ * without h or h without residual, dh and dw both NULL, dh_in without dh, a workspace that is NULL,
+ * misaligned or too small, a pointer not aligned to its element, h overlapping y or any other
+ * overlap not named above (TRLX_ERR_ARG); D outside [1, 8192], N < 0 (TRLX_ERR_SHAPE); a row stride
+ * below D (TRLX_ERR_STRIDE); a dtype other than the two (TRLX_ERR_DTYPE).
+ * trlx_t5_rmsnorm_geometry fills the launch geometry; the per-shape fields are 0 when D is outside
+ * [1, max_d].  Not built: fp16, dropout, a fused norm + projection GEMM, a double backward. */
+typedef struct TrlxT5RmsNormArgs {
+    const void* x;                    /* forward: the sub-layer output (add form) or the rows to normalise */
+    int64_t ld_x;
+    const void* residual;             /* forward, add form only, or NULL */
+    int64_t ld_residual;
+    void* h;                          /* forward: written in the add form, NULL otherwise; backward: read */
+    int64_t ld_h;
+    void* y;                          /* forward only */
+    int64_t ld_y;
+    const void* dy;                   /* backward only */
+    int64_t ld_dy;
+    const void* dh_in;                /* backward only, or NULL */
+    int64_t ld_dh_in;
+    void* dh;                         /* backward only, or NULL */
+    int64_t ld_dh;
+    const void* w;                    /* [D] */
+    void* dw;                         /* backward only, [D], or NULL */
+    void* rstd;                       /* fp32 [N]: written by the forward, read by the backward, or NULL */
+    void* ws;                         /* backward with dw: fp32 [G, D] */
+    int64_t ws_bytes;
+    int64_t N;
+    int64_t D;
+    float eps;
+    int dtype;                        /* TRLX_F32 / TRLX_BF16 */
+} TrlxT5RmsNormArgs;
+typedef struct TrlxT5RmsNormGeometry {
+    int vec_bf16, vec_f32;            /* elements per 16-byte access */
+    int threads;                      /* per workgroup */
+    int max_partials;                 /* the cap of G */
+    int max_d;                        /* the largest D taken */
+    int reg_max_d;                    /* the largest D whose row stays in registers (= max_d) */
+    int wave_row_max_d;               /* up to here one wave takes a row, threads / 64 rows per workgroup pass; above, one row */
+    int n_breaks;
+    int d_breaks[8];                  /* ascending: the largest D of each kernel form (elements per thread, wave or workgroup per row) */
+    int rows_per_block;               /* for this D: rows per workgroup pass */
+    int reserved;
+    int64_t row_blocks;               /* ceil(N / rows_per_block) */
+    int64_t partials;                 /* G = min(row_blocks, max_partials): workgroups of either row launch */
+    int64_t ws_bytes;                 /* G * D * 4 */
+} TrlxT5RmsNormGeometry;
+int trlx_t5_rmsnorm_fwd(const TrlxT5RmsNormArgs* a, void* stream);
+int trlx_t5_rmsnorm_bwd(const TrlxT5RmsNormArgs* a, void* stream);
+int trlx_t5_rmsnorm_geometry(int64_t N, int64_t D, TrlxT5RmsNormGeometry* g);
+
 /* ---------------------------------------------------------------- §8f: device-resident rollout store
  * Row copy between padded columnar [rows, W] buffers — replaces the reference's
  * `.cpu()` of the experience tensors, per-sample PPORLElement lists and the pad_sequence

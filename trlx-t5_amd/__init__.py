@@ -51,6 +51,10 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
       (gelu_new / silu / relu, gated or not) in one launch between the projections, fp32 arithmetic
       with one rounding, and a one-launch backward that saves u and v alone
       (HF T5DenseGatedActDense / T5DenseActDense)
+  t5_rmsnorm, t5_add_rmsnorm, T5LayerNorm — T5's layer norm with the residual add of the sub-layer
+      before it in one launch (h and the normed rows written, x and residual read once), fp32
+      arithmetic with one rounding, and a backward of at most two launches with no atomics
+      (HF T5LayerNorm, the adds of T5LayerSelfAttention / T5LayerCrossAttention / T5LayerFF)
   PPORolloutStorage, PPORLElement, PPORLBatch
       trlx/pipeline/ppo_pipeline.py, trlx/data/ppo_types.py (device-resident store)
   ILQLRolloutStorage (.from_samples = make_experience, .collate, .create_loader), ILQLElement
@@ -80,6 +84,7 @@ from .t5_decode import (T5DecodeKVCache, t5_decode_cross_attention, t5_decode_se
                         t5_relative_bias_table)
 from .t5_attention import t5_attention, t5_attention_train, t5_relative_bias_buckets, t5_relative_bias_offsets
 from .t5_ff import T5FeedForward, t5_ff_act, t5_ff_act_packed
+from .t5_norm import T5LayerNorm, t5_add_rmsnorm, t5_rmsnorm
 from .control import PPOControlState
 from .step import PPOHotPath
 from .comm import RcclComm
@@ -100,6 +105,7 @@ __all__ = [
     "T5DecodeKVCache", "t5_decode_self_attention", "t5_decode_cross_attention", "t5_relative_bias_table",
     "t5_attention", "t5_relative_bias_offsets", "t5_attention_train", "t5_relative_bias_buckets",
     "t5_ff_act", "t5_ff_act_packed", "T5FeedForward",
+    "t5_rmsnorm", "t5_add_rmsnorm", "T5LayerNorm",
 ]
 
 

@@ -136,6 +136,26 @@ class T5FfActArgs(ctypes.Structure):
     ]
 
 
+class T5RmsNormArgs(ctypes.Structure):
+    """Mirror of TrlxT5RmsNormArgs (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("x", _c_vp), ("ld_x", _c_i64), ("residual", _c_vp), ("ld_residual", _c_i64), ("h", _c_vp), ("ld_h", _c_i64),
+        ("y", _c_vp), ("ld_y", _c_i64), ("dy", _c_vp), ("ld_dy", _c_i64), ("dh_in", _c_vp), ("ld_dh_in", _c_i64),
+        ("dh", _c_vp), ("ld_dh", _c_i64), ("w", _c_vp), ("dw", _c_vp), ("rstd", _c_vp), ("ws", _c_vp),
+        ("ws_bytes", _c_i64), ("N", _c_i64), ("D", _c_i64), ("eps", _c_f), ("dtype", _c_int),
+    ]
+
+
+class T5RmsNormGeometry(ctypes.Structure):
+    """Mirror of TrlxT5RmsNormGeometry (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("vec_bf16", _c_int), ("vec_f32", _c_int), ("threads", _c_int), ("max_partials", _c_int), ("max_d", _c_int),
+        ("reg_max_d", _c_int), ("wave_row_max_d", _c_int), ("n_breaks", _c_int), ("d_breaks", _c_int * 8),
+        ("rows_per_block", _c_int), ("reserved", _c_int), ("row_blocks", _c_i64), ("partials", _c_i64),
+        ("ws_bytes", _c_i64),
+    ]
+
+
 POLYAK_MAX_TENSORS = 16
 ADAMW_MAX_TENSORS = 32
 ADAMW_CHUNK = 8192  # elements of one tensor per workgroup
@@ -320,6 +340,9 @@ SIGNATURES = {
     "trlx_t5_ff_act_fwd": (_c_int, [ctypes.POINTER(T5FfActArgs), _c_vp]),
     "trlx_t5_ff_act_bwd": (_c_int, [ctypes.POINTER(T5FfActArgs), _c_vp]),
     "trlx_t5_ff_act_geometry": (_c_int, [ctypes.POINTER(_c_int)] * 4),
+    "trlx_t5_rmsnorm_fwd": (_c_int, [ctypes.POINTER(T5RmsNormArgs), _c_vp]),
+    "trlx_t5_rmsnorm_bwd": (_c_int, [ctypes.POINTER(T5RmsNormArgs), _c_vp]),
+    "trlx_t5_rmsnorm_geometry": (_c_int, [_c_i64, _c_i64, ctypes.POINTER(T5RmsNormGeometry)]),
     "trlx_rows_copy": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                 _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_shift_tokens_right": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp]),
