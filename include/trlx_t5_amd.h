@@ -923,6 +923,35 @@ typedef struct TrlxPpoSampleProcArgs {
 } TrlxPpoSampleProcArgs;
 int trlx_ppo_sample_proc(const TrlxPpoSampleProcArgs* a, void* stream);
 
+/* The recording / processing step with its per-token scalars read from the decode clock (the
+ * record documented at trlx_decode_clock_init below): the same launch arguments at every token.
+ * The record block is required (a->ref_logits != NULL).  a->t, a->cur_len, a->forced_token_id and
+ * a->prefix1_len are not read; the kernel derives, from the clock's t and cur_len0:
+ *   t            the record column
+ *   cur_len      cur_len0 + t;  eos is suppressed while eos >= 0 && cur_len < min_length
+ *   forced token forced_eos_token_id at cur_len == max_length - 1, else forced_bos_token_id at
+ *                cur_len == 1, else none (eos wins when both fire)
+ *   prefix1_len  t; prefix1 / prefix1_ld are a->prefix1 / a->prefix1_ld when a->prefix1 is given
+ *                (row stride >= T - 1), else the record's own tokens / ld_tokens
+ *   u            u_ld == 0: u[b]; u_ld >= B: u[t * u_ld + b], row t of a [T, u_ld] table
+ * a->T must equal the clock's T; the step is live iff 0 <= t < min(a->T, clock T).  A live step
+ * is bit-identical, in every output and every record buffer, to trlx_ppo_sample_proc called with
+ * those host values.  A dead step stores nothing: no output, no record column, no unfinished and
+ * no lengths entry changes.  The processing kernel runs when a processor or either forced id is
+ * set, otherwise the recording kernel; each in its device-clock instantiation, on the launch
+ * table of trlx_ppo_sample.
+ * Refused with TRLX_ERR_ARG before any launch: a NULL d or clock, a clock not aligned to 8 bytes,
+ * u_ld not 0 and below B, a forced id outside [-1, V), forced_eos_token_id >= 0 with max_length
+ * < 1, a missing record block; and everything trlx_ppo_sample_proc refuses (t is not checked). */
+typedef struct TrlxPpoSampleDevArgs {
+    const int64_t* clock;          /* the decode clock record */
+    int64_t forced_bos_token_id;   /* -1 = none; forced at cur_len == 1 */
+    int64_t forced_eos_token_id;   /* -1 = none; forced at cur_len == max_length - 1; wins over bos */
+    int64_t max_length;            /* read only with forced_eos_token_id >= 0 */
+    int64_t u_ld;                  /* 0: u is [B]; >= B: u is a [T, u_ld] table, row t is this step's */
+} TrlxPpoSampleDevArgs;
+int trlx_ppo_sample_proc_dev(const TrlxPpoSampleProcArgs* a, const TrlxPpoSampleDevArgs* d, void* stream);
+
 /* ---------------------------------------------------------------- T5 decode-step attention
  * One query token per (batch row, head) over a device KV cache — replaces, per decoder layer
  * and generated token, the body of HF's T5Attention between the q / k / v projections and the
@@ -980,6 +1009,41 @@ typedef struct TrlxT5DecodeAttnArgs {
     int mode;                         /* TRLX_T5_ATTN_SELF / TRLX_T5_ATTN_CROSS */
 } TrlxT5DecodeAttnArgs;
 int trlx_t5_decode_attn(const TrlxT5DecodeAttnArgs* a, void* stream);
+
+/* ---------------------------------------------------------------- the decode clock
+ * The by-value scalars of a decode step that change every token — t of trlx_t5_decode_attn; t,
+ * cur_len, forced_token_id and prefix1_len of trlx_ppo_sample_proc — as a device record, so that
+ * the step's launches take the same arguments at every token and a graph captured once
+ * (hipGraph, torch.cuda.graph) replays the whole rollout.  The record is eight int64 words
+ * (64 bytes, 8-byte aligned, device memory):
+ *   word 0  t         the next decode step, which is also the next column
+ *   word 1  T         the capacity; a step issued with t outside [0, T) does nothing
+ *   word 2  cur_len0  HF's cur_len at t = 0 (1 for T5: the decoder start token)
+ *   word 3  overrun   the number of advances issued with t >= T; sticky
+ *   word 4-7          reserved, zero
+ * trlx_decode_clock_init sets {0, T, cur_len0, 0, 0, 0, 0, 0}; trlx_decode_clock_advance is one
+ * one-thread launch: t < T ? t += 1 : overrun += 1.  Both are stream-ordered, synchronise nothing
+ * and allocate nothing.  Nothing advances the clock implicitly: a decode step is the device-clock
+ * entries below, in any order, followed by one trlx_decode_clock_advance.
+ * Refused with TRLX_ERR_ARG before any launch: a NULL record or one not aligned to 8 bytes;
+ * init: T < 1, cur_len0 < 0. */
+#define TRLX_CLOCK_T 0
+#define TRLX_CLOCK_CAP 1
+#define TRLX_CLOCK_CUR_LEN0 2
+#define TRLX_CLOCK_OVERRUN 3
+#define TRLX_CLOCK_WORDS 8
+int trlx_decode_clock_init(int64_t* clock, int64_t T, int64_t cur_len0, void* stream);
+int trlx_decode_clock_advance(int64_t* clock, void* stream);
+
+/* trlx_t5_decode_attn, mode TRLX_T5_ATTN_SELF, with t read from the clock (a->t is not read).
+ * The step is live iff 0 <= t < min(clock T, max_len).  A live step is bit-identical to
+ * trlx_t5_decode_attn called with that t: out, column t of both caches, nothing else written.
+ * A dead step writes zeros to out and touches neither cache: every workgroup leaves before it
+ * forms an address from t.  Every other field, check and refusal is trlx_t5_decode_attn's; also
+ * refused with TRLX_ERR_ARG: a NULL clock, a clock not aligned to 8 bytes, mode
+ * TRLX_T5_ATTN_CROSS (the cross step reads no t: trlx_t5_decode_attn is already the same launch
+ * at every token). */
+int trlx_t5_decode_attn_dev(const TrlxT5DecodeAttnArgs* a, const int64_t* clock, void* stream);
 
 /* ---------------------------------------------------------------- T5 full-sequence attention
  * Many queries against many keys under T5's rules, forward only — replaces the body of HF's

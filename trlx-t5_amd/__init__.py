@@ -41,6 +41,9 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
       one decode step of a T5 decoder layer's attention over a device KV cache in one launch:
       cache append, scores, relative-position bias, encoder key mask, fp32 softmax, P·V
       (HF T5Attention between the projections and `o`, under generate)
+  T5DecodeClock — the decode position t as a device record: t5_decode_self_attention(t=clock) and
+      ppo_sample_step(recorder=PPORolloutRecorder(..., clock=clock)) read it on the device, so one
+      captured decode step (torch.cuda.graph) replays for every token; clock.advance() ends a step
   t5_attention, t5_relative_bias_offsets — T5's attention over whole sequences (encoder
       self-attention, teacher-forced decoder self- and cross-attention) as one flash-attention
       launch on MFMA: bias, key mask and causal rule inside, no [Tq, S] tensor
@@ -80,7 +83,7 @@ from .ilql_store import ILQLElement, ILQLRolloutStorage
 from .value_head import ValueHead, value_head, value_head_splits
 from .value_head import make_head as make_value_head
 from .sampling import PPOLogitsProcessors, ppo_sample_step
-from .t5_decode import (T5DecodeKVCache, t5_decode_cross_attention, t5_decode_self_attention,
+from .t5_decode import (T5DecodeClock, T5DecodeKVCache, t5_decode_cross_attention, t5_decode_self_attention,
                         t5_relative_bias_table)
 from .t5_attention import t5_attention, t5_attention_train, t5_relative_bias_buckets, t5_relative_bias_offsets
 from .t5_ff import T5FeedForward, t5_ff_act, t5_ff_act_packed
@@ -102,7 +105,7 @@ __all__ = [
     "RcclComm", "shift_tokens_right", "get_model_inputs",
     "ValueHead", "value_head", "value_head_splits", "make_value_head",
     "FusedAdamW", "adamw_step", "clip_grad_norm_", "schedule_table",
-    "T5DecodeKVCache", "t5_decode_self_attention", "t5_decode_cross_attention", "t5_relative_bias_table",
+    "T5DecodeKVCache", "T5DecodeClock", "t5_decode_self_attention", "t5_decode_cross_attention", "t5_relative_bias_table",
     "t5_attention", "t5_relative_bias_offsets", "t5_attention_train", "t5_relative_bias_buckets",
     "t5_ff_act", "t5_ff_act_packed", "T5FeedForward",
     "t5_rmsnorm", "t5_add_rmsnorm", "T5LayerNorm",

@@ -80,6 +80,15 @@ class PpoSampleProcArgs(ctypes.Structure):
     ]
 
 
+class PpoSampleDevArgs(ctypes.Structure):
+    """Mirror of TrlxPpoSampleDevArgs (include/trlx_t5_amd.h): the device-clock step's extra block."""
+    _fields_ = [("clock", _c_vp), ("forced_bos_token_id", _c_i64), ("forced_eos_token_id", _c_i64),
+                ("max_length", _c_i64), ("u_ld", _c_i64)]
+
+
+# the decode clock record (include/trlx_t5_amd.h): int64 words
+CLOCK_T, CLOCK_CAP, CLOCK_CUR_LEN0, CLOCK_OVERRUN, CLOCK_WORDS = 0, 1, 2, 3, 8
+
 T5_ATTN_SELF, T5_ATTN_CROSS = 0, 1
 
 
@@ -330,7 +339,12 @@ SIGNATURES = {
                                         _c_vp, _c_i64, _c_int, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp,
                                         _c_i64, _c_vp, _c_i64, _c_vp, _c_int, _c_vp, _c_int, _c_vp]),
     "trlx_ppo_sample_proc": (_c_int, [ctypes.POINTER(PpoSampleProcArgs), _c_vp]),
+    "trlx_ppo_sample_proc_dev": (_c_int, [ctypes.POINTER(PpoSampleProcArgs), ctypes.POINTER(PpoSampleDevArgs),
+                                          _c_vp]),
     "trlx_t5_decode_attn": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp]),
+    "trlx_decode_clock_init": (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp]),
+    "trlx_decode_clock_advance": (_c_int, [_c_vp, _c_vp]),
+    "trlx_t5_decode_attn_dev": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp, _c_vp]),
     "trlx_t5_attention": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp]),
     "trlx_t5_attention_tiles": (_c_int, [ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),
     "trlx_t5_attention_fwd_lse": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp, _c_vp]),

@@ -112,9 +112,40 @@ __device__ __forceinline__ PpoRecordArgs record_args(const PpoSampleProcArgs& a)
 __device__ __forceinline__ PpoProcArgs proc_args(const PpoSampleArgs&) { return PpoProcArgs{}; }
 __device__ __forceinline__ PpoProcArgs proc_args(const PpoSampleRecArgs&) { return PpoProcArgs{}; }
 __device__ __forceinline__ PpoProcArgs proc_args(const PpoSampleProcArgs& a) { return a.p; }
-template <bool REC, bool PROC>
-using ppo_sample_args_t =
-    std::conditional_t<PROC, PpoSampleProcArgs, std::conditional_t<REC, PpoSampleRecArgs, PpoSampleArgs>>;
+
+// The device-clock step (trlx_ppo_sample_proc_dev): what the host entries decide per token from
+// t and cur_len is decided by the kernel from the decode clock.  s.suppress_eos, r.t, p.n1 and
+// p.forced of the argument block are not read.
+struct PpoClockArgs {
+    const int64_t* clock;    // {t, T, cur_len0, overrun, ...}
+    int64_t T;               // the record buffers' columns
+    int64_t min_length;
+    int64_t forced_bos;      // -1 = none; at cur_len == 1
+    int64_t forced_eos;      // -1 = none; at cur_len == max_length - 1, wins
+    int64_t max_length;
+    int64_t u_ld;            // 0: u is [B]; else row t of a [T, u_ld] table
+};
+struct PpoSampleRecClockArgs {
+    PpoSampleArgs s;
+    PpoRecordArgs r;
+    PpoClockArgs c;
+};
+struct PpoSampleProcClockArgs {
+    PpoSampleArgs s;
+    PpoRecordArgs r;
+    PpoProcArgs p;
+    PpoClockArgs c;
+};
+__device__ __forceinline__ const PpoSampleArgs& sample_args(const PpoSampleRecClockArgs& a) { return a.s; }
+__device__ __forceinline__ const PpoSampleArgs& sample_args(const PpoSampleProcClockArgs& a) { return a.s; }
+__device__ __forceinline__ PpoRecordArgs record_args(const PpoSampleRecClockArgs& a) { return a.r; }
+__device__ __forceinline__ PpoRecordArgs record_args(const PpoSampleProcClockArgs& a) { return a.r; }
+__device__ __forceinline__ PpoProcArgs proc_args(const PpoSampleRecClockArgs&) { return PpoProcArgs{}; }
+__device__ __forceinline__ PpoProcArgs proc_args(const PpoSampleProcClockArgs& a) { return a.p; }
+template <bool REC, bool PROC, bool DEV = false>
+using ppo_sample_args_t = std::conditional_t<
+    DEV, std::conditional_t<PROC, PpoSampleProcClockArgs, PpoSampleRecClockArgs>,
+    std::conditional_t<PROC, PpoSampleProcArgs, std::conditional_t<REC, PpoSampleRecArgs, PpoSampleArgs>>>;
 
 // One row's step.  REC: the recording step — the reference row is reduced to per-wave
 // (max, sum exp) pairs first, parked in LDS (nothing of it stays in registers while the
@@ -134,12 +165,40 @@ using ppo_sample_args_t =
 // min-length drops eos: every thread tests the EPV bits of each vector it holds (two LDS words
 // per bitmap and vector).  A forced token needs no selection at all: the row is reduced for
 // the log-prob and the thread 0 writes the forced id, kept count 1, smallest kept logit 0.
-template <class DT, int NV, int NT, bool REC = false, bool PROC = false>
-__global__ __launch_bounds__(NT) void k_ppo_sample(ppo_sample_args_t<REC, PROC> args) {
+//
+// DEV: the device-clock step (instantiations of their own; DEV = false leaves the three kernels
+// above as they were).  t, T and cur_len0 are loaded from the clock once at the top of the
+// workgroup (uniform loads from a kernel-argument pointer).  A step with t outside
+// [0, min(T of the buffers, T of the clock)) is dead: every thread leaves before any store, and
+// no address is formed from t.  A live step sets the per-token fields the host entries receive
+// by value — the record column, the suppressed eos, the forced token, the length of the prefix's
+// second segment, this step's row of the uniforms — and runs the step unchanged.
+template <class DT, int NV, int NT, bool REC = false, bool PROC = false, bool DEV = false>
+__global__ __launch_bounds__(NT) void k_ppo_sample(ppo_sample_args_t<REC, PROC, DEV> args) {
     static_assert(REC || !PROC, "the processing step carries the record block");
-    const PpoSampleArgs& a = sample_args(args);
-    const PpoRecordArgs r = record_args(args);
-    [[maybe_unused]] const PpoProcArgs p = proc_args(args);
+    static_assert(REC || !DEV, "the device-clock step carries the record block");
+    [[maybe_unused]] PpoSampleArgs a_clock;
+    PpoRecordArgs r_step = record_args(args);
+    [[maybe_unused]] PpoProcArgs p_step = proc_args(args);
+    if constexpr (DEV) {
+        const PpoClockArgs c = args.c;
+        const int64_t tc = c.clock[TRLX_CLOCK_T], cap = c.clock[TRLX_CLOCK_CAP];
+        const int64_t cur_len = c.clock[TRLX_CLOCK_CUR_LEN0] + tc;
+        if (tc < 0 || tc >= (cap < c.T ? cap : c.T)) return;  // block-uniform, before any barrier
+        a_clock = args.s;
+        a_clock.suppress_eos = a_clock.eos >= 0 && cur_len < c.min_length;
+        a_clock.u = a_clock.u + tc * c.u_ld;
+        r_step.t = tc;
+        if constexpr (PROC) {
+            p_step.n1 = int(tc);
+            p_step.forced = c.forced_eos >= 0 && cur_len == c.max_length - 1 ? c.forced_eos
+                            : c.forced_bos >= 0 && cur_len == 1              ? c.forced_bos
+                                                                             : -1;
+        }
+    }
+    const PpoSampleArgs& a = DEV ? a_clock : sample_args(args);
+    const PpoRecordArgs r = r_step;
+    [[maybe_unused]] const PpoProcArgs p = p_step;
     [[maybe_unused]] bool rec_on = true;  // PROC: recording is a run-time choice (block-uniform)
     if constexpr (PROC) rec_on = r.ref_logits != nullptr;
     constexpr int kWaves = NT / kWave;
@@ -794,7 +853,7 @@ static int ppo_sample_launch(const char* who, const void* logits, int64_t ld_log
                              int64_t min_length, int64_t eos_token_id, int64_t pad_token_id, const float* u,
                              int64_t* out_ids, float* out_logprobs, float* out_min_kept, int32_t* out_kept_count,
                              int64_t* unfinished, const PpoRecordArgs* rec, void* stream,
-                             const PpoProcArgs* proc = nullptr) {
+                             const PpoProcArgs* proc = nullptr, const PpoClockArgs* clk = nullptr) {
     TRLX_REQUIRE(B == 0 || (logits && u && out_ids && out_logprobs && out_min_kept && out_kept_count), TRLX_ERR_ARG,
                  "NULL argument to %s", who);
     TRLX_REQUIRE(dtype == TRLX_F32 || dtype == TRLX_BF16, TRLX_ERR_DTYPE, "dtype %d", dtype);
@@ -828,6 +887,16 @@ static int ppo_sample_launch(const char* who, const void* logits, int64_t ld_log
     // cannot hold the row beside this kernel's state without scratch: rows end at ~53k entries)
 #define TRLX_PSMP(DTT, N, NT)                                                                                  \
     if (need(NT) <= N) {                                                                                       \
+        if (clk && proc) {                                                                                     \
+            hipLaunchKernelGGL((k_ppo_sample<DTT, N, NT, true, true, true>), dim3(unsigned(B)), dim3(NT), 0,   \
+                               (hipStream_t)stream, PpoSampleProcClockArgs{a, *rec, *proc, *clk});             \
+            return check_launch("k_ppo_sample<proc, clock>");                                                  \
+        }                                                                                                      \
+        if (clk) {                                                                                             \
+            hipLaunchKernelGGL((k_ppo_sample<DTT, N, NT, true, false, true>), dim3(unsigned(B)), dim3(NT), 0,  \
+                               (hipStream_t)stream, PpoSampleRecClockArgs{a, *rec, *clk});                     \
+            return check_launch("k_ppo_sample<record, clock>");                                                \
+        }                                                                                                      \
         if (proc) {                                                                                            \
             hipLaunchKernelGGL((k_ppo_sample<DTT, N, NT, true, true>), dim3(unsigned(B)), dim3(NT), 0,         \
                                (hipStream_t)stream, PpoSampleProcArgs{a, rec ? *rec : PpoRecordArgs{}, *proc}); \
@@ -877,12 +946,12 @@ static int ppo_sample_record_launch(const char* who, const void* logits, int64_t
                                     int64_t ld_tokens, float* logprobs, int64_t ld_logprobs, float* ref_logprobs,
                                     int64_t ld_ref_logprobs, float* values, int64_t ld_values,
                                     const void* step_values, int values_dtype, int64_t* lengths, int score_finished,
-                                    void* stream, const PpoProcArgs* proc) {
+                                    void* stream, const PpoProcArgs* proc, const PpoClockArgs* clk = nullptr) {
     TRLX_REQUIRE(B == 0 || (ref_logits && tokens && logprobs && ref_logprobs), TRLX_ERR_ARG,
                  "NULL argument to %s (ref_logits, tokens, logprobs, ref_logprobs)", who);
     TRLX_REQUIRE(ref_dtype == dtype, TRLX_ERR_DTYPE, "reference rows of dtype %d, policy rows of dtype %d", ref_dtype,
                  dtype);
-    TRLX_REQUIRE(T > 0 && t >= 0 && t < T, TRLX_ERR_SHAPE, "column t = %lld outside [0, T = %lld)", (long long)t,
+    TRLX_REQUIRE(T > 0 && (clk || (t >= 0 && t < T)), TRLX_ERR_SHAPE, "column t = %lld outside [0, T = %lld)", (long long)t,
                  (long long)T);
     TRLX_REQUIRE(ld_tokens >= T && ld_logprobs >= T && ld_ref_logprobs >= T && (!values || ld_values >= T),
                  TRLX_ERR_SHAPE, "a record buffer's row stride is below T = %lld", (long long)T);
@@ -910,7 +979,7 @@ static int ppo_sample_record_launch(const char* who, const void* logits, int64_t
     r.lengths = lengths;
     return ppo_sample_launch(who, logits, ld_logits, dtype, B, V, temperature, top_k, top_p, min_tokens_to_keep,
                              cur_len, min_length, eos_token_id, pad_token_id, u, out_ids, out_logprobs, out_min_kept,
-                             out_kept_count, unfinished, &r, stream, proc);
+                             out_kept_count, unfinished, &r, stream, proc, clk);
 }
 
 extern "C" int trlx_ppo_sample_record(const void* logits, int64_t ld_logits, int dtype, int64_t B, int64_t V,
@@ -931,22 +1000,51 @@ extern "C" int trlx_ppo_sample_record(const void* logits, int64_t ld_logits, int
                                     score_finished, stream, nullptr);
 }
 
-extern "C" int trlx_ppo_sample_proc(const TrlxPpoSampleProcArgs* a, void* stream) {
-    TRLX_REQUIRE(a, TRLX_ERR_ARG, "NULL argument to trlx_ppo_sample_proc");
+// trlx_ppo_sample_proc (d = NULL) and trlx_ppo_sample_proc_dev: with d, the per-token scalars of
+// *a (t, cur_len, forced_token_id, prefix1_len) are not read; the kernel takes them from the clock.
+static int ppo_sample_proc_entry(const char* who, const TrlxPpoSampleProcArgs* a, const TrlxPpoSampleDevArgs* d,
+                                 void* stream) {
+    TRLX_REQUIRE(a, TRLX_ERR_ARG, "NULL argument to %s", who);
     const int64_t V = a->V;
+    const bool dev = d != nullptr;
+    // the prefix's second segment: with the clock its length is t < T, and the record's own tokens
+    // unless the caller names another buffer
+    const int64_t* prefix1 = a->prefix1;
+    int64_t prefix1_ld = a->prefix1_ld, prefix1_len = a->prefix1_len;
+    int64_t forced = a->forced_token_id;
+    if (dev) {
+        TRLX_REQUIRE(d->clock, TRLX_ERR_ARG, "%s: NULL clock", who);
+        TRLX_REQUIRE((reinterpret_cast<uintptr_t>(d->clock) & 7u) == 0, TRLX_ERR_ARG,
+                     "%s: the clock is not aligned to 8 bytes", who);
+        TRLX_REQUIRE(a->ref_logits, TRLX_ERR_ARG, "%s: the record block is required (ref_logits is NULL)", who);
+        TRLX_REQUIRE(d->u_ld == 0 || d->u_ld >= a->B, TRLX_ERR_ARG, "%s: u_ld %lld (0, or a table row of >= B = %lld)",
+                     who, (long long)d->u_ld, (long long)a->B);
+        TRLX_REQUIRE(d->forced_bos_token_id >= -1 && d->forced_bos_token_id < V && d->forced_eos_token_id >= -1 &&
+                         d->forced_eos_token_id < V,
+                     TRLX_ERR_ARG, "%s: forced bos / eos token %lld / %lld outside [0, V) (-1 = none)", who,
+                     (long long)d->forced_bos_token_id, (long long)d->forced_eos_token_id);
+        TRLX_REQUIRE(d->forced_eos_token_id < 0 || d->max_length >= 1, TRLX_ERR_ARG,
+                     "%s: forced_eos_token_id needs max_length >= 1, got %lld", who, (long long)d->max_length);
+        TRLX_REQUIRE(a->T >= 1 && a->T < (int64_t(1) << 30), TRLX_ERR_SHAPE, "%s: T %lld", who, (long long)a->T);
+        if (!prefix1) {
+            prefix1 = a->tokens;
+            prefix1_ld = a->ld_tokens;
+        }
+        prefix1_len = a->T - 1;  // the longest the kernel reads; checked as such below
+        forced = -1;
+    }
     TRLX_REQUIRE(a->repetition_penalty > 0.f, TRLX_ERR_ARG, "repetition_penalty %g must be > 0",
                  double(a->repetition_penalty));
     TRLX_REQUIRE(a->no_repeat_ngram_size >= 0, TRLX_ERR_ARG, "no_repeat_ngram_size %d must be >= 0",
                  a->no_repeat_ngram_size);
-    TRLX_REQUIRE(a->forced_token_id >= -1 && a->forced_token_id < V, TRLX_ERR_ARG,
-                 "forced token %lld outside [0, V) (-1 = none)", (long long)a->forced_token_id);
-    TRLX_REQUIRE(a->prefix0_len >= 0 && a->prefix1_len >= 0 &&
-                     a->prefix0_len + a->prefix1_len < (int64_t(1) << 30),
-                 TRLX_ERR_SHAPE, "prefix lengths %lld + %lld", (long long)a->prefix0_len, (long long)a->prefix1_len);
-    TRLX_REQUIRE((a->prefix0_len == 0 || a->prefix0) && (a->prefix1_len == 0 || a->prefix1), TRLX_ERR_ARG,
+    TRLX_REQUIRE(forced >= -1 && forced < V, TRLX_ERR_ARG, "forced token %lld outside [0, V) (-1 = none)",
+                 (long long)forced);
+    TRLX_REQUIRE(a->prefix0_len >= 0 && prefix1_len >= 0 && a->prefix0_len + prefix1_len < (int64_t(1) << 30),
+                 TRLX_ERR_SHAPE, "prefix lengths %lld + %lld", (long long)a->prefix0_len, (long long)prefix1_len);
+    TRLX_REQUIRE((a->prefix0_len == 0 || a->prefix0) && (prefix1_len == 0 || prefix1), TRLX_ERR_ARG,
                  "a prefix segment with n > 0 and a NULL pointer");
     TRLX_REQUIRE((a->prefix0_len == 0 || a->prefix0_ld >= a->prefix0_len) &&
-                     (a->prefix1_len == 0 || a->prefix1_ld >= a->prefix1_len),
+                     (prefix1_len == 0 || prefix1_ld >= prefix1_len),
                  TRLX_ERR_SHAPE, "a prefix segment's row stride is below its length");
     const int64_t nbw = a->n_bad_words;
     TRLX_REQUIRE(nbw >= 0 && nbw < (int64_t(1) << 30), TRLX_ERR_SHAPE, "n_bad_words %lld", (long long)nbw);
@@ -966,16 +1064,35 @@ extern "C" int trlx_ppo_sample_proc(const TrlxPpoSampleProcArgs* a, void* stream
     p.seg0 = a->prefix0;
     p.ld0 = a->prefix0_ld;
     p.n0 = int(a->prefix0_len);
-    p.seg1 = a->prefix1;
-    p.ld1 = a->prefix1_ld;
-    p.n1 = int(a->prefix1_len);
+    p.seg1 = prefix1;
+    p.ld1 = prefix1_ld;
+    p.n1 = dev ? 0 : int(prefix1_len);
     p.bw_tok = a->bad_words;
     p.bw_off = a->bad_words_offsets;
     p.n_bw = int(nbw);
     p.ngram = a->no_repeat_ngram_size;
     p.rp = a->repetition_penalty;
     p.edits = p.rp != 1.f || p.ngram > 0 || p.n_bw > 0;
-    p.forced = a->forced_token_id;
+    p.forced = forced;
+    if (dev) {
+        // a processor or either forced id set: the processing kernel, else the recording kernel
+        const bool processing = p.edits || d->forced_bos_token_id >= 0 || d->forced_eos_token_id >= 0;
+        PpoClockArgs c = {};
+        c.clock = d->clock;
+        c.T = a->T;
+        c.min_length = a->min_length;
+        c.forced_bos = d->forced_bos_token_id;
+        c.forced_eos = d->forced_eos_token_id;
+        c.max_length = d->max_length;
+        c.u_ld = d->u_ld;
+        return ppo_sample_record_launch(who, a->logits, a->ld_logits, a->dtype, a->B, V, a->temperature, a->top_k,
+                                        a->top_p, a->min_tokens_to_keep, 0, a->min_length, a->eos_token_id,
+                                        a->pad_token_id, a->u, a->out_ids, a->out_logprobs, a->out_min_kept,
+                                        a->out_kept_count, a->unfinished, a->ref_logits, a->ld_ref, a->ref_dtype, 0,
+                                        a->T, a->tokens, a->ld_tokens, a->logprobs, a->ld_logprobs, a->ref_logprobs,
+                                        a->ld_ref_logprobs, a->values, a->ld_values, a->step_values, a->values_dtype,
+                                        a->lengths, a->score_finished, stream, processing ? &p : nullptr, &c);
+    }
     // every processor off and no forced token: the kernels of the other two entries
     const PpoProcArgs* proc = (p.edits || p.forced >= 0) ? &p : nullptr;
     if (a->ref_logits)
@@ -991,4 +1108,13 @@ extern "C" int trlx_ppo_sample_proc(const TrlxPpoSampleProcArgs* a, void* stream
                              a->top_k, a->top_p, a->min_tokens_to_keep, a->cur_len, a->min_length, a->eos_token_id,
                              a->pad_token_id, a->u, a->out_ids, a->out_logprobs, a->out_min_kept, a->out_kept_count,
                              a->unfinished, nullptr, stream, proc);
+}
+
+extern "C" int trlx_ppo_sample_proc(const TrlxPpoSampleProcArgs* a, void* stream) {
+    return ppo_sample_proc_entry("trlx_ppo_sample_proc", a, nullptr, stream);
+}
+
+extern "C" int trlx_ppo_sample_proc_dev(const TrlxPpoSampleProcArgs* a, const TrlxPpoSampleDevArgs* d, void* stream) {
+    TRLX_REQUIRE(d, TRLX_ERR_ARG, "NULL device arguments to trlx_ppo_sample_proc_dev");
+    return ppo_sample_proc_entry("trlx_ppo_sample_proc_dev", a, d, stream);
 }

@@ -14,6 +14,7 @@
 // column t of the cache and attends to them FROM THE REGISTERS; the loop reads columns 0..t-1
 // only, so nothing written by this launch is read by it and columns above t are never touched.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 
@@ -37,14 +38,29 @@ struct T5AttnArgs {
     int nH, max_len, t;
 };
 
+// The device-clock step (trlx_t5_decode_attn_dev): t comes from the decode clock, a.t is not read.
+struct T5AttnDevArgs {
+    T5AttnArgs a;
+    const int64_t* clock;
+};
+__device__ __forceinline__ const T5AttnArgs& t5_args(const T5AttnArgs& a) { return a; }
+__device__ __forceinline__ const T5AttnArgs& t5_args(const T5AttnDevArgs& a) { return a.a; }
+
 template <class DT>
 __device__ __forceinline__ vec4u t5_ld(const typename DT::elem_t* p) {
     return *reinterpret_cast<const vec4u*>(p);
 }
 
 // MODE: kT5Self (append + bias), kT5Cross (no mask), kT5CrossMasked (key_mask given)
-template <class DT, int DKV, int MODE>
-__global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn(const T5AttnArgs a) {
+// DEVT (kT5Self only): t and the capacity T are loaded from the decode clock, once, at the top of
+// the workgroup (uniform loads from a kernel-argument pointer).  A step with t outside
+// [0, min(T, max_len)) is dead: zeros to out[b, h, :] and out, before any address is formed from t
+// and before any barrier; the exit is uniform.  DEVT = false compiles to the kernel without it.
+template <class DT, int DKV, int MODE, bool DEVT = false>
+__global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn(
+    const std::conditional_t<DEVT, T5AttnDevArgs, T5AttnArgs> args) {
+    static_assert(!DEVT || MODE == kT5Self, "only the self-attention reads t");
+    const T5AttnArgs& a = t5_args(args);
     typedef typename DT::elem_t E;
     constexpr int EPV = DT::kEPV;
     constexpr int LPR = DKV / EPV;             // lanes per key row
@@ -61,7 +77,27 @@ __global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn(const T5AttnArgs 
     const int sl = lane % LPR;                 // this lane's vector of the row
     const int gg = wave * KPW + lane / LPR;    // group id in the workgroup
     const int col = h * DKV + sl * EPV;
-    const int t = a.t;
+    [[maybe_unused]] int t_clock = 0;
+    if constexpr (DEVT) {
+        const int64_t tc = args.clock[TRLX_CLOCK_T], cap = args.clock[TRLX_CLOCK_CAP];
+        const int64_t lim = cap < int64_t(a.max_len) ? cap : int64_t(a.max_len);
+        if (tc < 0 || tc >= lim) {   // block-uniform
+            if (threadIdx.x < DKV / 2) {
+                const int64_t o = int64_t(bh) * DKV + 2 * threadIdx.x;
+                if (sizeof(E) == 2) {
+                    *reinterpret_cast<uint32_t*>(static_cast<uint16_t*>(a.out) + o) = 0u;
+                } else {
+                    float2 z;
+                    z.x = 0.f;
+                    z.y = 0.f;
+                    *reinterpret_cast<float2*>(static_cast<float*>(a.out) + o) = z;
+                }
+            }
+            return;
+        }
+        t_clock = int(tc);
+    }
+    const int t = DEVT ? t_clock : a.t;
 
     float qf[EPV];
     DT::unpack(t5_ld<DT>(static_cast<const E*>(a.q) + int64_t(b) * a.ldq + col), qf);
@@ -187,7 +223,8 @@ static bool t5_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p)
 
 using namespace trlx;
 
-extern "C" int trlx_t5_decode_attn(const TrlxT5DecodeAttnArgs* a, void* stream) {
+// The argument checks of both entries and the kernel's argument block.  dev: a->t is not read.
+static int t5_decode_attn_prepare(const TrlxT5DecodeAttnArgs* a, bool dev, T5AttnArgs* args) {
     TRLX_REQUIRE(a, TRLX_ERR_ARG, "t5 decode attention: NULL arguments");
     TRLX_REQUIRE(a->dtype == TRLX_BF16 || a->dtype == TRLX_F32, TRLX_ERR_ARG,
                  "t5 decode attention: dtype %d (bf16 and fp32 only)", a->dtype);
@@ -212,7 +249,7 @@ extern "C" int trlx_t5_decode_attn(const TrlxT5DecodeAttnArgs* a, void* stream) 
                  "t5 decode attention: q, K, V and out must be 16-byte aligned");
     int64_t ldk = 0, ldv = 0;
     if (self) {
-        TRLX_REQUIRE(a->t >= 0 && a->t < a->max_len, TRLX_ERR_ARG, "t5 decode attention: t %lld outside [0, max_len %lld)",
+        TRLX_REQUIRE(dev || (a->t >= 0 && a->t < a->max_len), TRLX_ERR_ARG, "t5 decode attention: t %lld outside [0, max_len %lld)",
                      (long long)a->t, (long long)a->max_len);
         TRLX_REQUIRE(a->k_new && a->v_new, TRLX_ERR_ARG, "t5 decode attention: NULL k_new / v_new");
         ldk = a->B == 1 ? inner : a->ldk;
@@ -245,9 +282,41 @@ extern "C" int trlx_t5_decode_attn(const TrlxT5DecodeAttnArgs* a, void* stream) 
     k.ldv = ldv;
     k.nH = int(a->n_heads);
     k.max_len = int(a->max_len);
-    k.t = int(a->t);
-    const int mode = self ? kT5Self : a->key_mask ? kT5CrossMasked : kT5Cross;
+    k.t = dev ? 0 : int(a->t);
+    *args = k;
+    return TRLX_OK;
+}
+
+extern "C" int trlx_t5_decode_attn(const TrlxT5DecodeAttnArgs* a, void* stream) {
+    T5AttnArgs k;
+    const int rc = t5_decode_attn_prepare(a, false, &k);
+    if (rc) return rc;
+    const int mode = a->mode == TRLX_T5_ATTN_SELF ? kT5Self : a->key_mask ? kT5CrossMasked : kT5Cross;
     hipLaunchKernelGGL(t5_pick(a->dtype, a->d_kv, mode), dim3(unsigned(a->B * a->n_heads)), dim3(kT5Threads), 0,
                        (hipStream_t)stream, k);
     return check_launch("k_t5_decode_attn");
+}
+
+typedef void (*t5_clock_kernel_t)(const T5AttnDevArgs);
+static t5_clock_kernel_t t5_pick_clock(int dtype, int64_t d_kv) {
+    if (dtype == TRLX_BF16)
+        return d_kv == 64 ? k_t5_decode_attn<BF16T, 64, kT5Self, true> : k_t5_decode_attn<BF16T, 128, kT5Self, true>;
+    return d_kv == 64 ? k_t5_decode_attn<F32T, 64, kT5Self, true> : k_t5_decode_attn<F32T, 128, kT5Self, true>;
+}
+
+extern "C" int trlx_t5_decode_attn_dev(const TrlxT5DecodeAttnArgs* a, const int64_t* clock, void* stream) {
+    TRLX_REQUIRE(a, TRLX_ERR_ARG, "t5 decode attention: NULL arguments");
+    TRLX_REQUIRE(a->mode == TRLX_T5_ATTN_SELF, TRLX_ERR_ARG,
+                 "t5 decode attention, device clock: mode %d (the self-attention only; the cross step reads no t)",
+                 a->mode);
+    TRLX_REQUIRE(clock, TRLX_ERR_ARG, "t5 decode attention, device clock: NULL clock");
+    TRLX_REQUIRE((reinterpret_cast<uintptr_t>(clock) & 7u) == 0, TRLX_ERR_ARG,
+                 "t5 decode attention, device clock: the clock is not aligned to 8 bytes");
+    T5AttnDevArgs k;
+    const int rc = t5_decode_attn_prepare(a, true, &k.a);
+    if (rc) return rc;
+    k.clock = clock;
+    hipLaunchKernelGGL(t5_pick_clock(a->dtype, a->d_kv), dim3(unsigned(a->B * a->n_heads)), dim3(kT5Threads), 0,
+                       (hipStream_t)stream, k);
+    return check_launch("k_t5_decode_attn<clock>");
 }

@@ -209,13 +209,31 @@ class PPORolloutRecorder:
     Allocated once; a step allocates nothing here.  hot_path: a PPOHotPath of the same B and T —
     logprobs / ref_logprobs are then its own lp_old / ref_lp, so
     PPOHotPath.experience_from_logprobs() reads them with no copy.  reset() re-arms the
-    recorder for the next chunk; push_to() hands the chunk to a PPORolloutStorage."""
+    recorder for the next chunk; push_to() hands the chunk to a PPORolloutStorage.
 
-    def __init__(self, B: int, T: int, device, pad_token_id: int, eos_token_id: Optional[int], hot_path=None):
+    clock: a T5DecodeClock of capacity T on the same device.  The recording step then reads the
+    column from the clock on the device (trlx_ppo_sample_proc_dev): the same launch at every token,
+    so a captured decode step replays.  The step does not touch `t` and does not advance the clock
+    — the caller's step ends with clock.advance(); a step issued with the clock at or past T
+    writes nothing.  reset() also resets the clock; sync_t() reads the clock once (a host sync)
+    and sets t = min(clock.t, T) for push_to() and PPOHotPath.experience_from_logprobs()."""
+
+    def __init__(self, B: int, T: int, device, pad_token_id: int, eos_token_id: Optional[int], hot_path=None,
+                 clock=None):
         self.B, self.T = int(B), int(T)
         if self.B < 1 or self.T < 1:
             raise ValueError("PPORolloutRecorder needs B >= 1 and T >= 1")
         self.device = torch.device(device)
+        if clock is not None:
+            from .t5_decode import T5DecodeClock
+            if not isinstance(clock, T5DecodeClock):
+                raise ValueError("clock must be a T5DecodeClock")
+            if clock.T != self.T:
+                raise ValueError(f"the clock's capacity T = {clock.T} is not the recorder's T = {self.T}")
+            cd, rd = clock.device, self.device
+            if cd.type != rd.type or (cd.index or 0) != (rd.index or 0):
+                raise ValueError(f"the clock is on {clock.device}, the recorder on {self.device}")
+        self.clock = clock
         if pad_token_id is None:
             raise ValueError("PPORolloutRecorder needs pad_token_id (the token of a finished row)")
         self.pad_token_id = int(pad_token_id)
@@ -246,13 +264,21 @@ class PPORolloutRecorder:
         self.lengths.fill_(self.T)
         self.unfinished.fill_(1)
         self.t = 0
+        if self.clock is not None:
+            self.clock.reset()
+
+    def sync_t(self):
+        """With a clock: t = min(clock.t, T), one host read (it synchronises).  Returns t."""
+        if self.clock is not None:
+            self.t = min(max(self.clock.t, 0), self.T)
+        return self.t
 
     def _step_inputs(self, logits, ref_logits, values, pad_token_id, eos_token_id, unfinished):
         """The recording step's argument checks (all before any launch) -> (pad, eos, unfinished)."""
         B, V = logits.shape
         if B != self.B:
             raise ValueError(f"logits have {B} rows, the recorder {self.B}")
-        if self.t >= self.T:
+        if self.clock is None and self.t >= self.T:
             raise ValueError(f"the recorder is full (t = {self.t} = T): reset() starts the next chunk")
         if logits.device != self.device:
             raise ValueError(f"logits on {logits.device}, the recorder on {self.device}")

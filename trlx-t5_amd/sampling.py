@@ -145,7 +145,19 @@ def ppo_sample_step(logits, *, temperature=1.0, top_k=0, top_p=1.0, min_tokens_t
     policy / reference log-probs stay those of the unmodified rows at the token, forced tokens
     included; min_kept_logit / kept_count describe the processed row (0 and 1 at a forced step).
     On bf16 rows the penalised logit stays fp32 (HF rounds it back to bf16).  Without
-    `processors` the step is today's, through today's entries."""
+    `processors` the step is today's, through today's entries.
+
+    A recorder built with clock= (a T5DecodeClock): the device-clock step
+    (trlx_ppo_sample_proc_dev).  The column t, cur_len = clock.cur_len0 + t, the eos suppression
+    below min_length, the forced token (processors' forced_bos_token_id / forced_eos_token_id /
+    max_length, the rule of PPOLogitsProcessors.forced) and the prefix's second segment
+    recorder.tokens[:, :t] are all taken on the device from the clock: the call is the same
+    launch at every token, reads nothing of the device on the host, and can be captured
+    (torch.cuda.graph).  A live step is bit-identical to the host step at that t; a step with the
+    clock at or past T stores nothing.  cur_len must not be passed (ValueError); recorder.t is
+    not touched (recorder.sync_t() reads it back after the rollout) and the clock is NOT
+    advanced: the caller's decode step ends with clock.advance().  `u` may also be a contiguous
+    float32 [T, B] table, row t being step t's uniforms: one torch.rand serves the rollout."""
     if processors is None:
         if prefix is not None or prefix_len is not None:
             raise ValueError("prefix / prefix_len are read by the processors: pass processors=")
@@ -175,6 +187,16 @@ def ppo_sample_step(logits, *, temperature=1.0, top_k=0, top_p=1.0, min_tokens_t
     recording = ref_logits is not None or recorder is not None
     if recording and (ref_logits is None or recorder is None):
         raise ValueError("ref_logits and recorder go together (the recording step needs both)")
+    clock = getattr(recorder, "clock", None) if recording else None
+    if clock is not None:  # the device-clock step: nothing below may depend on the position
+        if cur_len is not None:
+            raise ValueError("cur_len with a clocked recorder: the kernel derives cur_len = clock.cur_len0 + t from "
+                             "the device clock (a host value would be baked into a captured step); set cur_len0 on "
+                             "the T5DecodeClock instead")
+        if u is not None and u.dim() == 2:
+            if u.dtype != torch.float32 or tuple(u.shape) != (recorder.T, logits.shape[0]) or not u.is_contiguous():
+                raise ValueError(f"a u table must be contiguous float32 [T, B] = [{recorder.T}, {logits.shape[0]}] "
+                                 f"(row t is step t's uniforms), got {u.dtype} {tuple(u.shape)}")
     _lib.require_cuda(logits, unfinished, u)
     if logits.dim() != 2:
         raise ValueError("logits must be [B, V] (the last position)")
@@ -200,8 +222,11 @@ def ppo_sample_step(logits, *, temperature=1.0, top_k=0, top_p=1.0, min_tokens_t
         unf = unfinished.reshape(B)
         if unf.dtype != torch.int64 or not unf.is_contiguous() or unf.data_ptr() != unfinished.data_ptr():
             raise ValueError("unfinished must be a contiguous int64 tensor (updated in place)")
+    u_ld = 0
     if u is None:
         u = torch.rand(B, generator=generator, device=dev, dtype=torch.float32)
+    elif clock is not None and u.dim() == 2:  # the [T, B] table, checked above
+        u_ld = B
     elif u.dtype != torch.float32 or tuple(u.shape) != (B,) or not u.is_contiguous():
         raise ValueError("u must be a contiguous float32 [B] tensor")
     if out is None:
@@ -218,17 +243,20 @@ def ppo_sample_step(logits, *, temperature=1.0, top_k=0, top_p=1.0, min_tokens_t
             top_k, float(top_p), int(min_tokens_to_keep), 0 if cur_len is None else int(cur_len), int(min_length),
             -1 if eos_token_id is None else int(eos_token_id), -1 if pad_token_id is None else int(pad_token_id),
             u.data_ptr(), ids.data_ptr(), lp.data_ptr(), min_kept.data_ptr(), kept.data_ptr(), _lib.ptr(unf))
-    if processors is not None:
+    if processors is not None or clock is not None:
         pa = _lib.PpoSampleProcArgs()
         (pa.logits, pa.ld_logits, pa.dtype, pa.B, pa.V, pa.temperature, pa.top_k, pa.top_p, pa.min_tokens_to_keep,
          pa.cur_len, pa.min_length, pa.eos_token_id, pa.pad_token_id, pa.u, pa.out_ids, pa.out_logprobs,
          pa.out_min_kept, pa.out_kept_count, pa.unfinished) = step
-        pa.repetition_penalty = processors.repetition_penalty
-        pa.no_repeat_ngram_size = processors.no_repeat_ngram_size
-        pa.forced_token_id = processors.forced(cur_len)
+        pa.repetition_penalty, pa.forced_token_id = 1.0, -1
+        if processors is not None:
+            pa.repetition_penalty = processors.repetition_penalty
+            pa.no_repeat_ngram_size = processors.no_repeat_ngram_size
+            if clock is None:
+                pa.forced_token_id = processors.forced(cur_len)
         if prefix is not None and int(prefix_len) > 0:
             pa.prefix0, pa.prefix0_ld, pa.prefix0_len = prefix.data_ptr(), prefix.stride(0), int(prefix_len)
-        if processors.n_bad_words:
+        if processors is not None and processors.n_bad_words:
             pa.bad_words, pa.bad_words_offsets = processors.bad_tokens.data_ptr(), processors.bad_offsets.data_ptr()
             pa.bad_words_host = processors._host_tokens.data_ptr()
             pa.bad_words_offsets_host = processors._host_offsets.data_ptr()
@@ -236,10 +264,12 @@ def ppo_sample_step(logits, *, temperature=1.0, top_k=0, top_p=1.0, min_tokens_t
         if recording:
             rec = recorder
             ref = ref_logits if ref_logits.stride(-1) == 1 else ref_logits.contiguous()
-            if rec.t > 0:
+            if clock is not None:  # the kernel reads tokens[:, :t] with the clock's t
+                pa.prefix1, pa.prefix1_ld = rec.tokens.data_ptr(), rec.tokens.stride(0)
+            elif rec.t > 0:
                 pa.prefix1, pa.prefix1_ld, pa.prefix1_len = rec.tokens.data_ptr(), rec.tokens.stride(0), rec.t
             pa.ref_logits, pa.ld_ref, pa.ref_dtype, pa.t, pa.T = ref.data_ptr(), ref.stride(0), _lib.dtype_code(ref), \
-                rec.t, rec.T
+                (0 if clock is not None else rec.t), rec.T
             pa.tokens, pa.ld_tokens = rec.tokens.data_ptr(), rec.tokens.stride(0)
             pa.logprobs, pa.ld_logprobs = rec.logprobs.data_ptr(), rec.logprobs.stride(0)
             pa.ref_logprobs, pa.ld_ref_logprobs = rec.ref_logprobs.data_ptr(), rec.ref_logprobs.stride(0)
@@ -249,9 +279,20 @@ def ppo_sample_step(logits, *, temperature=1.0, top_k=0, top_p=1.0, min_tokens_t
             pa.ld_values = rec.values.stride(0)
             pa.lengths = rec.lengths.data_ptr()
             pa.score_finished = int(bool(score_finished))
-        _lib.call("trlx_ppo_sample_proc", ctypes.byref(pa), _lib.stream_of(rows))
-        if recording:
-            recorder.t += 1
+        if clock is not None:
+            # forced bos / eos and max_length go to the entry; the kernel applies processors.forced's rule
+            da = _lib.PpoSampleDevArgs(clock=clock.record.data_ptr(), forced_bos_token_id=-1, forced_eos_token_id=-1,
+                                       max_length=0, u_ld=u_ld)
+            if processors is not None:
+                if processors.forced_bos_token_id is not None:
+                    da.forced_bos_token_id = processors.forced_bos_token_id
+                if processors.forced_eos_token_id is not None:
+                    da.forced_eos_token_id, da.max_length = processors.forced_eos_token_id, processors.max_length
+            _lib.call("trlx_ppo_sample_proc_dev", ctypes.byref(pa), ctypes.byref(da), _lib.stream_of(rows))
+        else:
+            _lib.call("trlx_ppo_sample_proc", ctypes.byref(pa), _lib.stream_of(rows))
+            if recording:
+                recorder.t += 1
     elif recording:
         rec = recorder
         ref = ref_logits if ref_logits.stride(-1) == 1 else ref_logits.contiguous()

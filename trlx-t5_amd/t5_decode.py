@@ -6,6 +6,8 @@
   t5_decode_self_attention   append k_new / v_new at column t, attend over columns 0..t with the
                              relative-position bias: one launch
   t5_decode_cross_attention  attend over the encoder's keys under its key mask: one launch
+  T5DecodeClock              the decode position t as a device record: t5_decode_self_attention(t=clock)
+                             reads it on the device, so a captured decode step replays per token
 
 Per layer and generated token HF's eager T5Attention spends, between the projections and `o`, a
 cache append, a [B, nH, 1, t] matmul, compute_bias (arange, bucket formula, embedding lookup,
@@ -25,7 +27,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["t5_relative_bias_table", "T5DecodeKVCache", "t5_decode_self_attention", "t5_decode_cross_attention"]
+__all__ = ["t5_relative_bias_table", "T5DecodeKVCache", "T5DecodeClock", "t5_decode_self_attention",
+           "t5_decode_cross_attention"]
 
 KERNEL_DTYPES = (torch.bfloat16, torch.float32)
 KERNEL_D_KV = (64, 128)
@@ -73,6 +76,56 @@ class T5DecodeKVCache:
     @property
     def device(self):
         return self.k.device
+
+
+class T5DecodeClock:
+    """The decode position as a device record (trlx_decode_clock_init in trlx_t5_amd.h): int64 [8]
+    = {t, T, cur_len0, overrun, 0, 0, 0, 0}.  t5_decode_self_attention(t=clock) and
+    ppo_sample_step(recorder=PPORolloutRecorder(..., clock=clock)) read t from it on the device, so
+    the launches of a decode step take the same arguments at every token and a step captured once
+    (torch.cuda.graph) replays the whole rollout.
+
+      T          the capacity: a step issued with t outside [0, T) does nothing
+      cur_len0   HF's cur_len at t = 0 (1 for T5, the decoder start token)
+      record     the int64 [8] tensor
+      reset()    {0, T, cur_len0, 0, ...}: one launch, stream-ordered
+      advance()  t < T ? t += 1 : overrun += 1: one launch, stream-ordered
+      t, overrun host reads that synchronise: for after the rollout and for tests
+
+    Nothing advances the clock implicitly: the caller's decode step ends with clock.advance(), one
+    launch, after every call of the step that reads the clock.  On a CPU device the record exists
+    for argument checks only and advance() raises."""
+
+    def __init__(self, T, device, cur_len0=1):
+        if isinstance(T, bool) or int(T) != T or int(T) < 1:
+            raise ValueError(f"T5DecodeClock needs an integer capacity T >= 1, got {T!r}")
+        if isinstance(cur_len0, bool) or int(cur_len0) != cur_len0 or int(cur_len0) < 0:
+            raise ValueError(f"cur_len0 must be an integer >= 0, got {cur_len0!r}")
+        self.T, self.cur_len0 = int(T), int(cur_len0)
+        self.device = torch.device(device)
+        self.record = torch.zeros(_lib.CLOCK_WORDS, dtype=torch.int64, device=self.device)
+        self.reset()
+
+    def reset(self):
+        """t = 0, overrun = 0 (one launch on the current stream)."""
+        if self.record.is_cuda:
+            _lib.call("trlx_decode_clock_init", self.record.data_ptr(), self.T, self.cur_len0,
+                      _lib.stream_of(self.record))
+        else:
+            self.record.copy_(torch.tensor([0, self.T, self.cur_len0, 0, 0, 0, 0, 0], dtype=torch.int64))
+
+    def advance(self):
+        """The end of a decode step: t += 1, or overrun += 1 once t has reached T (one launch)."""
+        _lib.require_cuda(self.record)
+        _lib.call("trlx_decode_clock_advance", self.record.data_ptr(), _lib.stream_of(self.record))
+
+    @property
+    def t(self):
+        return int(self.record[_lib.CLOCK_T])
+
+    @property
+    def overrun(self):
+        return int(self.record[_lib.CLOCK_OVERRUN])
 
 
 def _rows(x, name, B, nH, d):
@@ -139,15 +192,32 @@ def t5_decode_self_attention(q, k_new, v_new, cache, t, bias_table=None):
 
     q, k_new, v_new: the projections of this token, [B, nH*d_kv], [B, 1, nH*d_kv], [B, nH, d_kv] or
     [B, nH, 1, d_kv] (HF's transposed view); row-strided views such as the three slices of a fused
-    [B, 3*nH*d_kv] qkv projection are read in place.  t: a host int, 0 <= t < cache.max_len.
+    [B, 3*nH*d_kv] qkv projection are read in place.  t: a host int, 0 <= t < cache.max_len, or a
+    T5DecodeClock on the cache's device with clock.T <= cache.max_len: the kernel then reads t from
+    the clock (trlx_t5_decode_attn_dev), the call is the same launch at every token and can be
+    captured; a live step is bit-identical to the call with that host t, a step with the clock at
+    or past T (or below 0) returns zeros and leaves the cache alone.  The clock is not advanced
+    here: the caller's step ends with clock.advance().  With a clock, a dtype or d_kv the kernel
+    does not take raises ValueError (the torch fallback slices by a host t).
     bias_table: t5_relative_bias_table(...) for the layer that owns the bias, or None.
     Runs on the current stream, no host sync; only the output is allocated."""
     if not isinstance(cache, T5DecodeKVCache):
         raise TypeError("cache must be a T5DecodeKVCache")
     B, nH, d = cache.B, cache.n_heads, cache.d_kv
-    t = int(t)
-    if not 0 <= t < cache.max_len:
-        raise ValueError(f"t = {t} outside [0, max_len = {cache.max_len})")
+    clock = t if isinstance(t, T5DecodeClock) else None
+    if clock is not None:
+        if clock.T > cache.max_len:
+            raise ValueError(f"the clock's capacity T = {clock.T} exceeds the cache's max_len = {cache.max_len}")
+        if clock.device != cache.device:
+            raise ValueError(f"the clock is on {clock.device}, the cache on {cache.device}")
+        if not _kernel_takes(cache.dtype, d):
+            raise ValueError(f"t=clock needs the kernel ({KERNEL_DTYPES}, d_kv in {KERNEL_D_KV}); the torch "
+                             f"fallback for {cache.dtype}, d_kv {d} slices by a host t and cannot be captured")
+        t = 0
+    else:
+        t = int(t)
+        if not 0 <= t < cache.max_len:
+            raise ValueError(f"t = {t} outside [0, max_len = {cache.max_len})")
     for x in (q, k_new, v_new):
         _check_q(x, B, nH, d, cache.dtype, cache.device)
     if bias_table is not None:
@@ -165,7 +235,10 @@ def t5_decode_self_attention(q, k_new, v_new, cache, t, bias_table=None):
         k=cache.k.data_ptr(), v=cache.v.data_ptr(), bias_by_distance=_lib.ptr(bias_table), key_mask=None,
         out=out.data_ptr(), B=B, n_heads=nH, d_kv=d, max_len=cache.max_len, t=t,
         dtype=_lib.dtype_code(cache.k), mode=_lib.T5_ATTN_SELF)
-    _lib.call("trlx_t5_decode_attn", ctypes.byref(args), _lib.stream_of(out))
+    if clock is not None:
+        _lib.call("trlx_t5_decode_attn_dev", ctypes.byref(args), clock.record.data_ptr(), _lib.stream_of(out))
+    else:
+        _lib.call("trlx_t5_decode_attn", ctypes.byref(args), _lib.stream_of(out))
     return out
 
 
