@@ -1045,6 +1045,67 @@ int trlx_decode_clock_advance(int64_t* clock, void* stream);
  * at every token). */
 int trlx_t5_decode_attn_dev(const TrlxT5DecodeAttnArgs* a, const int64_t* clock, void* stream);
 
+/* trlx_t5_decode_attn with a per-row skip: live is int64 [B], 0 or non-zero (the recording step's
+ * `unfinished` is passed as it is).  clock: NULL for the host t (self) and for the cross mode, or
+ * the decode clock for the self mode as in trlx_t5_decode_attn_dev (a->t is then not read).
+ * A workgroup of a row with live[b] == 0 loads that one word, writes zeros to out[b, h, :] and
+ * returns, before any barrier and before it forms an address into q, k_new, v_new, k, v, key_mask
+ * or bias_by_distance; in the self mode column t of both caches stays unwritten for that row.  A
+ * row with live[b] != 0 is bit-identical, in out and in column t of the caches, to
+ * trlx_t5_decode_attn (host t, cross) / trlx_t5_decode_attn_dev (clock) with the same arguments.
+ * Kernels of their own: the instantiations behind the two entries above are not touched.
+ * For rollouts whose recording step runs with score_finished = 0: with score_finished != 0 the
+ * sampler would score the pad of a row whose attention was skipped.  Within one decode step every
+ * layer's call reads live before that step's sampling launch writes it (stream order).
+ * Refused with TRLX_ERR_ARG before any launch: a NULL live, a live or clock not aligned to 8
+ * bytes, a clock with mode TRLX_T5_ATTN_CROSS; and everything trlx_t5_decode_attn refuses (with a
+ * clock, t is not checked). */
+int trlx_t5_decode_attn_live(const TrlxT5DecodeAttnArgs* a, const int64_t* live, const int64_t* clock, void* stream);
+
+/* The decoder's input row of decode step t, ONE launch — replaces, per generated token, the
+ * gather of the token drawn at step t - 1, the `shared` embedding lookup (T5 applies no scale)
+ * and layer 0's first T5LayerNorm.  clock == NULL: t is a->t; otherwise t and the capacity are
+ * read from the decode clock (a->t is not read), once at the top of each workgroup.  Per row b:
+ *   tok     = t == 0 ? start_token_id : tokens[b * ld_tokens + t - 1]
+ *   h[b, :] = weight[tok, :], bit for bit; a tok outside [0, V) gives a zero row (tested before
+ *             any address is formed from tok)
+ *   y[b, :] = norm_w * h[b, :] * rsqrt(mean(h[b, :]^2) + eps), only with norm_w: bit-equal to
+ *             trlx_t5_rmsnorm_fwd on h (the same row tile, sum order and kernel form by D); the
+ *             row stays in registers between the gather and the two stores
+ *   weight  : [V, D] of `dtype`, rows ld_w >= D elements apart (HF's shared.weight, or a slice of
+ *             it, read in place)
+ *   tokens  : int64 [B, T], rows ld_tokens >= T apart (the rollout record's tokens; a finished
+ *             row holds pad there, which is what HF feeds)
+ *   h, y    : [B, D] of `dtype`, rows ld_h / ld_y >= D apart; y NULL iff norm_w NULL
+ * With a clock the step is live iff 0 <= t < clock T and t - 1 < a->T.  A dead step writes zeros
+ * to h and y and reads neither tokens nor weight.  Stream-ordered, no sync, nothing allocated.
+ * Refused before any launch, the outputs untouched — TRLX_ERR_ARG: a NULL a / weight / tokens /
+ * h, y without norm_w or norm_w without y, a weight / h / y / norm_w not aligned to its element
+ * or tokens / clock not aligned to 8 bytes, a NaN eps, a host t outside [0, T], h or y
+ * overlapping any other operand; TRLX_ERR_SHAPE: D outside [1, 8192], B, V or T < 1;
+ * TRLX_ERR_STRIDE: ld_w, ld_h or ld_y below D, ld_tokens below T; TRLX_ERR_DTYPE: a dtype other
+ * than TRLX_F32 / TRLX_BF16. */
+typedef struct TrlxT5DecodeEmbedArgs {
+    const void* weight;               /* [V, D] */
+    int64_t ld_w;
+    const int64_t* tokens;            /* [B, T] */
+    int64_t ld_tokens;
+    const void* norm_w;               /* [D], or NULL: no y */
+    void* h;                          /* [B, D] */
+    int64_t ld_h;
+    void* y;                          /* [B, D], or NULL */
+    int64_t ld_y;
+    int64_t B;
+    int64_t D;                        /* 1..8192 */
+    int64_t V;
+    int64_t T;                        /* columns of tokens */
+    int64_t t;                        /* host t in [0, T]; not read with a clock */
+    int64_t start_token_id;           /* the token of t == 0 */
+    float eps;
+    int dtype;                        /* TRLX_F32 / TRLX_BF16: weight, norm_w, h, y */
+} TrlxT5DecodeEmbedArgs;
+int trlx_t5_decode_embed(const TrlxT5DecodeEmbedArgs* a, const int64_t* clock, void* stream);
+
 /* ---------------------------------------------------------------- T5 full-sequence attention
  * Many queries against many keys under T5's rules, forward only — replaces the body of HF's
  * T5Attention between the q / k / v projections and the `o` projection (a [B, nH, Tq, S] matmul,

@@ -1,0 +1,259 @@
+"""The captured decode step of tools/t5_decode_graph_bench.py made autoregressive: the token drawn at
+step t - 1 is fed back through the `shared` embedding table, and the rows that have finished are
+skipped in both attentions.  Three routes, each ONE captured step (torch.cuda.graph) replayed once
+per token:
+
+  c0_torch_feedback   the feedback as torch ops (a gather of rec.tokens at an index tensor derived
+                      from clock.record, a where for t == 0, F.embedding), then t5_rmsnorm; no skip
+  c1_decode_embed     t5_decode_embed(clock): the gather, the embedding row and layer 0's first norm
+                      in one launch; no skip
+  c2_embed_live_skip  c1 plus live=rec.unfinished on the self- and the cross-attention of every layer
+
+The decoder is the graph bench's (L 12, nH 12, d_kv 64, D 768, F 2048 gated, V 32128, S 512, T 48,
+bf16, at B 256 and B 8) with a `shared` [V, D] table.  The recorder is built with eos_token_id=None
+and rec.unfinished is preset to a fixed pattern, so the sampler never changes it; every route runs at
+live fractions 1.0, 0.52 (the share of valid positions of the C3 ragged batch) and 0.25.
+
+All (route, fraction) pairs run interleaved in one process, their order shuffled per repetition;
+each sample is a whole T-token rollout between two HIP events; the figure is the median of --reps
+rollouts with min-max, in ms per token.  No speed-up is assumed: the output names the fastest route
+per shape and fraction and says where c2 does not beat c1 or c1 does not beat c0.
+
+--parent-lib PATH: also the A/B of the entries that existed before (trlx_t5_decode_attn, self at
+t 47 and cross at S 512 with the key mask, T5-base B 256) against another build of the library, in
+alternating child processes, four runs each: this tree's median must lie inside the other build's
+own min-max spread, else it is reported as a regression with both spreads.
+
+    python tools/t5_rollout_bench.py [--parent-lib other/libtrlx_t5_amd.so]
+"""
+import argparse
+import ctypes
+import json
+import os
+import random
+import statistics
+import subprocess
+import sys
+
+import torch
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import t5_decode_graph_bench as G  # noqa: E402  (the decoder; it loads the package)
+
+P = G.P
+_lib = G._lib
+L, NH, DKV, D, FF, V, S, T, INNER, DT = G.L, G.NH, G.DKV, G.D, G.F, G.V, G.S, G.T, G.INNER, G.DT
+FRACTIONS = (1.0, 0.52, 0.25)
+START = 0
+
+
+class RolloutDecoder(G.Decoder):
+    """The graph bench's decoder with the token feedback in front of it."""
+
+    def __init__(self, B, dev):
+        super().__init__(B, dev)
+        g = torch.Generator(device=dev).manual_seed(B + 1)
+        self.shared = torch.randn(V, D, generator=g, device=dev).to(DT)
+        self.start = torch.full((B,), START, dtype=torch.int64, device=dev)
+
+    def state(self):
+        clock, caches, rec = self.rollout_state(True)
+        out = (torch.empty(self.B, D, dtype=DT, device=self.dev), torch.empty(self.B, D, dtype=DT, device=self.dev))
+        return clock, caches, rec, out
+
+    def feed_torch(self, state):
+        clock, _, rec, _ = state
+        t = clock.record[0:1]
+        idx = (t - 1).clamp_min(0).expand(self.B).unsqueeze(1)
+        tok = torch.where(t == 0, self.start, rec.tokens.gather(1, idx).squeeze(1))
+        h = F.embedding(tok, self.shared)
+        return h, P.t5_rmsnorm(h, self.layers[0]["ln"][0])
+
+    def feed_kernel(self, state):
+        clock, _, rec, out = state
+        return P.t5_decode_embed(self.shared, rec, clock, START, self.layers[0]["ln"][0], out=out)
+
+    def token(self, state, route):
+        clock, caches, rec, _ = state
+        h, y = self.feed_torch(state) if route == "c0_torch_feedback" else self.feed_kernel(state)
+        kw = dict(live=rec.unfinished) if route == "c2_embed_live_skip" else {}
+        for i, w in enumerate(self.layers):
+            qkv = torch.matmul(y, w["qkv"])
+            q, kn, vn = (qkv[:, j * INNER:(j + 1) * INNER] for j in range(3))
+            a = P.t5_decode_self_attention(q, kn, vn, caches[i], clock, self.table, **kw)
+            h, y = P.t5_add_rmsnorm(torch.matmul(a, w["o"]), h, w["ln"][1])
+            c = P.t5_decode_cross_attention(torch.matmul(y, w["cq"]), w["k_enc"], w["v_enc"], self.mask, **kw)
+            h, y = P.t5_add_rmsnorm(torch.matmul(c, w["co"]), h, w["ln"][2])
+            f = P.t5_ff_act_packed(torch.matmul(y, w["wi"]))
+            nxt = self.layers[i + 1]["ln"][0] if i + 1 < L else self.final_ln
+            h, y = P.t5_add_rmsnorm(torch.matmul(f, w["wo"]), h, nxt)
+        logits, ref = torch.matmul(y, self.lm), torch.matmul(y, self.ref_lm)
+        P.ppo_sample_step(logits, ref_logits=ref, recorder=rec, u=self.u, out=self.out, top_k=50, top_p=0.95)
+        clock.advance()
+
+
+ROUTES = ("c0_torch_feedback", "c1_decode_embed", "c2_embed_live_skip")
+
+
+def live_pattern(B, frac, dev):
+    """round(B * frac) live rows at fixed, scattered places."""
+    n = max(1, round(B * frac))
+    perm = torch.randperm(B, generator=torch.Generator().manual_seed(17))
+    live = torch.zeros(B, dtype=torch.int64)
+    live[perm[:n]] = 1
+    return live.to(dev), n / B
+
+
+def run_shape(B, dev, reps):
+    dec = RolloutDecoder(B, dev)
+    patterns = {f: live_pattern(B, f, dev) for f in FRACTIONS}
+    states, graphs = {}, {}
+    with torch.no_grad():
+        for r in ROUTES:
+            st = states[r] = dec.state()
+            dec.token(st, r)                                      # warm-up
+            torch.cuda.synchronize()
+            st[0].reset()
+            graphs[r] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[r]):                     # one stream, a linear chain of launches
+                dec.token(st, r)
+
+        def rollout(r, f):
+            clock, _, rec, _ = states[r]
+            clock.reset()
+            rec.unfinished.copy_(patterns[f][0])
+            for _ in range(T):
+                graphs[r].replay()
+
+        # the three routes record the same tokens for the rows that are live (fraction 1.0: every row)
+        for r in ROUTES:
+            rollout(r, 1.0)
+        torch.cuda.synchronize()
+        same = all(torch.equal(getattr(states[ROUTES[0]][2], f), getattr(states[r][2], f))
+                   for r in ROUTES[1:] for f in ("tokens", "logprobs", "ref_logprobs"))
+        assert all(states[r][0].t == T and states[r][0].overrun == 0 for r in ROUTES)
+        keys = [(r, f) for r in ROUTES for f in FRACTIONS]
+        samples = {k: [] for k in keys}
+        rng = random.Random(B)
+        for _ in range(reps):
+            rng.shuffle(keys)
+            for r, f in keys:
+                clock, _, rec, _ = states[r]
+                clock.reset()
+                rec.unfinished.copy_(patterns[f][0])
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(T):
+                    graphs[r].replay()
+                e1.record()
+                e1.synchronize()
+                samples[(r, f)].append(e0.elapsed_time(e1) / T)
+    res = {"routes_record_the_same_rollout_at_fraction_1": bool(same)}
+    for f in FRACTIONS:
+        per = {r: {"ms_per_token_median": statistics.median(samples[(r, f)]), "min": min(samples[(r, f)]),
+                   "max": max(samples[(r, f)])} for r in ROUTES}
+        med = {r: per[r]["ms_per_token_median"] for r in ROUTES}
+        per["live_fraction_actual"] = patterns[f][1]
+        per["fastest"] = min(ROUTES, key=med.get)
+        per["c1_beats_c0"] = med["c1_decode_embed"] < med["c0_torch_feedback"]
+        per["c2_beats_c1"] = med["c2_embed_live_skip"] < med["c1_decode_embed"]
+        res[f"live_{f}"] = per
+    return res
+
+
+# ------------------------------------------------------------------ the entries that existed before
+def ab_child():
+    """Per-call µs of trlx_t5_decode_attn (self, cross) on whatever library TRLX_T5_AMD_LIB names."""
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for n in [n for n in _lib.SIGNATURES if not hasattr(lib, n)]:   # an older build lacks the newer entries
+        del _lib.SIGNATURES[n]
+    dev = torch.device("cuda:0")
+    B, t = 256, 47
+    g = torch.Generator(device=dev).manual_seed(3)
+    cache = P.T5DecodeKVCache(B, NH, DKV, T, DT, dev)
+    cache.k.copy_(torch.randn(cache.k.shape, generator=g, device=dev) * DKV ** -0.25)
+    cache.v.copy_(torch.randn(cache.v.shape, generator=g, device=dev))
+    qkv = (torch.randn(B, 3 * INNER, generator=g, device=dev) * DKV ** -0.25).to(DT)
+    q, kn, vn = (qkv[:, j * INNER:(j + 1) * INNER] for j in range(3))
+    table = P.t5_relative_bias_table(torch.randn(32, NH, generator=g, device=dev), T)
+    k_enc = (torch.randn(B, NH, S, DKV, generator=g, device=dev) * DKV ** -0.25).to(DT)
+    v_enc = torch.randn(B, NH, S, DKV, generator=g, device=dev).to(DT)
+    mask = torch.ones(B, S, dtype=torch.int64, device=dev)
+    mask[:, S - 37:] = 0
+
+    def self_attn():
+        P.t5_decode_self_attention(q, kn, vn, cache, t, table)
+
+    def cross_attn():
+        P.t5_decode_cross_attention(q, k_enc, v_enc, mask)
+
+    res = {}
+    for name, fn in (("t5_decode_attn_self_B256_t47", self_attn), ("t5_decode_attn_cross_B256_S512", cross_attn)):
+        for _ in range(20):
+            fn()
+        per = []
+        for _ in range(30):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(20):
+                fn()
+            e1.record()
+            e1.synchronize()
+            per.append(e0.elapsed_time(e1) * 1000.0 / 20)
+        res[name] = statistics.median(per)
+    print("AB_CHILD " + json.dumps(res))
+
+
+def existing_entries_ab(parent_lib, runs=4):
+    sides = {"parent": os.path.abspath(parent_lib), "this_tree": _lib.LIB_PATH}
+    got = {s: {} for s in sides}
+    for _ in range(runs):
+        for side, lib in sides.items():   # alternating child processes
+            env = dict(os.environ, TRLX_T5_AMD_LIB=lib)
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--ab-child"], env=env, capture_output=True,
+                               text=True, timeout=300, check=True)
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("AB_CHILD ")][-1]
+            for k, v in json.loads(line[len("AB_CHILD "):]).items():
+                got[side].setdefault(k, []).append(v)
+    out = {"unit": "us per call (HIP events around 20 calls, median of 30), one figure per child process",
+           "criterion": "this tree's median inside the parent's own min-max spread"}
+    for k in got["parent"]:
+        p, c = got["parent"][k], got["this_tree"][k]
+        med = statistics.median(c)
+        out[k] = {"parent": p, "this_tree": c, "parent_spread": [min(p), max(p)], "this_tree_spread": [min(c), max(c)],
+                  "this_tree_median": med, "inside_parent_spread": min(p) <= med <= max(p),
+                  "verdict": "inside" if min(p) <= med <= max(p) else ("faster" if med < min(p) else "REGRESSION")}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--batches", default="256,8")
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--ab-child", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "t5_rollout_bench.json"))
+    args = ap.parse_args()
+    if args.ab_child:
+        return ab_child()
+    result = {"tool": "tools/t5_rollout_bench.py",
+              "shape": dict(L=L, n_heads=NH, d_kv=DKV, D=D, F=FF, V=V, S=S, T=T, dtype="bf16"),
+              "timing": f"HIP events around whole {T}-token rollouts, (route, live fraction) pairs interleaved and "
+                        f"shuffled per repetition, median of {args.reps}, ms per token"}
+    if args.parent_lib:   # first: no GPU context in this process while the children run
+        result["existing_entries_ab"] = existing_entries_ab(args.parent_lib)
+        print(json.dumps(result["existing_entries_ab"]))
+    dev = torch.device("cuda:0")
+    result["device"] = torch.cuda.get_device_name(0)
+    for B in (int(b) for b in args.batches.split(",")):
+        result[f"B{B}"] = run_shape(B, dev, args.reps)
+        print(f"B {B}: " + json.dumps(result[f"B{B}"]))
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

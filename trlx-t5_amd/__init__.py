@@ -44,6 +44,10 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
   T5DecodeClock — the decode position t as a device record: t5_decode_self_attention(t=clock) and
       ppo_sample_step(recorder=PPORolloutRecorder(..., clock=clock)) read it on the device, so one
       captured decode step (torch.cuda.graph) replays for every token; clock.advance() ends a step
+  t5_decode_embed — the decoder's input row of a decode step in one launch: the token drawn at the
+      step before (read from the recorder on the device), the embedding row, layer 0's first norm;
+      with `live=recorder.unfinished` both decode attentions skip the rows that have drawn eos
+      (the token feedback and the finished rows of HF generate, ppo_orchestrator.py:76)
   t5_attention, t5_relative_bias_offsets — T5's attention over whole sequences (encoder
       self-attention, teacher-forced decoder self- and cross-attention) as one flash-attention
       launch on MFMA: bias, key mask and causal rule inside, no [Tq, S] tensor
@@ -83,8 +87,8 @@ from .ilql_store import ILQLElement, ILQLRolloutStorage
 from .value_head import ValueHead, value_head, value_head_splits
 from .value_head import make_head as make_value_head
 from .sampling import PPOLogitsProcessors, ppo_sample_step
-from .t5_decode import (T5DecodeClock, T5DecodeKVCache, t5_decode_cross_attention, t5_decode_self_attention,
-                        t5_relative_bias_table)
+from .t5_decode import (T5DecodeClock, T5DecodeKVCache, t5_decode_cross_attention, t5_decode_embed,
+                        t5_decode_self_attention, t5_relative_bias_table)
 from .t5_attention import t5_attention, t5_attention_train, t5_relative_bias_buckets, t5_relative_bias_offsets
 from .t5_ff import T5FeedForward, t5_ff_act, t5_ff_act_packed
 from .t5_norm import T5LayerNorm, t5_add_rmsnorm, t5_rmsnorm
@@ -106,6 +110,7 @@ __all__ = [
     "ValueHead", "value_head", "value_head_splits", "make_value_head",
     "FusedAdamW", "adamw_step", "clip_grad_norm_", "schedule_table",
     "T5DecodeKVCache", "T5DecodeClock", "t5_decode_self_attention", "t5_decode_cross_attention", "t5_relative_bias_table",
+    "t5_decode_embed",
     "t5_attention", "t5_relative_bias_offsets", "t5_attention_train", "t5_relative_bias_buckets",
     "t5_ff_act", "t5_ff_act_packed", "T5FeedForward",
     "t5_rmsnorm", "t5_add_rmsnorm", "T5LayerNorm",

@@ -102,6 +102,16 @@ class T5DecodeAttnArgs(ctypes.Structure):
     ]
 
 
+class T5DecodeEmbedArgs(ctypes.Structure):
+    """Mirror of TrlxT5DecodeEmbedArgs (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("weight", _c_vp), ("ld_w", _c_i64), ("tokens", _c_vp), ("ld_tokens", _c_i64), ("norm_w", _c_vp),
+        ("h", _c_vp), ("ld_h", _c_i64), ("y", _c_vp), ("ld_y", _c_i64),
+        ("B", _c_i64), ("D", _c_i64), ("V", _c_i64), ("T", _c_i64), ("t", _c_i64), ("start_token_id", _c_i64),
+        ("eps", _c_f), ("dtype", _c_int),
+    ]
+
+
 class T5AttentionArgs(ctypes.Structure):
     """Mirror of TrlxT5AttentionArgs (include/trlx_t5_amd.h)."""
     _fields_ = [
@@ -345,6 +355,8 @@ SIGNATURES = {
     "trlx_decode_clock_init": (_c_int, [_c_vp, _c_i64, _c_i64, _c_vp]),
     "trlx_decode_clock_advance": (_c_int, [_c_vp, _c_vp]),
     "trlx_t5_decode_attn_dev": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp, _c_vp]),
+    "trlx_t5_decode_attn_live": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp, _c_vp, _c_vp]),
+    "trlx_t5_decode_embed": (_c_int, [ctypes.POINTER(T5DecodeEmbedArgs), _c_vp, _c_vp]),
     "trlx_t5_attention": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp]),
     "trlx_t5_attention_tiles": (_c_int, [ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),
     "trlx_t5_attention_fwd_lse": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp, _c_vp]),

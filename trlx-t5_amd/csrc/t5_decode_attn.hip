@@ -43,8 +43,31 @@ struct T5AttnDevArgs {
     T5AttnArgs a;
     const int64_t* clock;
 };
+// The live-row step (trlx_t5_decode_attn_live): live[b] == 0 skips row b; clock as above or NULL.
+struct T5AttnLiveArgs {
+    T5AttnArgs a;
+    const int64_t* clock;
+    const int64_t* live;    // [B]
+};
 __device__ __forceinline__ const T5AttnArgs& t5_args(const T5AttnArgs& a) { return a; }
 __device__ __forceinline__ const T5AttnArgs& t5_args(const T5AttnDevArgs& a) { return a.a; }
+__device__ __forceinline__ const T5AttnArgs& t5_args(const T5AttnLiveArgs& a) { return a.a; }
+
+// zeros to out[b, h, :]: what a dead step and a skipped row store
+template <class E, int DKV>
+__device__ __forceinline__ void t5_zero_out(void* out, int bh) {
+    if (threadIdx.x < DKV / 2) {
+        const int64_t o = int64_t(bh) * DKV + 2 * threadIdx.x;
+        if (sizeof(E) == 2) {
+            *reinterpret_cast<uint32_t*>(static_cast<uint16_t*>(out) + o) = 0u;
+        } else {
+            float2 z;
+            z.x = 0.f;
+            z.y = 0.f;
+            *reinterpret_cast<float2*>(static_cast<float*>(out) + o) = z;
+        }
+    }
+}
 
 template <class DT>
 __device__ __forceinline__ vec4u t5_ld(const typename DT::elem_t* p) {
@@ -56,9 +79,13 @@ __device__ __forceinline__ vec4u t5_ld(const typename DT::elem_t* p) {
 // the workgroup (uniform loads from a kernel-argument pointer).  A step with t outside
 // [0, min(T, max_len)) is dead: zeros to out[b, h, :] and out, before any address is formed from t
 // and before any barrier; the exit is uniform.  DEVT = false compiles to the kernel without it.
-template <class DT, int DKV, int MODE, bool DEVT = false>
+// LIVE: the workgroup loads live[b] first, one uniform load; a row with live[b] == 0 gets zeros in
+// out[b, h, :] and the workgroup leaves, before any barrier and before any address is formed into
+// q, k_new, v_new, the cache, the mask or the bias: column t of a skipped row stays unwritten.  A
+// row with live[b] != 0 runs the code below unchanged.  LIVE = false compiles to the kernel without it.
+template <class DT, int DKV, int MODE, bool DEVT = false, bool LIVE = false>
 __global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn(
-    const std::conditional_t<DEVT, T5AttnDevArgs, T5AttnArgs> args) {
+    const std::conditional_t<LIVE, T5AttnLiveArgs, std::conditional_t<DEVT, T5AttnDevArgs, T5AttnArgs>> args) {
     static_assert(!DEVT || MODE == kT5Self, "only the self-attention reads t");
     const T5AttnArgs& a = t5_args(args);
     typedef typename DT::elem_t E;
@@ -77,22 +104,18 @@ __global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn(
     const int sl = lane % LPR;                 // this lane's vector of the row
     const int gg = wave * KPW + lane / LPR;    // group id in the workgroup
     const int col = h * DKV + sl * EPV;
+    if constexpr (LIVE) {
+        if (args.live[b] == 0) {   // block-uniform
+            t5_zero_out<E, DKV>(a.out, bh);
+            return;
+        }
+    }
     [[maybe_unused]] int t_clock = 0;
     if constexpr (DEVT) {
         const int64_t tc = args.clock[TRLX_CLOCK_T], cap = args.clock[TRLX_CLOCK_CAP];
         const int64_t lim = cap < int64_t(a.max_len) ? cap : int64_t(a.max_len);
         if (tc < 0 || tc >= lim) {   // block-uniform
-            if (threadIdx.x < DKV / 2) {
-                const int64_t o = int64_t(bh) * DKV + 2 * threadIdx.x;
-                if (sizeof(E) == 2) {
-                    *reinterpret_cast<uint32_t*>(static_cast<uint16_t*>(a.out) + o) = 0u;
-                } else {
-                    float2 z;
-                    z.x = 0.f;
-                    z.y = 0.f;
-                    *reinterpret_cast<float2*>(static_cast<float*>(a.out) + o) = z;
-                }
-            }
+            t5_zero_out<E, DKV>(a.out, bh);
             return;
         }
         t_clock = int(tc);
@@ -319,4 +342,40 @@ extern "C" int trlx_t5_decode_attn_dev(const TrlxT5DecodeAttnArgs* a, const int6
     hipLaunchKernelGGL(t5_pick_clock(a->dtype, a->d_kv), dim3(unsigned(a->B * a->n_heads)), dim3(kT5Threads), 0,
                        (hipStream_t)stream, k);
     return check_launch("k_t5_decode_attn<clock>");
+}
+
+typedef void (*t5_live_kernel_t)(const T5AttnLiveArgs);
+template <class DT, int DKV>
+static t5_live_kernel_t t5_pick_live_mode(int mode, bool clock) {
+    if (mode == kT5Self)
+        return clock ? k_t5_decode_attn<DT, DKV, kT5Self, true, true> : k_t5_decode_attn<DT, DKV, kT5Self, false, true>;
+    return mode == kT5Cross ? k_t5_decode_attn<DT, DKV, kT5Cross, false, true>
+                            : k_t5_decode_attn<DT, DKV, kT5CrossMasked, false, true>;
+}
+static t5_live_kernel_t t5_pick_live(int dtype, int64_t d_kv, int mode, bool clock) {
+    if (dtype == TRLX_BF16)
+        return d_kv == 64 ? t5_pick_live_mode<BF16T, 64>(mode, clock) : t5_pick_live_mode<BF16T, 128>(mode, clock);
+    return d_kv == 64 ? t5_pick_live_mode<F32T, 64>(mode, clock) : t5_pick_live_mode<F32T, 128>(mode, clock);
+}
+
+extern "C" int trlx_t5_decode_attn_live(const TrlxT5DecodeAttnArgs* a, const int64_t* live, const int64_t* clock,
+                                        void* stream) {
+    TRLX_REQUIRE(a, TRLX_ERR_ARG, "t5 decode attention: NULL arguments");
+    TRLX_REQUIRE(live, TRLX_ERR_ARG, "t5 decode attention, live rows: NULL live");
+    TRLX_REQUIRE((reinterpret_cast<uintptr_t>(live) & 7u) == 0, TRLX_ERR_ARG,
+                 "t5 decode attention, live rows: live is not aligned to 8 bytes");
+    TRLX_REQUIRE(!clock || a->mode == TRLX_T5_ATTN_SELF, TRLX_ERR_ARG,
+                 "t5 decode attention, live rows: a clock with mode %d (the self-attention only; the cross step "
+                 "reads no t)", a->mode);
+    TRLX_REQUIRE((reinterpret_cast<uintptr_t>(clock) & 7u) == 0, TRLX_ERR_ARG,
+                 "t5 decode attention, live rows: the clock is not aligned to 8 bytes");
+    T5AttnLiveArgs k;
+    const int rc = t5_decode_attn_prepare(a, clock != nullptr, &k.a);
+    if (rc) return rc;
+    k.clock = clock;
+    k.live = live;
+    const int mode = a->mode == TRLX_T5_ATTN_SELF ? kT5Self : a->key_mask ? kT5CrossMasked : kT5Cross;
+    hipLaunchKernelGGL(t5_pick_live(a->dtype, a->d_kv, mode, clock != nullptr), dim3(unsigned(a->B * a->n_heads)),
+                       dim3(kT5Threads), 0, (hipStream_t)stream, k);
+    return check_launch("k_t5_decode_attn<live>");
 }

@@ -22,6 +22,8 @@
 // fp32 operations in the same order on the same values, so they give the same bits.
 #include <string.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace trlx {
@@ -346,9 +348,182 @@ static int rn_no_overlap(const char* who, const RnOp* ops, int nops, const char*
     return TRLX_OK;
 }
 
+// ------------------------------------------------------------------ the decoder's input row of a decode step
+// trlx_t5_decode_embed: h[b, :] = weight[tok_b, :] with tok_b the token drawn at step t - 1 (the
+// start token at t = 0), and, with a norm weight, y[b, :] = the forward above on that row -- the
+// same RnTile, the same sum, rn_rstd and the same product, so y has the bits of k_t5_rmsnorm_fwd on
+// h.  The row stays in registers between the gather and the two stores.
+struct EmbArgs {
+    const void* weight;
+    const int64_t* tokens;
+    const void* w;          // the norm weight or NULL
+    void *h, *y;
+    int64_t ld_w, ld_tokens, ld_h, ld_y;
+    int64_t B, nblk, V, T, t, start;
+    int D;
+    float eps;
+};
+// The device-clock step: t comes from the decode clock, a.t is not read.
+struct EmbDevArgs {
+    EmbArgs a;
+    const int64_t* clock;
+};
+__device__ __forceinline__ const EmbArgs& emb_args(const EmbArgs& a) { return a; }
+__device__ __forceinline__ const EmbArgs& emb_args(const EmbDevArgs& a) { return a.a; }
+
+// DEVT: t and the capacity are loaded from the clock once, at the top of the workgroup.  The step is
+// live iff 0 <= t < capacity and t - 1 < T (the columns of `tokens`); a dead step stores zeros to h
+// and y and leaves, before any address is formed from t and before any barrier (the exit is
+// uniform).  A token outside [0, V) is tested before any address is formed from it: a zero row.
+template <class DT, bool VEC, int TEAM, int E, bool NORM, bool DEVT>
+__global__ __launch_bounds__(kRnThreads) void k_t5_decode_embed(const std::conditional_t<DEVT, EmbDevArgs, EmbArgs> args) {
+    typedef RnTile<DT, VEC, TEAM, E> T;
+    __shared__ float sh[2 * (kRnThreads / kWave)];
+    const EmbArgs& k = emb_args(args);
+    const T t(k.D);
+    int64_t step = k.t;
+    if constexpr (DEVT) {
+        const int64_t tc = args.clock[TRLX_CLOCK_T], cap = args.clock[TRLX_CLOCK_CAP];
+        if (tc < 0 || tc >= cap || tc - 1 >= k.T) {   // block-uniform
+            float z[E];
+#pragma unroll
+            for (int i = 0; i < E; ++i) z[i] = 0.f;
+#pragma unroll 1
+            for (int64_t b = blockIdx.x; b < k.nblk; b += gridDim.x) {
+                const int64_t row = b * T::RPB + t.rib;
+                if (T::RPB > 1 && row >= k.B) continue;
+                t.store(k.h, row * k.ld_h, z);
+                if constexpr (NORM) t.store(k.y, row * k.ld_y, z);
+            }
+            return;
+        }
+        step = tc;
+    }
+    int turn = 0;
+    float w[NORM ? E : 1];
+    if constexpr (NORM) t.load(k.w, 0, w);
+#pragma unroll 1
+    for (int64_t b = blockIdx.x; b < k.nblk; b += gridDim.x) {
+        const int64_t row = b * T::RPB + t.rib;
+        if (T::RPB > 1 && row >= k.B) continue;                // a whole wave: no barrier in this form
+        const int64_t tok = step == 0 ? k.start : k.tokens[row * k.ld_tokens + step - 1];
+        float f[E];
+        if (tok >= 0 && tok < k.V) {                           // uniform over the row's team
+            t.load(k.weight, tok * k.ld_w, f);
+        } else {
+#pragma unroll
+            for (int i = 0; i < E; ++i) f[i] = 0.f;
+        }
+        t.store(k.h, row * k.ld_h, f);
+        if constexpr (NORM) {
+            const float rstd = rn_rstd(t.sum(rn_sumsq(f), sh, turn), k.D, k.eps);
+#pragma unroll
+            for (int i = 0; i < E; ++i) f[i] = w[i] * (f[i] * rstd);
+            t.store(k.y, row * k.ld_y, f);
+        }
+    }
+}
+
+template <bool DEVT>
+using emb_kernel_t = void (*)(const std::conditional_t<DEVT, EmbDevArgs, EmbArgs>);
+
+template <class DT, bool VEC, bool NORM, bool DEVT>
+static emb_kernel_t<DEVT> emb_pick_form(int form) {
+    switch (form) {
+        case 0: return k_t5_decode_embed<DT, VEC, kWave, 8, NORM, DEVT>;
+        case 1: return k_t5_decode_embed<DT, VEC, kWave, 16, NORM, DEVT>;
+        case 2: return k_t5_decode_embed<DT, VEC, kRnThreads, 8, NORM, DEVT>;
+        case 3: return k_t5_decode_embed<DT, VEC, kRnThreads, 16, NORM, DEVT>;
+        default: return k_t5_decode_embed<DT, VEC, kRnThreads, 32, NORM, DEVT>;
+    }
+}
+template <bool DEVT>
+static emb_kernel_t<DEVT> emb_pick(bool bf, int form, bool vec, bool norm) {
+    if (bf) {
+        if (vec) return norm ? emb_pick_form<BF16T, true, true, DEVT>(form) : emb_pick_form<BF16T, true, false, DEVT>(form);
+        return norm ? emb_pick_form<BF16T, false, true, DEVT>(form) : emb_pick_form<BF16T, false, false, DEVT>(form);
+    }
+    if (vec) return norm ? emb_pick_form<F32T, true, true, DEVT>(form) : emb_pick_form<F32T, true, false, DEVT>(form);
+    return norm ? emb_pick_form<F32T, false, true, DEVT>(form) : emb_pick_form<F32T, false, false, DEVT>(form);
+}
+
+// One operand of trlx_t5_decode_embed as a byte range.
+struct EmbOp {
+    const char* name;
+    uintptr_t lo, hi;
+    bool written;
+};
+
 }  // namespace trlx
 
 using namespace trlx;
+
+extern "C" int trlx_t5_decode_embed(const TrlxT5DecodeEmbedArgs* a, const int64_t* clock, void* stream) {
+    const char* who = "t5 decode embed";
+    TRLX_REQUIRE(a, TRLX_ERR_ARG, "%s: NULL arguments", who);
+    TRLX_REQUIRE(a->dtype == TRLX_F32 || a->dtype == TRLX_BF16, TRLX_ERR_DTYPE, "%s: dtype %d (float32 and bfloat16 only)",
+                 who, a->dtype);
+    TRLX_REQUIRE(a->D >= 1 && a->D <= kRnMaxD, TRLX_ERR_SHAPE, "%s: D %lld (1 to %d: a row stays in registers)", who,
+                 (long long)a->D, kRnMaxD);
+    TRLX_REQUIRE(a->B >= 1 && a->B <= 0x7fffffffLL && a->V >= 1 && a->V <= 0x7fffffffLL && a->T >= 1 &&
+                     a->T <= 0x7fffffffLL,
+                 TRLX_ERR_SHAPE, "%s: B %lld, V %lld, T %lld (1 to 2^31 - 1 each)", who, (long long)a->B, (long long)a->V,
+                 (long long)a->T);
+    TRLX_REQUIRE(a->weight && a->tokens && a->h, TRLX_ERR_ARG, "%s: NULL weight / tokens / h", who);
+    TRLX_REQUIRE((a->y != nullptr) == (a->norm_w != nullptr), TRLX_ERR_ARG,
+                 "%s: y and norm_w go together (without a norm weight only h is written)", who);
+    TRLX_REQUIRE(a->eps == a->eps, TRLX_ERR_ARG, "%s: eps is NaN", who);
+    TRLX_REQUIRE(clock || (a->t >= 0 && a->t <= a->T), TRLX_ERR_ARG, "%s: t %lld outside [0, T = %lld]", who,
+                 (long long)a->t, (long long)a->T);
+    const int64_t esz = a->dtype == TRLX_BF16 ? 2 : 4, vw = 16 / esz;
+    const bool norm = a->norm_w != nullptr;
+    const int64_t ld_y = norm ? a->ld_y : a->D;
+    TRLX_REQUIRE(a->ld_w >= a->D && a->ld_h >= a->D && ld_y >= a->D, TRLX_ERR_STRIDE,
+                 "%s: row strides %lld (weight), %lld (h), %lld (y) below D = %lld", who, (long long)a->ld_w,
+                 (long long)a->ld_h, (long long)ld_y, (long long)a->D);
+    TRLX_REQUIRE(a->ld_tokens >= a->T, TRLX_ERR_STRIDE, "%s: tokens row stride %lld below T = %lld", who,
+                 (long long)a->ld_tokens, (long long)a->T);
+    TRLX_REQUIRE(a->ld_w <= (int64_t(1) << 28) && a->ld_h <= (int64_t(1) << 28) && ld_y <= (int64_t(1) << 28) &&
+                     a->ld_tokens <= (int64_t(1) << 28),
+                 TRLX_ERR_STRIDE, "%s: rows that far apart do not fit the address space", who);
+    const uintptr_t pw = reinterpret_cast<uintptr_t>(a->weight), ph = reinterpret_cast<uintptr_t>(a->h),
+                    py = reinterpret_cast<uintptr_t>(a->y), pn = reinterpret_cast<uintptr_t>(a->norm_w),
+                    pt = reinterpret_cast<uintptr_t>(a->tokens), pc = reinterpret_cast<uintptr_t>(clock);
+    TRLX_REQUIRE(pw % uintptr_t(esz) == 0 && ph % uintptr_t(esz) == 0 && py % uintptr_t(esz) == 0 &&
+                     pn % uintptr_t(esz) == 0,
+                 TRLX_ERR_ARG, "%s: weight / h / y / norm_w not aligned to the element", who);
+    TRLX_REQUIRE(pt % 8 == 0 && pc % 8 == 0, TRLX_ERR_ARG, "%s: tokens / clock not aligned to 8 bytes", who);
+    EmbOp ops[6];
+    int n = 0;
+    ops[n++] = {"weight", pw, pw + uintptr_t(((a->V - 1) * a->ld_w + a->D) * esz), false};
+    ops[n++] = {"tokens", pt, pt + uintptr_t(((a->B - 1) * a->ld_tokens + a->T) * 8), false};
+    ops[n++] = {"h", ph, ph + uintptr_t(((a->B - 1) * a->ld_h + a->D) * esz), true};
+    if (norm) {
+        ops[n++] = {"y", py, py + uintptr_t(((a->B - 1) * ld_y + a->D) * esz), true};
+        ops[n++] = {"norm_w", pn, pn + uintptr_t(a->D * esz), false};
+    }
+    if (clock) ops[n++] = {"clock", pc, pc + uintptr_t(TRLX_CLOCK_WORDS * 8), false};
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j)
+            TRLX_REQUIRE(i == j || !ops[i].written || ops[i].hi <= ops[j].lo || ops[j].hi <= ops[i].lo, TRLX_ERR_ARG,
+                         "%s: %s overlaps %s", who, ops[i].name, ops[j].name);
+    const bool vec = a->D % vw == 0 && pw % 16 == 0 && ph % 16 == 0 && py % 16 == 0 && pn % 16 == 0 &&
+                     a->ld_w % vw == 0 && a->ld_h % vw == 0 && ld_y % vw == 0;
+    EmbDevArgs k = {};
+    k.a.weight = a->weight, k.a.tokens = a->tokens, k.a.w = a->norm_w, k.a.h = a->h, k.a.y = a->y;
+    k.a.ld_w = a->ld_w, k.a.ld_tokens = a->ld_tokens, k.a.ld_h = a->ld_h, k.a.ld_y = ld_y;
+    k.a.B = a->B, k.a.nblk = rn_row_blocks(a->B, a->D), k.a.V = a->V, k.a.T = a->T, k.a.t = clock ? 0 : a->t;
+    k.a.start = a->start_token_id, k.a.D = int(a->D), k.a.eps = a->eps;
+    k.clock = clock;
+    const int form = rn_form(a->D);
+    const dim3 grid(unsigned(rn_partials(a->B, a->D))), block(kRnThreads);
+    const bool bf = a->dtype == TRLX_BF16;
+    if (clock)
+        hipLaunchKernelGGL(emb_pick<true>(bf, form, vec, norm), grid, block, 0, (hipStream_t)stream, k);
+    else
+        hipLaunchKernelGGL(emb_pick<false>(bf, form, vec, norm), grid, block, 0, (hipStream_t)stream, k.a);
+    return check_launch("k_t5_decode_embed");
+}
 
 extern "C" int trlx_t5_rmsnorm_geometry(int64_t N, int64_t D, TrlxT5RmsNormGeometry* g) {
     TRLX_REQUIRE(g, TRLX_ERR_ARG, "t5 rmsnorm geometry: NULL result");

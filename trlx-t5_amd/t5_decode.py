@@ -8,6 +8,11 @@
   t5_decode_cross_attention  attend over the encoder's keys under its key mask: one launch
   T5DecodeClock              the decode position t as a device record: t5_decode_self_attention(t=clock)
                              reads it on the device, so a captured decode step replays per token
+  t5_decode_embed            the decoder's input row of step t: the token drawn at step t - 1 (the
+                             start token at 0) through the embedding table and, optionally, layer
+                             0's first norm: one launch, t from a host int or the clock
+  live=                      both attentions skip the rows whose entry of `live` is 0 (the
+                             recorder's `unfinished`): zeros out, nothing read, the cache untouched
 
 Per layer and generated token HF's eager T5Attention spends, between the projections and `o`, a
 cache append, a [B, nH, 1, t] matmul, compute_bias (arange, bucket formula, embedding lookup,
@@ -28,7 +33,7 @@ import torch
 from . import _lib
 
 __all__ = ["t5_relative_bias_table", "T5DecodeKVCache", "T5DecodeClock", "t5_decode_self_attention",
-           "t5_decode_cross_attention"]
+           "t5_decode_cross_attention", "t5_decode_embed"]
 
 KERNEL_DTYPES = (torch.bfloat16, torch.float32)
 KERNEL_D_KV = (64, 128)
@@ -162,6 +167,17 @@ def _kernel_takes(dtype, d):
     return dtype in KERNEL_DTYPES and d in KERNEL_D_KV
 
 
+def _check_live(live, B, dtype, d, device):
+    """The `live` argument of both attentions: a contiguous int64 [B] tensor on the keys' device."""
+    if not isinstance(live, torch.Tensor):
+        raise TypeError(f"live must be a tensor, got {type(live).__name__}")
+    if live.dtype != torch.int64 or tuple(live.shape) != (B,) or live.device != device or not live.is_contiguous():
+        raise ValueError(f"live must be a contiguous int64 [B] = [{B}] tensor on {device}, got {live.dtype} "
+                         f"{tuple(live.shape)} on {live.device}")
+    if not _kernel_takes(dtype, d):
+        raise ValueError(f"live= needs the kernel ({KERNEL_DTYPES}, d_kv in {KERNEL_D_KV}); got {dtype}, d_kv {d}")
+
+
 def _torch_self_attention(q, k_new, v_new, cache, t, bias_table):
     """The same step as torch expressions, HF's op order: append, matmul, bias add, fp32 softmax
     cast back, matmul."""
@@ -186,7 +202,7 @@ def _torch_cross_attention(q, k_enc, v_enc, key_mask):
     return torch.matmul(w, v).reshape(B, nH * d)
 
 
-def t5_decode_self_attention(q, k_new, v_new, cache, t, bias_table=None):
+def t5_decode_self_attention(q, k_new, v_new, cache, t, bias_table=None, live=None):
     """The self-attention of decode step t: k_new / v_new go to column t of `cache`, the query
     attends over columns 0..t with score_j = q·k_j + bias_table[h, t - j].  Returns [B, nH*d_kv].
 
@@ -200,6 +216,14 @@ def t5_decode_self_attention(q, k_new, v_new, cache, t, bias_table=None):
     here: the caller's step ends with clock.advance().  With a clock, a dtype or d_kv the kernel
     does not take raises ValueError (the torch fallback slices by a host t).
     bias_table: t5_relative_bias_table(...) for the layer that owns the bias, or None.
+    live: None, or a contiguous int64 [B] tensor on the cache's device, 0 = skip the row
+    (PPORolloutRecorder.unfinished as it is): a skipped row returns zeros, none of its q / k_new /
+    v_new / cache is read and its column t of the cache stays unwritten; every other row has the
+    bits of the call without `live` (trlx_t5_decode_attn_live, kernels of their own; live=None
+    takes the entries it always took).  The skip is for recorders used with score_finished=False,
+    the default: with score_finished=True the sampler would score the pad of a row whose attention
+    was skipped.  Within one decode step every layer reads `live` before that step's sampling
+    launch writes it: all of them are on one stream, in that order.
     Runs on the current stream, no host sync; only the output is allocated."""
     if not isinstance(cache, T5DecodeKVCache):
         raise TypeError("cache must be a T5DecodeKVCache")
@@ -225,6 +249,8 @@ def t5_decode_self_attention(q, k_new, v_new, cache, t, bias_table=None):
                 or bias_table.device != cache.device or not bias_table.is_contiguous():
             raise ValueError(f"bias_table must be contiguous float32 [nH, max_len] = [{nH}, {cache.max_len}] on "
                              f"{cache.device}, got {bias_table.dtype} {tuple(bias_table.shape)}")
+    if live is not None:
+        _check_live(live, B, cache.dtype, d, cache.device)
     if not _kernel_takes(cache.dtype, d):
         return _torch_self_attention(q, k_new, v_new, cache, t, bias_table)
     _lib.require_cuda(cache.k, q, k_new, v_new)
@@ -235,14 +261,17 @@ def t5_decode_self_attention(q, k_new, v_new, cache, t, bias_table=None):
         k=cache.k.data_ptr(), v=cache.v.data_ptr(), bias_by_distance=_lib.ptr(bias_table), key_mask=None,
         out=out.data_ptr(), B=B, n_heads=nH, d_kv=d, max_len=cache.max_len, t=t,
         dtype=_lib.dtype_code(cache.k), mode=_lib.T5_ATTN_SELF)
-    if clock is not None:
+    if live is not None:
+        _lib.call("trlx_t5_decode_attn_live", ctypes.byref(args), live.data_ptr(),
+                  None if clock is None else clock.record.data_ptr(), _lib.stream_of(out))
+    elif clock is not None:
         _lib.call("trlx_t5_decode_attn_dev", ctypes.byref(args), clock.record.data_ptr(), _lib.stream_of(out))
     else:
         _lib.call("trlx_t5_decode_attn", ctypes.byref(args), _lib.stream_of(out))
     return out
 
 
-def t5_decode_cross_attention(q, k_enc, v_enc, key_mask=None):
+def t5_decode_cross_attention(q, k_enc, v_enc, key_mask=None, live=None):
     """The cross-attention of a decode step: score_j = q·k_enc_j over the keys with
     key_mask[b, j] != 0.  Returns [B, nH*d_kv].
 
@@ -250,7 +279,9 @@ def t5_decode_cross_attention(q, k_enc, v_enc, key_mask=None):
     transposed view contiguous once per rollout).  key_mask: int64 [B, S], 0 = masked (the
     encoder's attention_mask; holes allowed), or None.  Masked keys are excluded from the softmax
     and not read; a row with every key masked returns zeros, where HF's additive finfo.min mask
-    returns the plain average of the values.  q as in t5_decode_self_attention.
+    returns the plain average of the values.  q and live as in t5_decode_self_attention: a row
+    with live[b] == 0 returns zeros and none of its q, keys, values or mask is read -- the S keys
+    of a finished row are the larger part of what the skip saves.
     Runs on the current stream, no host sync; only the output is allocated."""
     if k_enc.dim() != 4 or k_enc.shape != v_enc.shape or k_enc.dtype != v_enc.dtype or k_enc.device != v_enc.device:
         raise ValueError("k_enc and v_enc must be [B, nH, S, d_kv] of one dtype on one device")
@@ -262,6 +293,8 @@ def t5_decode_cross_attention(q, k_enc, v_enc, key_mask=None):
         if tuple(key_mask.shape) != (B, S) or key_mask.dtype != torch.int64 or key_mask.device != k_enc.device:
             raise ValueError(f"key_mask must be int64 [B, S] = [{B}, {S}] on {k_enc.device}, got {key_mask.dtype} "
                              f"{tuple(key_mask.shape)}")
+    if live is not None:
+        _check_live(live, B, k_enc.dtype, d, k_enc.device)
     if not _kernel_takes(k_enc.dtype, d):
         return _torch_cross_attention(q, k_enc, v_enc, key_mask)
     _lib.require_cuda(k_enc, q)
@@ -275,5 +308,107 @@ def t5_decode_cross_attention(q, k_enc, v_enc, key_mask=None):
         q=q2.data_ptr(), ldq=ldq, k_new=None, ldk=0, v_new=None, ldv=0, k=k_enc.data_ptr(), v=v_enc.data_ptr(),
         bias_by_distance=None, key_mask=_lib.ptr(key_mask), out=out.data_ptr(), B=B, n_heads=nH, d_kv=d,
         max_len=S, t=0, dtype=_lib.dtype_code(k_enc), mode=_lib.T5_ATTN_CROSS)
-    _lib.call("trlx_t5_decode_attn", ctypes.byref(args), _lib.stream_of(out))
+    if live is not None:
+        _lib.call("trlx_t5_decode_attn_live", ctypes.byref(args), live.data_ptr(), None, _lib.stream_of(out))
+    else:
+        _lib.call("trlx_t5_decode_attn", ctypes.byref(args), _lib.stream_of(out))
     return out
+
+
+EMBED_MAX_D = 8192   # the row tile of csrc/t5_rmsnorm.hip
+
+
+def _torch_decode_embed(weight, tokens, t, start_token_id, norm_weight, eps):
+    """The same step as torch expressions: the gather, F.embedding with zero rows for ids outside
+    [0, V), HF's T5LayerNorm."""
+    from .t5_norm import _torch_rmsnorm
+    B, V = tokens.shape[0], weight.shape[0]
+    tok = torch.full((B,), int(start_token_id), dtype=torch.int64, device=tokens.device) if t == 0 else tokens[:, t - 1]
+    ok = (tok >= 0) & (tok < V)
+    h = torch.nn.functional.embedding(torch.where(ok, tok, torch.zeros_like(tok)), weight)
+    h = torch.where(ok[:, None], h, torch.zeros_like(h))
+    return h, (None if norm_weight is None else _torch_rmsnorm(h, norm_weight, eps))
+
+
+def t5_decode_embed(weight, tokens, t, start_token_id, norm_weight=None, eps=1e-6, out=None):
+    """The decoder's input row of decode step t, one launch (trlx_t5_decode_embed): returns (h, y).
+
+      tok = start_token_id at t == 0, else tokens[:, t - 1]      the token drawn at step t - 1
+      h   = weight[tok]                                           bit for bit; T5 applies no scale
+      y   = t5_rmsnorm(h, norm_weight, eps)                       bit for bit; None without norm_weight
+
+    weight: [V, D] bfloat16 / float32 with unit element stride, rows any stride >= D apart (HF's
+    shared.weight or a slice of it, read in place).  tokens: an int64 [B, T] tensor (row-strided
+    views are read in place) or a PPORolloutRecorder, whose `.tokens` is used: a finished row holds
+    pad there, which is what HF feeds.  A token outside [0, V) gives a zero row.  t: a host int in
+    [0, T], or a T5DecodeClock: the kernel then reads t on the device, nothing is read on the host,
+    the call is the same launch at every token and can be captured; the step is live iff
+    0 <= t < clock.T and t - 1 < T, and a dead step writes zeros to h and y.  The clock is not
+    advanced here.  norm_weight: [D] of weight's dtype, layer 0's first layer norm.  out=(h, y)
+    (y None without norm_weight): preallocated [B, D] outputs with unit element stride, written in
+    place, so that a captured step allocates nothing.  Forward only, current stream, no host sync.
+    On a CPU device (host t only), or for another dtype or D > 8192, the same step runs as torch
+    expressions."""
+    if hasattr(tokens, "tokens") and not isinstance(tokens, torch.Tensor):
+        tokens = tokens.tokens
+    if not isinstance(weight, torch.Tensor) or not isinstance(tokens, torch.Tensor):
+        raise TypeError("weight and tokens must be tensors (or tokens a PPORolloutRecorder)")
+    if weight.dim() != 2 or min(weight.shape) < 1:
+        raise ValueError(f"weight must be [V, D], got {tuple(weight.shape)}")
+    if tokens.dim() != 2 or tokens.dtype != torch.int64 or min(tokens.shape) < 1 or tokens.device != weight.device:
+        raise ValueError(f"tokens must be int64 [B, T] on {weight.device}, got {tokens.dtype} {tuple(tokens.shape)} "
+                         f"on {tokens.device}")
+    (V, D), (B, T) = weight.shape, tokens.shape
+    if norm_weight is not None and (not isinstance(norm_weight, torch.Tensor) or tuple(norm_weight.shape) != (D,) or
+                                    norm_weight.dtype != weight.dtype or norm_weight.device != weight.device):
+        raise ValueError(f"norm_weight must be [D] = [{D}] {weight.dtype} on {weight.device}")
+    clock = t if isinstance(t, T5DecodeClock) else None
+    if clock is not None:
+        if clock.device != weight.device:
+            raise ValueError(f"the clock is on {clock.device}, weight on {weight.device}")
+    else:
+        t = int(t)
+        if not 0 <= t <= T:
+            raise ValueError(f"t = {t} outside [0, T = {T}]")
+    kernel = weight.is_cuda and weight.dtype in KERNEL_DTYPES and D <= EMBED_MAX_D
+    if out is not None:
+        h, y = out
+        for name, o, want in (("h", h, True), ("y", y, norm_weight is not None)):
+            if (o is not None) != want:
+                raise ValueError(f"out = (h, y): {name} must be {'a tensor' if want else 'None'} "
+                                 f"{'with' if norm_weight is not None else 'without'} norm_weight")
+            if o is not None and (tuple(o.shape) != (B, D) or o.dtype != weight.dtype or o.device != weight.device or
+                                  o.stride(1) != 1):
+                raise ValueError(f"out: {name} must be [B, D] = [{B}, {D}] {weight.dtype} on {weight.device} with unit "
+                                 f"element stride")
+    if not kernel:
+        if clock is not None:
+            raise ValueError(f"t=clock needs the kernel (a ROCm device, {KERNEL_DTYPES}, D <= {EMBED_MAX_D}); the torch "
+                             f"fallback slices by a host t and cannot be captured")
+        h2, y2 = _torch_decode_embed(weight, tokens, t, start_token_id, norm_weight, eps)
+        if out is None:
+            return h2, y2
+        h.copy_(h2)
+        if y is not None:
+            y.copy_(y2)
+        return h, y
+    if weight.stride(1) != 1:
+        raise ValueError("weight must have unit element stride (rows may be any stride >= D apart)")
+    if tokens.stride(1) != 1 or (B > 1 and tokens.stride(0) < T):
+        tokens = tokens.contiguous()
+    if norm_weight is not None and not norm_weight.is_contiguous():
+        norm_weight = norm_weight.contiguous()
+    if out is None:
+        h = torch.empty(B, D, dtype=weight.dtype, device=weight.device)
+        y = torch.empty(B, D, dtype=weight.dtype, device=weight.device) if norm_weight is not None else None
+    def ld(x, n):   # a single row has no stride to speak of
+        return x.stride(0) if x.shape[0] > 1 else n
+
+    args = _lib.T5DecodeEmbedArgs(
+        weight=weight.data_ptr(), ld_w=ld(weight, D), tokens=tokens.data_ptr(), ld_tokens=ld(tokens, T),
+        norm_w=_lib.ptr(norm_weight), h=h.data_ptr(), ld_h=ld(h, D), y=_lib.ptr(y), ld_y=D if y is None else ld(y, D),
+        B=B, D=D, V=V, T=T, t=0 if clock is not None else t, start_token_id=int(start_token_id), eps=float(eps),
+        dtype=_lib.dtype_code(weight))
+    _lib.call("trlx_t5_decode_embed", ctypes.byref(args), None if clock is None else clock.record.data_ptr(),
+              _lib.stream_of(h))
+    return h, y
