@@ -1062,6 +1062,71 @@ int trlx_t5_decode_attn_dev(const TrlxT5DecodeAttnArgs* a, const int64_t* clock,
  * clock, t is not checked). */
 int trlx_t5_decode_attn_live(const TrlxT5DecodeAttnArgs* a, const int64_t* live, const int64_t* clock, void* stream);
 
+/* ---------------------------------------------------------------- fp8 encoder keys and values
+ * The encoder's projected keys and values are written once per rollout and read once per generated
+ * token and layer.  trlx_t5_cross_kv_quantize stores them as OCP e4m3fn bytes with one
+ * power-of-two scale per (batch row, head) and tensor; trlx_t5_decode_attn_kv8 is the cross step
+ * over those bytes: half the K / V traffic, fp32 arithmetic.  Opt-in and lossy against the bf16
+ * keys (e4m3 keeps 3 mantissa bits); exact against its own dequantised values (below).
+ *
+ * trlx_t5_cross_kv_quantize: ONE launch, K and V together, one workgroup per (b, h).
+ *   k, v     : bf16 [B, n_heads, S, d_kv] as a base pointer + element strides over (b, h, s), unit
+ *              stride along d_kv: a contiguous [B, nH, S, d] tensor (strides nH*S*d, S*d, d) and
+ *              the projection output [B, S, nH*d] (strides S*nH*d, d, nH*d) are both read in
+ *              place.  The stride of a dimension of size 1 is not read.
+ *   key_mask : int64 [B, S], 0 = masked, or NULL.
+ *   k8, v8   : bytes, contiguous [B, n_heads, S, d_kv].  k_scale, v_scale: fp32 [B, n_heads].
+ * Per (b, h), separately for K and V:
+ *   amax  = max |x| over the keys with key_mask != 0; a masked row is not read and is stored as
+ *           zero bytes
+ *   e     = the smallest integer with amax * 2^-e <= 448: with frexp(amax) = (m, x), x - 9 if
+ *           m <= 0.875, else x - 8; 0 for amax == 0; then clamped to [-100, 119]
+ *   scale = 2^e;  byte = e4m3fn(x * 2^-e), round to nearest, ties to even
+ * x * 2^-e is exact in fp32, and the rounding restates torch's .to(torch.float8_e4m3fn) in integer
+ * arithmetic, so the bytes are torch's cast of the scaled values bit for bit (torch's cast turns
+ * what lies above 464 into the NaN byte; only an amax above 448 * 2^119, past the upper clamp,
+ * gets there).  byte * scale is exactly representable in bf16: the attention below computes on values
+ * that the bf16 entries can be fed bit for bit.
+ * A live Inf or NaN in a (b, h) block of K (of V): that block's scale is NaN and each of its live
+ * bytes is 0x7f, the e4m3fn NaN; the attention then gives NaN for that (b, h) and no other.
+ * Refused with TRLX_ERR_ARG before any launch: NULL a / k / v / k8 / v8 / k_scale / v_scale, a
+ * d_kv other than 64 / 128, B, n_heads or S < 1, k / v / k8 / v8 not 16-byte aligned, a scale not
+ * 4-byte or key_mask not 8-byte aligned, a stride that is negative or not a whole number of
+ * 16-byte vectors, a head or key stride below d_kv. */
+typedef struct TrlxT5CrossKvQuantArgs {
+    const void* k;                    /* bf16 */
+    int64_t k_stride_b, k_stride_h, k_stride_s;
+    const void* v;                    /* bf16 */
+    int64_t v_stride_b, v_stride_h, v_stride_s;
+    const int64_t* key_mask;          /* [B, S] int64, 0 = masked, or NULL */
+    void* k8;                         /* [B, n_heads, S, d_kv] bytes */
+    void* v8;
+    float* k_scale;                   /* [B, n_heads] */
+    float* v_scale;
+    int64_t B;
+    int64_t n_heads;
+    int64_t S;
+    int64_t d_kv;                     /* 64 or 128 */
+} TrlxT5CrossKvQuantArgs;
+int trlx_t5_cross_kv_quantize(const TrlxT5CrossKvQuantArgs* a, void* stream);
+
+/* trlx_t5_decode_attn, mode TRLX_T5_ATTN_CROSS, over the quantiser's bytes: a->k and a->v are k8 and
+ * v8, a->dtype is TRLX_BF16 (q and out), every other field as in the cross mode.
+ *   score_j      = (q · k8_j) * k_scale[b, h]                  key_mask[b, j] != 0
+ *   out[b, h, :] = (sum_j p_j * v8_j) * v_scale[b, h] / sum_j p_j,   p_j = exp(score_j - max)
+ * The bytes are converted to fp32 in hardware; the dot, the online softmax and P·V are fp32, the
+ * result is rounded once.  Masked keys are not read; a row whose keys are all masked gives zeros.
+ * Fixed merge order: bit-reproducible, independent of B and of q's stride.
+ * live: NULL, or int64 [B] with the semantics of trlx_t5_decode_attn_live: a workgroup of a row
+ * with live[b] == 0 loads that one word, writes zeros to out[b, h, :] and returns before any
+ * barrier and before it forms any other address.  The launch takes the same arguments at every
+ * token: it captures as it is.
+ * Refused with TRLX_ERR_ARG before any launch: everything the cross mode of trlx_t5_decode_attn
+ * refuses (k and v not 16-byte aligned among it), mode TRLX_T5_ATTN_SELF, a dtype other than
+ * TRLX_BF16, a NULL scale or one not 4-byte aligned, a live not 8-byte aligned. */
+int trlx_t5_decode_attn_kv8(const TrlxT5DecodeAttnArgs* a, const float* k_scale, const float* v_scale,
+                            const int64_t* live, void* stream);
+
 /* The decoder's input row of decode step t, ONE launch — replaces, per generated token, the
  * gather of the token drawn at step t - 1, the `shared` embedding lookup (T5 applies no scale)
  * and layer 0's first T5LayerNorm.  clock == NULL: t is a->t; otherwise t and the capacity are

@@ -1,6 +1,6 @@
 """The captured decode step of tools/t5_decode_graph_bench.py made autoregressive: the token drawn at
 step t - 1 is fed back through the `shared` embedding table, and the rows that have finished are
-skipped in both attentions.  Three routes, each ONE captured step (torch.cuda.graph) replayed once
+skipped in both attentions.  Four routes, each ONE captured step (torch.cuda.graph) replayed once
 per token:
 
   c0_torch_feedback   the feedback as torch ops (a gather of rec.tokens at an index tensor derived
@@ -8,6 +8,13 @@ per token:
   c1_decode_embed     t5_decode_embed(clock): the gather, the embedding row and layer 0's first norm
                       in one launch; no skip
   c2_embed_live_skip  c1 plus live=rec.unfinished on the self- and the cross-attention of every layer
+  c3_live_skip_kv8    c2 with the cross-attention over fp8 keys and values (t5_quantize_cross_kv once
+                      per layer outside the step, t5_decode_cross_attention_kv8 inside it).  Lossy:
+                      c3 does not record c2's rollout.  Its drift is reported beside its time: the
+                      largest |difference| of the recorded policy log-probs against c2 over the
+                      T-token rollout at live fraction 1.0 -- over all positions, and over the
+                      positions up to each row's first differing token, where both routes still score
+                      the same token after the same prefix -- and the share of tokens that differ
 
 The decoder is the graph bench's (L 12, nH 12, d_kv 64, D 768, F 2048 gated, V 32128, S 512, T 48,
 bf16, at B 256 and B 8) with a `shared` [V, D] table.  The recorder is built with eos_token_id=None
@@ -57,6 +64,7 @@ class RolloutDecoder(G.Decoder):
         g = torch.Generator(device=dev).manual_seed(B + 1)
         self.shared = torch.randn(V, D, generator=g, device=dev).to(DT)
         self.start = torch.full((B,), START, dtype=torch.int64, device=dev)
+        self.kv8 = [P.t5_quantize_cross_kv(w["k_enc"], w["v_enc"], self.mask) for w in self.layers]
 
     def state(self):
         clock, caches, rec = self.rollout_state(True)
@@ -78,13 +86,16 @@ class RolloutDecoder(G.Decoder):
     def token(self, state, route):
         clock, caches, rec, _ = state
         h, y = self.feed_torch(state) if route == "c0_torch_feedback" else self.feed_kernel(state)
-        kw = dict(live=rec.unfinished) if route == "c2_embed_live_skip" else {}
+        kw = dict(live=rec.unfinished) if route in ("c2_embed_live_skip", "c3_live_skip_kv8") else {}
         for i, w in enumerate(self.layers):
             qkv = torch.matmul(y, w["qkv"])
             q, kn, vn = (qkv[:, j * INNER:(j + 1) * INNER] for j in range(3))
             a = P.t5_decode_self_attention(q, kn, vn, caches[i], clock, self.table, **kw)
             h, y = P.t5_add_rmsnorm(torch.matmul(a, w["o"]), h, w["ln"][1])
-            c = P.t5_decode_cross_attention(torch.matmul(y, w["cq"]), w["k_enc"], w["v_enc"], self.mask, **kw)
+            if route == "c3_live_skip_kv8":
+                c = P.t5_decode_cross_attention_kv8(torch.matmul(y, w["cq"]), self.kv8[i], self.mask, **kw)
+            else:
+                c = P.t5_decode_cross_attention(torch.matmul(y, w["cq"]), w["k_enc"], w["v_enc"], self.mask, **kw)
             h, y = P.t5_add_rmsnorm(torch.matmul(c, w["co"]), h, w["ln"][2])
             f = P.t5_ff_act_packed(torch.matmul(y, w["wi"]))
             nxt = self.layers[i + 1]["ln"][0] if i + 1 < L else self.final_ln
@@ -94,7 +105,20 @@ class RolloutDecoder(G.Decoder):
         clock.advance()
 
 
-ROUTES = ("c0_torch_feedback", "c1_decode_embed", "c2_embed_live_skip")
+EXACT_ROUTES = ("c0_torch_feedback", "c1_decode_embed", "c2_embed_live_skip")   # these record one rollout
+ROUTES = EXACT_ROUTES + ("c3_live_skip_kv8",)
+
+
+def kv8_drift(rec2, rec3):
+    """c3's recorded rollout against c2's (both at live fraction 1.0)."""
+    differ = rec2.tokens != rec3.tokens
+    d = (rec2.logprobs.float() - rec3.logprobs.float()).abs()
+    same_prefix = differ.long().cumsum(1) == 0                    # before the row's first differing token
+    return {"max_abs_logprob_drift_all_positions": float(d.max()),
+            "max_abs_logprob_drift_same_token_same_prefix": float(d[same_prefix].max()) if bool(same_prefix.any()) else None,
+            "share_of_tokens_that_differ": float(differ.float().mean()),
+            "share_of_rows_with_a_differing_token": float(differ.any(dim=1).float().mean()),
+            "positions": int(differ.numel())}
 
 
 def live_pattern(B, frac, dev):
@@ -132,7 +156,8 @@ def run_shape(B, dev, reps):
             rollout(r, 1.0)
         torch.cuda.synchronize()
         same = all(torch.equal(getattr(states[ROUTES[0]][2], f), getattr(states[r][2], f))
-                   for r in ROUTES[1:] for f in ("tokens", "logprobs", "ref_logprobs"))
+                   for r in EXACT_ROUTES[1:] for f in ("tokens", "logprobs", "ref_logprobs"))
+        drift = kv8_drift(states["c2_embed_live_skip"][2], states["c3_live_skip_kv8"][2])
         assert all(states[r][0].t == T and states[r][0].overrun == 0 for r in ROUTES)
         keys = [(r, f) for r in ROUTES for f in FRACTIONS]
         samples = {k: [] for k in keys}
@@ -150,7 +175,7 @@ def run_shape(B, dev, reps):
                 e1.record()
                 e1.synchronize()
                 samples[(r, f)].append(e0.elapsed_time(e1) / T)
-    res = {"routes_record_the_same_rollout_at_fraction_1": bool(same)}
+    res = {"routes_record_the_same_rollout_at_fraction_1": bool(same), "c3_kv8_against_c2_at_fraction_1": drift}
     for f in FRACTIONS:
         per = {r: {"ms_per_token_median": statistics.median(samples[(r, f)]), "min": min(samples[(r, f)]),
                    "max": max(samples[(r, f)])} for r in ROUTES}
@@ -159,6 +184,8 @@ def run_shape(B, dev, reps):
         per["fastest"] = min(ROUTES, key=med.get)
         per["c1_beats_c0"] = med["c1_decode_embed"] < med["c0_torch_feedback"]
         per["c2_beats_c1"] = med["c2_embed_live_skip"] < med["c1_decode_embed"]
+        per["c3_beats_c2"] = med["c3_live_skip_kv8"] < med["c2_embed_live_skip"]
+        per["c3_over_c2"] = med["c3_live_skip_kv8"] / med["c2_embed_live_skip"]
         res[f"live_{f}"] = per
     return res
 

@@ -48,6 +48,10 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
       step before (read from the recorder on the device), the embedding row, layer 0's first norm;
       with `live=recorder.unfinished` both decode attentions skip the rows that have drawn eos
       (the token feedback and the finished rows of HF generate, ppo_orchestrator.py:76)
+  t5_quantize_cross_kv, T5CrossKV8, t5_decode_cross_attention_kv8 — opt-in: the encoder's keys and
+      values as e4m3fn bytes with a power-of-two scale per (row, head), quantised once per rollout
+      in one launch, and the decode cross-attention over them: half the K / V bytes per token,
+      fp32 arithmetic; lossy against the bf16 keys, exact against its own dequantised values
   t5_attention, t5_relative_bias_offsets — T5's attention over whole sequences (encoder
       self-attention, teacher-forced decoder self- and cross-attention) as one flash-attention
       launch on MFMA: bias, key mask and causal rule inside, no [Tq, S] tensor
@@ -87,8 +91,9 @@ from .ilql_store import ILQLElement, ILQLRolloutStorage
 from .value_head import ValueHead, value_head, value_head_splits
 from .value_head import make_head as make_value_head
 from .sampling import PPOLogitsProcessors, ppo_sample_step
-from .t5_decode import (T5DecodeClock, T5DecodeKVCache, t5_decode_cross_attention, t5_decode_embed,
-                        t5_decode_self_attention, t5_relative_bias_table)
+from .t5_decode import (T5CrossKV8, T5DecodeClock, T5DecodeKVCache, t5_decode_cross_attention,
+                        t5_decode_cross_attention_kv8, t5_decode_embed, t5_decode_self_attention,
+                        t5_quantize_cross_kv, t5_relative_bias_table)
 from .t5_attention import t5_attention, t5_attention_train, t5_relative_bias_buckets, t5_relative_bias_offsets
 from .t5_ff import T5FeedForward, t5_ff_act, t5_ff_act_packed
 from .t5_norm import T5LayerNorm, t5_add_rmsnorm, t5_rmsnorm
@@ -110,7 +115,7 @@ __all__ = [
     "ValueHead", "value_head", "value_head_splits", "make_value_head",
     "FusedAdamW", "adamw_step", "clip_grad_norm_", "schedule_table",
     "T5DecodeKVCache", "T5DecodeClock", "t5_decode_self_attention", "t5_decode_cross_attention", "t5_relative_bias_table",
-    "t5_decode_embed",
+    "t5_decode_embed", "T5CrossKV8", "t5_quantize_cross_kv", "t5_decode_cross_attention_kv8",
     "t5_attention", "t5_relative_bias_offsets", "t5_attention_train", "t5_relative_bias_buckets",
     "t5_ff_act", "t5_ff_act_packed", "T5FeedForward",
     "t5_rmsnorm", "t5_add_rmsnorm", "T5LayerNorm",

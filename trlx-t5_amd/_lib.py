@@ -102,6 +102,16 @@ class T5DecodeAttnArgs(ctypes.Structure):
     ]
 
 
+class T5CrossKvQuantArgs(ctypes.Structure):
+    """Mirror of TrlxT5CrossKvQuantArgs (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("k", _c_vp), ("k_stride_b", _c_i64), ("k_stride_h", _c_i64), ("k_stride_s", _c_i64),
+        ("v", _c_vp), ("v_stride_b", _c_i64), ("v_stride_h", _c_i64), ("v_stride_s", _c_i64),
+        ("key_mask", _c_vp), ("k8", _c_vp), ("v8", _c_vp), ("k_scale", _c_vp), ("v_scale", _c_vp),
+        ("B", _c_i64), ("n_heads", _c_i64), ("S", _c_i64), ("d_kv", _c_i64),
+    ]
+
+
 class T5DecodeEmbedArgs(ctypes.Structure):
     """Mirror of TrlxT5DecodeEmbedArgs (include/trlx_t5_amd.h)."""
     _fields_ = [
@@ -356,6 +366,8 @@ SIGNATURES = {
     "trlx_decode_clock_advance": (_c_int, [_c_vp, _c_vp]),
     "trlx_t5_decode_attn_dev": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp, _c_vp]),
     "trlx_t5_decode_attn_live": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp, _c_vp, _c_vp]),
+    "trlx_t5_cross_kv_quantize": (_c_int, [ctypes.POINTER(T5CrossKvQuantArgs), _c_vp]),
+    "trlx_t5_decode_attn_kv8": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp, _c_vp, _c_vp, _c_vp]),
     "trlx_t5_decode_embed": (_c_int, [ctypes.POINTER(T5DecodeEmbedArgs), _c_vp, _c_vp]),
     "trlx_t5_attention": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp]),
     "trlx_t5_attention_tiles": (_c_int, [ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),

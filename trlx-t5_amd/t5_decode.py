@@ -13,6 +13,10 @@
                              0's first norm: one launch, t from a host int or the clock
   live=                      both attentions skip the rows whose entry of `live` is 0 (the
                              recorder's `unfinished`): zeros out, nothing read, the cache untouched
+  t5_quantize_cross_kv       the encoder's keys / values to e4m3fn bytes with one power-of-two scale
+                             per (row, head), once per rollout: one launch, a T5CrossKV8
+  t5_decode_cross_attention_kv8   the cross-attention over those bytes: half the K / V traffic per
+                             token, fp32 arithmetic; opt-in and lossy (3 mantissa bits)
 
 Per layer and generated token HF's eager T5Attention spends, between the projections and `o`, a
 cache append, a [B, nH, 1, t] matmul, compute_bias (arange, bucket formula, embedding lookup,
@@ -33,7 +37,8 @@ import torch
 from . import _lib
 
 __all__ = ["t5_relative_bias_table", "T5DecodeKVCache", "T5DecodeClock", "t5_decode_self_attention",
-           "t5_decode_cross_attention", "t5_decode_embed"]
+           "t5_decode_cross_attention", "t5_decode_embed", "T5CrossKV8", "t5_quantize_cross_kv",
+           "t5_decode_cross_attention_kv8"]
 
 KERNEL_DTYPES = (torch.bfloat16, torch.float32)
 KERNEL_D_KV = (64, 128)
@@ -312,6 +317,171 @@ def t5_decode_cross_attention(q, k_enc, v_enc, key_mask=None, live=None):
         _lib.call("trlx_t5_decode_attn_live", ctypes.byref(args), live.data_ptr(), None, _lib.stream_of(out))
     else:
         _lib.call("trlx_t5_decode_attn", ctypes.byref(args), _lib.stream_of(out))
+    return out
+
+
+# ------------------------------------------------------------------ fp8 encoder keys and values
+KV8_E_MIN, KV8_E_MAX = -100, 119    # the clamp of the scale's exponent (trlx_t5_cross_kv_quantize)
+KV8_MAX = 448.0                     # the largest finite e4m3fn
+
+
+class T5CrossKV8:
+    """The encoder's keys and values of one decoder layer as e4m3fn bytes (t5_quantize_cross_kv).
+
+      k8, v8             torch.float8_e4m3fn [B, nH, S, d_kv], contiguous
+      k_scale, v_scale   float32 [B, nH], powers of two: key = k8 * k_scale[b, h]
+      dequantize()       (K, V) in bfloat16, exact: byte * scale is representable in bf16, so
+                         t5_decode_cross_attention on them sees the values the fp8 route computes on
+    """
+
+    def __init__(self, B, n_heads, S, d_kv, device):
+        if min(B, n_heads, S) < 1 or d_kv not in KERNEL_D_KV:
+            raise ValueError(f"B, n_heads, S = {B}, {n_heads}, {S} (>= 1), d_kv = {d_kv} (in {KERNEL_D_KV})")
+        self.B, self.n_heads, self.S, self.d_kv = int(B), int(n_heads), int(S), int(d_kv)
+        self.k8 = torch.zeros(B, n_heads, S, d_kv, dtype=torch.float8_e4m3fn, device=device)
+        self.v8 = torch.zeros(B, n_heads, S, d_kv, dtype=torch.float8_e4m3fn, device=device)
+        self.k_scale = torch.ones(B, n_heads, dtype=torch.float32, device=device)
+        self.v_scale = torch.ones(B, n_heads, dtype=torch.float32, device=device)
+
+    @property
+    def device(self):
+        return self.k8.device
+
+    def dequantize(self):
+        return tuple((x.float() * s[:, :, None, None]).to(torch.bfloat16)
+                     for x, s in ((self.k8, self.k_scale), (self.v8, self.v_scale)))
+
+
+def _torch_quantize_kv8(x, live, x8, scale):
+    """One tensor of trlx_t5_cross_kv_quantize as torch expressions, bit for bit.  x: bf16
+    [B, nH, S, d] (any strides), live: bool [B, S] or None."""
+    B, nH, S, d = x.shape
+    xf = x.float()
+    if live is not None:
+        xf = torch.where(live[:, None, :, None], xf, torch.zeros_like(xf))   # masked rows: not read, zero bytes
+    amax = xf.abs().amax(dim=(2, 3))
+    bad = ~torch.isfinite(amax)
+    amax = torch.where(bad, torch.zeros_like(amax), amax)
+    m, x2 = torch.frexp(amax)
+    e = torch.where(m <= 0.875, x2 - 9, x2 - 8)
+    e = torch.where(amax == 0, torch.zeros_like(e), e).clamp(KV8_E_MIN, KV8_E_MAX)
+    e = e.to(torch.int32)
+    inv = ((127 - e) << 23).view(torch.float32)   # 2^-e, from its bits
+    y =(xf * inv[:, :, None, None]).to(torch.float8_e4m3fn).view(torch.uint8)
+    nan_byte = torch.full_like(y, 0x7f)
+    if live is not None:
+        nan_byte = torch.where(live[:, None, :, None], nan_byte, torch.zeros_like(nan_byte))
+    y = torch.where(bad[:, :, None, None], nan_byte, y)
+    x8.view(torch.uint8).copy_(y)
+    scale.copy_(torch.where(bad, torch.full_like(amax, float("nan")), ((127 + e) << 23).view(torch.float32)))
+
+
+def _kv_strides(x, name, n_heads):
+    """x as (tensor, (B, nH, S, d), (sb, sh, ss)): [B, nH, S, d] (HF's transposed view included) or
+    the projection output [B, S, nH*d] with n_heads=; read in place when the last dimension has unit
+    stride and the base and the other strides are whole 16-byte vectors, else copied once."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.bfloat16:
+        raise ValueError(f"{name} must be a bfloat16 tensor")
+    if x.dim() == 3:
+        if n_heads is None or int(n_heads) < 1 or x.shape[2] % int(n_heads):
+            raise ValueError(f"{name} is [B, S, nH*d_kv] = {tuple(x.shape)}: pass n_heads= (a divisor of the last dimension)")
+        x = x.unflatten(2, (int(n_heads), x.shape[2] // int(n_heads))).permute(0, 2, 1, 3)   # a view
+    elif x.dim() != 4:
+        raise ValueError(f"{name} must be [B, nH, S, d_kv] or [B, S, nH*d_kv] with n_heads=, got {tuple(x.shape)}")
+    B, nH, S, d = x.shape
+    if n_heads is not None and int(n_heads) != nH:
+        raise ValueError(f"{name} has {nH} heads, n_heads = {n_heads}")
+    if min(B, nH, S) < 1 or d not in KERNEL_D_KV:
+        raise ValueError(f"{name}: B, nH, S = {B}, {nH}, {S} (>= 1), d_kv = {d} (in {KERNEL_D_KV})")
+    st = [x.stride(i) if x.shape[i] > 1 else 0 for i in range(3)]
+    if x.stride(3) != 1 or x.data_ptr() % 16 or any(s < 0 or s % 8 for s in st) or \
+            (nH > 1 and st[1] < d) or (S > 1 and st[2] < d):
+        x = x.contiguous()
+        st = [x.stride(i) if x.shape[i] > 1 else 0 for i in range(3)]
+    return x, (B, nH, S, d), st
+
+
+def t5_quantize_cross_kv(k_enc, v_enc, key_mask=None, out=None, n_heads=None):
+    """The encoder's keys and values of one layer to e4m3fn, once per rollout: returns a T5CrossKV8.
+    One launch for K and V (trlx_t5_cross_kv_quantize).
+
+    k_enc, v_enc: bfloat16, [B, nH, S, d_kv] -- contiguous or HF's transposed view of the
+    projection -- or the projection output [B, S, nH*d_kv] with n_heads=; d_kv 64 or 128.  Both are
+    read in place: the .contiguous() that t5_decode_cross_attention asks for is not needed here.
+    key_mask: int64 [B, S], 0 = masked, or None: a masked row is not read, is stored as zero bytes
+    and does not enter the scale.  Per (b, h) and tensor: scale = 2^e with e the smallest integer
+    such that max|x| * 2^-e <= 448 (0 for an all-zero block, clamped to [-100, 119]), byte =
+    (x * 2^-e).to(torch.float8_e4m3fn), bit for bit.  A live Inf / NaN makes that block's scale NaN
+    and its live bytes 0x7f: the attention gives NaN for that (b, h) only.
+    out: a preallocated T5CrossKV8 of the same B, nH, S, d_kv on the same device, written in place.
+    On a CPU device the same values come from torch expressions (`_torch_quantize_kv8`), bit for bit.
+    Lossy against the bf16 keys: e4m3 keeps 3 mantissa bits.  Current stream, no host sync."""
+    k, shape, k_st = _kv_strides(k_enc, "k_enc", n_heads)
+    v, v_shape, v_st = _kv_strides(v_enc, "v_enc", n_heads)
+    if shape != v_shape or k.device != v.device:
+        raise ValueError(f"k_enc and v_enc differ: {shape} on {k.device}, {v_shape} on {v.device}")
+    B, nH, S, d = shape
+    if key_mask is not None:
+        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (B, S) or key_mask.dtype != torch.int64 \
+                or key_mask.device != k.device:
+            raise ValueError(f"key_mask must be int64 [B, S] = [{B}, {S}] on {k.device}")
+        key_mask = key_mask.contiguous()
+    if out is None:
+        out = T5CrossKV8(B, nH, S, d, k.device)
+    elif not isinstance(out, T5CrossKV8) or (out.B, out.n_heads, out.S, out.d_kv) != shape or out.device != k.device:
+        raise ValueError(f"out must be a T5CrossKV8 of B, nH, S, d_kv = {shape} on {k.device}")
+    if not k.is_cuda:
+        live = None if key_mask is None else key_mask != 0
+        _torch_quantize_kv8(k, live, out.k8, out.k_scale)
+        _torch_quantize_kv8(v, live, out.v8, out.v_scale)
+        return out
+    args = _lib.T5CrossKvQuantArgs(
+        k=k.data_ptr(), k_stride_b=k_st[0], k_stride_h=k_st[1], k_stride_s=k_st[2],
+        v=v.data_ptr(), v_stride_b=v_st[0], v_stride_h=v_st[1], v_stride_s=v_st[2],
+        key_mask=_lib.ptr(key_mask), k8=out.k8.data_ptr(), v8=out.v8.data_ptr(), k_scale=out.k_scale.data_ptr(),
+        v_scale=out.v_scale.data_ptr(), B=B, n_heads=nH, S=S, d_kv=d)
+    _lib.call("trlx_t5_cross_kv_quantize", ctypes.byref(args), _lib.stream_of(k))
+    return out
+
+
+def t5_decode_cross_attention_kv8(q, kv8, key_mask=None, live=None):
+    """t5_decode_cross_attention over fp8 keys and values (trlx_t5_decode_attn_kv8): half the K / V
+    bytes per token, the same fp32 arithmetic.  Returns bfloat16 [B, nH*d_kv].
+
+    q: bfloat16, the shapes and strides of t5_decode_cross_attention.  kv8: a T5CrossKV8.
+    key_mask, live: as in t5_decode_cross_attention.  score_j = (q · k8_j) * k_scale[b, h]; the
+    output is (P · v8) * v_scale[b, h] / sum P, rounded once.  The result differs from the bf16
+    route by the quantisation of K and V and by nothing else: t5_decode_cross_attention on
+    kv8.dequantize() computes on the same values.  The launch takes the same arguments at every
+    token and can be captured.  On a CPU device: the torch expressions on dequantize()."""
+    if not isinstance(kv8, T5CrossKV8):
+        raise TypeError("kv8 must be a T5CrossKV8")
+    B, nH, S, d = kv8.B, kv8.n_heads, kv8.S, kv8.d_kv
+    dev = kv8.device
+    _check_q(q, B, nH, d, torch.bfloat16, dev)
+    if key_mask is not None:
+        if tuple(key_mask.shape) != (B, S) or key_mask.dtype != torch.int64 or key_mask.device != dev:
+            raise ValueError(f"key_mask must be int64 [B, S] = [{B}, {S}] on {dev}, got {key_mask.dtype} "
+                             f"{tuple(key_mask.shape)}")
+    if live is not None:
+        _check_live(live, B, torch.bfloat16, d, dev)
+    if not kv8.k8.is_cuda:
+        k, v = kv8.dequantize()
+        out = _torch_cross_attention(q, k, v, key_mask)
+        return out if live is None else torch.where((live != 0)[:, None], out, torch.zeros_like(out))
+    for x in (kv8.k8, kv8.v8, kv8.k_scale, kv8.v_scale):
+        if not x.is_contiguous():
+            raise ValueError("kv8: k8, v8 and the scales must be contiguous")
+    if key_mask is not None and not key_mask.is_contiguous():
+        key_mask = key_mask.contiguous()
+    q2, ldq = _rows(q, "q", B, nH, d)
+    out = torch.empty(B, nH * d, dtype=torch.bfloat16, device=dev)
+    args = _lib.T5DecodeAttnArgs(
+        q=q2.data_ptr(), ldq=ldq, k_new=None, ldk=0, v_new=None, ldv=0, k=kv8.k8.data_ptr(), v=kv8.v8.data_ptr(),
+        bias_by_distance=None, key_mask=_lib.ptr(key_mask), out=out.data_ptr(), B=B, n_heads=nH, d_kv=d,
+        max_len=S, t=0, dtype=_lib.BF16, mode=_lib.T5_ATTN_CROSS)
+    _lib.call("trlx_t5_decode_attn_kv8", ctypes.byref(args), kv8.k_scale.data_ptr(), kv8.v_scale.data_ptr(),
+              _lib.ptr(live), _lib.stream_of(out))
     return out
 
 
