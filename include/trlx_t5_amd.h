@@ -1407,7 +1407,8 @@ int trlx_t5_ff_act_geometry(int* vec_bf16, int* vec_f32, int* cols_per_block, in
  * overlap not named above (TRLX_ERR_ARG); D outside [1, 8192], N < 0 (TRLX_ERR_SHAPE); a row stride
  * below D (TRLX_ERR_STRIDE); a dtype other than the two (TRLX_ERR_DTYPE).
  * trlx_t5_rmsnorm_geometry fills the launch geometry; the per-shape fields are 0 when D is outside
- * [1, max_d].  Not built: fp16, dropout, a fused norm + projection GEMM, a double backward. */
+ * [1, max_d].  Not built: fp16, dropout, a double backward; the norm fused into a projection exists for
+ * decode steps only (trlx_t5_decode_linear). */
 typedef struct TrlxT5RmsNormArgs {
     const void* x;                    /* forward: the sub-layer output (add form) or the rows to normalise */
     int64_t ld_x;
@@ -1451,6 +1452,73 @@ typedef struct TrlxT5RmsNormGeometry {
 int trlx_t5_rmsnorm_fwd(const TrlxT5RmsNormArgs* a, void* stream);
 int trlx_t5_rmsnorm_bwd(const TrlxT5RmsNormArgs* a, void* stream);
 int trlx_t5_rmsnorm_geometry(int64_t N, int64_t D, TrlxT5RmsNormGeometry* g);
+
+/* ---------------------------------------------------------------- T5 decode-step projection
+ * One projection of a decode step with its neighbours in the same launch (opt-in; the projections
+ * of every other path stay hipBLASLt):
+ *   out[m, n] = epilogue( sum_k xh[m, k] * weight[n, k] )      bf16 MFMA, fp32 accumulation
+ *   prologue  norm_weight NULL: xh = x.  Else T5's RMSNorm in front of the projection:
+ *             xh[m, k] = bf16(norm_weight[k] * (x[m, k] * rstd[m])), rstd[m] = 1 / sqrt(mean_k x[m, k]^2 + eps),
+ *             the sum order, the product and the one rounding of trlx_t5_rmsnorm_fwd for D = K, so xh
+ *             has the bits of that forward on x; the normed rows are never written.  K <= 8192.
+ *   epilogue  at most one of
+ *             residual [M, N]  : out = bf16(acc + residual), one rounding.  out may be the very rows of
+ *                                residual (same pointer, same stride): the stream updated in place.
+ *             act, gated = 0   : out = bf16(act(acc)), weight [N, K]               (T5DenseActDense's wi)
+ *             act, gated = 1   : weight is [2N, K], wi_0's rows then wi_1's; out[m, j] =
+ *                                bf16(act(u) * v) with u, v the fp32 accumulators of weight rows j and
+ *                                N + j                                       (T5DenseGatedActDense)
+ *             act is a trlx_t5_act evaluated as trlx_t5_ff_act_fwd evaluates it, or TRLX_T5_ACT_NONE.
+ *   x       : [M, K], element stride 1, row stride ld_x >= K (h[:, -1, :] is read in place)
+ *   weight  : nn.Linear.weight layout, rows of K elements ld_w >= K apart
+ *   out     : [M, N], row stride ld_out >= N.  N counts output columns in every form.
+ * TRLX_BF16 only.  M >= 1; K a multiple of 32, 32 to 16384; N a multiple of 16.  Every pointer is
+ * 16-byte aligned and every row stride a multiple of 8 elements.
+ * A workgroup owns 16 output columns and every row; K is split across the four waves of the
+ * workgroup only and their partial sums are added in wave order: no atomics, no workspace, two calls
+ * give the same bits.  No allocation and no host read: the call is the same launch at every token
+ * and can be captured.
+ * Refused before any launch, out untouched: NULL args / x / weight / out, a pointer off the 16-byte
+ * grid, an unknown act, gated without an act, a residual together with an act, a NaN eps, out sharing
+ * a byte range with x, weight or norm_weight, or with residual other than as the very same rows
+ * (TRLX_ERR_ARG); M, K or N off the grid above, K > 8192 with a norm weight (TRLX_ERR_SHAPE); a row
+ * stride below the row or off the 16-byte grid (TRLX_ERR_STRIDE); a dtype other than TRLX_BF16
+ * (TRLX_ERR_DTYPE).
+ * trlx_t5_decode_linear_geometry reports the blocking.  Not built: fp32 / fp16, a backward, a bias,
+ * K split across workgroups. */
+#define TRLX_T5_ACT_NONE (-1)
+typedef struct trlx_t5_decode_linear_args {
+    const void* x;
+    int64_t ld_x;
+    const void* weight;
+    int64_t ld_w;
+    const void* norm_weight;          /* [K] or NULL */
+    const void* residual;             /* [M, N] or NULL */
+    int64_t ld_residual;
+    void* out;
+    int64_t ld_out;
+    int64_t M;
+    int64_t K;
+    int64_t N;                        /* output columns */
+    float eps;
+    int dtype;                        /* TRLX_BF16 */
+    int act;                          /* trlx_t5_act or TRLX_T5_ACT_NONE */
+    int gated;                        /* weight is [2N, K] */
+} trlx_t5_decode_linear_args;
+typedef struct TrlxT5DecodeLinearGeometry {
+    int threads;                      /* per workgroup */
+    int cols_per_block;               /* output columns a workgroup owns */
+    int rows_per_tile;
+    int k_per_chunk;                  /* K of one MFMA */
+    int chunks_per_wave_turn;         /* chunk c belongs to wave (c / this) % (threads / 64) */
+    int max_row_tiles;                /* accumulator tiles of a wave: row tiles per pass x weight slabs */
+    int max_k;
+    int norm_max_k;                   /* the largest K taken with a norm weight */
+    int norm_wave_row_max_k;          /* up to here the norm's sum takes one wave per row */
+    int reserved;
+} TrlxT5DecodeLinearGeometry;
+int trlx_t5_decode_linear(const trlx_t5_decode_linear_args* a, void* stream);
+int trlx_t5_decode_linear_geometry(TrlxT5DecodeLinearGeometry* g);
 
 /* ---------------------------------------------------------------- §8f: device-resident rollout store
  * Row copy between padded columnar [rows, W] buffers — replaces the reference's

@@ -16,6 +16,12 @@ per token:
                       positions up to each row's first differing token, where both routes still score
                       the same token after the same prefix -- and the share of tokens that differ
 
+  c4_fused_projections  c2's step with the 8-launch layer (t5_decode_layer_fused): the six projections of a
+                      layer on trlx_t5_decode_linear with the norms, the residual adds and the gated
+                      activation inside them; the final norm, the lm_head matmuls and the sampler as in
+                      c2.  It rounds differently, so it need not record c2's rollout: its drift against
+                      c2 is reported by the method of c3's, beside its time and the launches per step
+
 The decoder is the graph bench's (L 12, nH 12, d_kv 64, D 768, F 2048 gated, V 32128, S 512, T 48,
 bf16, at B 256 and B 8) with a `shared` [V, D] table.  The recorder is built with eos_token_id=None
 and rec.unfinished is preset to a fixed pattern, so the sampler never changes it; every route runs at
@@ -65,6 +71,11 @@ class RolloutDecoder(G.Decoder):
         self.shared = torch.randn(V, D, generator=g, device=dev).to(DT)
         self.start = torch.full((B,), START, dtype=torch.int64, device=dev)
         self.kv8 = [P.t5_quantize_cross_kv(w["k_enc"], w["v_enc"], self.mask) for w in self.layers]
+        # c4: the same weights in nn.Linear.weight layout [N, K]
+        self.blocks = [P.T5DecodeBlockWeights(*(w[k].t().contiguous() for k in ("qkv", "o", "cq", "co", "wi", "wo")),
+                                              ln=w["ln"], gated=True) for w in self.layers]
+        self.bufs = dict(qkv=torch.empty(B, 3 * INNER, dtype=DT, device=dev), cq=torch.empty(B, INNER, dtype=DT, device=dev),
+                         ff=torch.empty(B, FF, dtype=DT, device=dev))
 
     def state(self):
         clock, caches, rec = self.rollout_state(True)
@@ -83,7 +94,22 @@ class RolloutDecoder(G.Decoder):
         clock, _, rec, out = state
         return P.t5_decode_embed(self.shared, rec, clock, START, self.layers[0]["ln"][0], out=out)
 
+    def token_fused(self, state):
+        clock, caches, rec, out = state
+        h, _ = P.t5_decode_embed(self.shared, rec, clock, START, out=(out[0], None))
+        kw = dict(live=rec.unfinished)
+        for i, (w, blk) in enumerate(zip(self.layers, self.blocks)):
+            P.t5_decode_layer_fused(
+                h, blk, lambda q, kn, vn: P.t5_decode_self_attention(q, kn, vn, caches[i], clock, self.table, **kw),
+                lambda q: P.t5_decode_cross_attention(q, w["k_enc"], w["v_enc"], self.mask, **kw), bufs=self.bufs)
+        y = P.t5_rmsnorm(h, self.final_ln)
+        logits, ref = torch.matmul(y, self.lm), torch.matmul(y, self.ref_lm)
+        P.ppo_sample_step(logits, ref_logits=ref, recorder=rec, u=self.u, out=self.out, top_k=50, top_p=0.95)
+        clock.advance()
+
     def token(self, state, route):
+        if route == "c4_fused_projections":
+            return self.token_fused(state)
         clock, caches, rec, _ = state
         h, y = self.feed_torch(state) if route == "c0_torch_feedback" else self.feed_kernel(state)
         kw = dict(live=rec.unfinished) if route in ("c2_embed_live_skip", "c3_live_skip_kv8") else {}
@@ -106,7 +132,11 @@ class RolloutDecoder(G.Decoder):
 
 
 EXACT_ROUTES = ("c0_torch_feedback", "c1_decode_embed", "c2_embed_live_skip")   # these record one rollout
-ROUTES = EXACT_ROUTES + ("c3_live_skip_kv8",)
+ROUTES = EXACT_ROUTES + ("c3_live_skip_kv8", "c4_fused_projections")
+# launches of one step, counted from the step's code: the feedback, 12 (or 8) per layer, the final norm of
+# c4, two lm_head matmuls, the sampler, the clock
+LAUNCHES = {"c0_torch_feedback": None, "c1_decode_embed": 1 + 12 * L + 4, "c2_embed_live_skip": 1 + 12 * L + 4,
+            "c3_live_skip_kv8": 1 + 12 * L + 4, "c4_fused_projections": 1 + 8 * L + 1 + 4}
 
 
 def kv8_drift(rec2, rec3):
@@ -158,6 +188,7 @@ def run_shape(B, dev, reps):
         same = all(torch.equal(getattr(states[ROUTES[0]][2], f), getattr(states[r][2], f))
                    for r in EXACT_ROUTES[1:] for f in ("tokens", "logprobs", "ref_logprobs"))
         drift = kv8_drift(states["c2_embed_live_skip"][2], states["c3_live_skip_kv8"][2])
+        drift4 = kv8_drift(states["c2_embed_live_skip"][2], states["c4_fused_projections"][2])
         assert all(states[r][0].t == T and states[r][0].overrun == 0 for r in ROUTES)
         keys = [(r, f) for r in ROUTES for f in FRACTIONS]
         samples = {k: [] for k in keys}
@@ -175,7 +206,9 @@ def run_shape(B, dev, reps):
                 e1.record()
                 e1.synchronize()
                 samples[(r, f)].append(e0.elapsed_time(e1) / T)
-    res = {"routes_record_the_same_rollout_at_fraction_1": bool(same), "c3_kv8_against_c2_at_fraction_1": drift}
+    res = {"routes_record_the_same_rollout_at_fraction_1": bool(same), "c3_kv8_against_c2_at_fraction_1": drift,
+           "c4_fused_projections_against_c2_at_fraction_1": drift4,
+           "launches_per_step_counted_from_the_code": LAUNCHES}
     for f in FRACTIONS:
         per = {r: {"ms_per_token_median": statistics.median(samples[(r, f)]), "min": min(samples[(r, f)]),
                    "max": max(samples[(r, f)])} for r in ROUTES}
@@ -186,6 +219,8 @@ def run_shape(B, dev, reps):
         per["c2_beats_c1"] = med["c2_embed_live_skip"] < med["c1_decode_embed"]
         per["c3_beats_c2"] = med["c3_live_skip_kv8"] < med["c2_embed_live_skip"]
         per["c3_over_c2"] = med["c3_live_skip_kv8"] / med["c2_embed_live_skip"]
+        per["c4_beats_c2"] = med["c4_fused_projections"] < med["c2_embed_live_skip"]
+        per["c4_over_c2"] = med["c4_fused_projections"] / med["c2_embed_live_skip"]
         res[f"live_{f}"] = per
     return res
 

@@ -185,6 +185,24 @@ class T5RmsNormGeometry(ctypes.Structure):
     ]
 
 
+T5_ACT_NONE = -1
+
+
+class T5DecodeLinearArgs(ctypes.Structure):
+    """Mirror of trlx_t5_decode_linear_args (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("x", _c_vp), ("ld_x", _c_i64), ("weight", _c_vp), ("ld_w", _c_i64), ("norm_weight", _c_vp),
+        ("residual", _c_vp), ("ld_residual", _c_i64), ("out", _c_vp), ("ld_out", _c_i64),
+        ("M", _c_i64), ("K", _c_i64), ("N", _c_i64), ("eps", _c_f), ("dtype", _c_int), ("act", _c_int), ("gated", _c_int),
+    ]
+
+
+class T5DecodeLinearGeometry(ctypes.Structure):
+    """Mirror of TrlxT5DecodeLinearGeometry (include/trlx_t5_amd.h)."""
+    _fields_ = [(n, _c_int) for n in ("threads", "cols_per_block", "rows_per_tile", "k_per_chunk", "chunks_per_wave_turn",
+                                      "max_row_tiles", "max_k", "norm_max_k", "norm_wave_row_max_k", "reserved")]
+
+
 POLYAK_MAX_TENSORS = 16
 ADAMW_MAX_TENSORS = 32
 ADAMW_CHUNK = 8192  # elements of one tensor per workgroup
@@ -381,6 +399,8 @@ SIGNATURES = {
     "trlx_t5_rmsnorm_fwd": (_c_int, [ctypes.POINTER(T5RmsNormArgs), _c_vp]),
     "trlx_t5_rmsnorm_bwd": (_c_int, [ctypes.POINTER(T5RmsNormArgs), _c_vp]),
     "trlx_t5_rmsnorm_geometry": (_c_int, [_c_i64, _c_i64, ctypes.POINTER(T5RmsNormGeometry)]),
+    "trlx_t5_decode_linear": (_c_int, [ctypes.POINTER(T5DecodeLinearArgs), _c_vp]),
+    "trlx_t5_decode_linear_geometry": (_c_int, [ctypes.POINTER(T5DecodeLinearGeometry)]),
     "trlx_rows_copy": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                 _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_shift_tokens_right": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp]),

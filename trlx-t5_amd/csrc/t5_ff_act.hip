@@ -18,6 +18,7 @@
 // Overflow: u^2 may be +inf (|u| > 1.8e19); then x = +-inf, e = 0, sigmoid' = 0 exactly, and the
 // derivative's u x' sigmoid'(x) term (inf * 0) is replaced by the 0 it tends to.
 #include "common.h"
+#include "t5_row_math.h"
 
 namespace trlx {
 
@@ -26,10 +27,6 @@ constexpr int kFaCols = 512;                                   // columns per wo
 constexpr int kFaWaveRows = 4;                                 // rows per wave
 constexpr int kFaRows = (kFaThreads / kWave) * kFaWaveRows;    // rows per workgroup
 
-constexpr float kGeluC = 0.044715f;
-constexpr float kGelu3C = 3.f * 0.044715f;
-constexpr float kGelu2K = 1.5957691216057308f;                 // 2 sqrt(2 / pi)
-
 struct FaArgs {
     const void *u, *v, *dy;
     void *out, *du, *dv;
@@ -37,34 +34,6 @@ struct FaArgs {
     int64_t N, F;
     unsigned nct;   // column blocks per row block
 };
-
-// a = act(u) and, with GRAD, d = act'(u)
-template <int ACT, bool GRAD>
-__device__ __forceinline__ void fa_eval(float u, float& a, float& d) {
-    if constexpr (ACT == TRLX_T5_ACT_RELU) {
-        a = u <= 0.f ? 0.f : u;                                // NaN stays NaN
-        if (GRAD) d = u > 0.f ? 1.f : (u <= 0.f ? 0.f : u);
-    } else {
-        float x, xp;                                           // sigmoid's argument and dx/du
-        if constexpr (ACT == TRLX_T5_ACT_SILU) {
-            x = u;
-            xp = 1.f;
-        } else {
-            const float u2 = u * u;
-            x = kGelu2K * (u * (1.f + kGeluC * u2));
-            xp = kGelu2K * (1.f + kGelu3C * u2);
-        }
-        const float e = exp2_fast(-fabsf(x) * kLog2e);
-        const float r = __builtin_amdgcn_rcpf(1.f + e);
-        const float s = x >= 0.f ? r : e * r;
-        a = u * s;
-        if (GRAD) {
-            const float t = e * (r * r);                       // sigmoid'(x); 0 once |x| > ~88
-            const float w = t > 0.f ? (u * xp) * t : 0.f;      // u x' may be inf where t is 0
-            d = s + w;                                         // NaN u: s is NaN
-        }
-    }
-}
 
 // One access: a 16-byte vector of the row (VEC) or one element.
 template <class DT, bool VEC>

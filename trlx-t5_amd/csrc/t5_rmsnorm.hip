@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "t5_row_math.h"
 
 namespace trlx {
 
@@ -115,16 +116,6 @@ struct RnTile {
         return ((s[0] + s[1]) + s[2]) + s[3];
     }
 };
-
-template <int E>
-__device__ __forceinline__ float rn_sumsq(const float (&f)[E]) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < E; ++i) s += f[i] * f[i];
-    return s;
-}
-
-__device__ __forceinline__ float rn_rstd(float sumsq, int D, float eps) { return 1.f / sqrtf(sumsq / float(D) + eps); }
 
 template <class DT, bool VEC, int TEAM, int E>
 __global__ __launch_bounds__(kRnThreads) void k_t5_rmsnorm_fwd(RnArgs k) {
