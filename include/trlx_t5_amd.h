@@ -1520,6 +1520,58 @@ typedef struct TrlxT5DecodeLinearGeometry {
 int trlx_t5_decode_linear(const trlx_t5_decode_linear_args* a, void* stream);
 int trlx_t5_decode_linear_geometry(TrlxT5DecodeLinearGeometry* g);
 
+/* The same projection with the rows spread over workgroups and a skip of finished rows (opt-in;
+ * csrc/t5_decode_linear_rows.hip).  The expression, the eight epilogue forms, the norm prologue and
+ * the per-tile arithmetic are trlx_t5_decode_linear's; the grid is (N / 16, ceil(M / rows_per_block))
+ * and a workgroup owns 16 output columns and ONE block of rows_per_block rows.  A row's output does
+ * not depend on the tile or workgroup it lands in: every live row has the bits
+ * trlx_t5_decode_linear gives it.
+ *   live : NULL (every row live), or device int64 [M], nonzero = live (the rollout recorder's
+ *          `unfinished` as it is), read on the device: the launch is the same at every token.  The
+ *          live rows are compacted in row order, rows_per_block of them per workgroup; a workgroup
+ *          without live rows loads no weight.  A dead row behaves as a zero input row and nothing of
+ *          x is read for it: out[m] = 0 in the plain, norm and activation forms; out[m] = residual[m]
+ *          in the residual form; left untouched when out is the residual.  Every element of out is
+ *          written exactly once per call (an in-place dead row: not at all).
+ * No atomics, no workspace, no allocation; K is never split across workgroups; two calls give the
+ * same bits.
+ * Refused before any launch, out untouched: everything trlx_t5_decode_linear refuses, with its
+ * statuses; live off the 8-byte grid or sharing a byte range with out (TRLX_ERR_ARG); M above
+ * 65535 * rows_per_block (the grid's second dimension), or above max_m_live = 4096 with live
+ * (TRLX_ERR_SHAPE).  max_m_live is a bound on a cost, not on the scan, which would run for any M:
+ * every workgroup reads up to M live words from L2, 32 KB at 4096 rows, and only M 256 is measured.
+ * trlx_t5_decode_linear_rows_geometry is a host call and needs no device. */
+typedef struct trlx_t5_decode_linear_rows_args {
+    const void* x;
+    int64_t ld_x;
+    const void* weight;
+    int64_t ld_w;
+    const void* norm_weight;          /* [K] or NULL */
+    const void* residual;             /* [M, N] or NULL */
+    int64_t ld_residual;
+    void* out;
+    int64_t ld_out;
+    int64_t M;
+    int64_t K;
+    int64_t N;                        /* output columns */
+    float eps;
+    int dtype;                        /* TRLX_BF16 */
+    int act;                          /* trlx_t5_act or TRLX_T5_ACT_NONE */
+    int gated;                        /* weight is [2N, K] */
+    const int64_t* live;              /* device int64 [M], nonzero = live, or NULL */
+    int64_t reserved;                 /* 0 */
+} trlx_t5_decode_linear_rows_args;
+typedef struct TrlxT5DecodeLinearRowsGeometry {
+    int threads;                      /* per workgroup */
+    int cols_per_block;               /* output columns a workgroup owns */
+    int rows_per_tile;
+    int rows_per_block;               /* rows a workgroup owns: the grid's second dimension is ceil(M / this) */
+    int max_m_live;                   /* the largest M taken with live */
+    int reserved;
+} TrlxT5DecodeLinearRowsGeometry;
+int trlx_t5_decode_linear_rows(const trlx_t5_decode_linear_rows_args* a, void* stream);
+int trlx_t5_decode_linear_rows_geometry(TrlxT5DecodeLinearRowsGeometry* g);
+
 /* ---------------------------------------------------------------- §8f: device-resident rollout store
  * Row copy between padded columnar [rows, W] buffers — replaces the reference's
  * `.cpu()` of the experience tensors, per-sample PPORLElement lists and the pad_sequence

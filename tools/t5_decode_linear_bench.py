@@ -1,6 +1,11 @@
 """t5_decode_linear against the launches it replaces, per fused call, inside replayed graphs.
 
-Calls (K -> N), each at M 8 and M 256, for T5-base (D 768, inner 768, F 2048 gated) and a d_model
+Three routes per call: `fused` (trlx_t5_decode_linear: every row in each workgroup), `rows`
+(split_rows=True, trlx_t5_decode_linear_rows: the rows spread over workgroups) and `unfused`
+(hipBLASLt and its neighbours).  At M 256 the rows route also runs with live=: a fixed scattered
+pattern of live fractions 1.0 / 0.52 / 0.25 (`rows_live_1.0` ...), the finished rows skipped on the device.
+
+Calls (K -> N), each at M 8, 32, 64, 128 and 256, for T5-base (D 768, inner 768, F 2048 gated) and a d_model
 4096 shape (inner 4096, F 10240 gated, T5-XXL's):
 
   norm_qkv        [norm -> qkv]         against t5_rmsnorm + torch.matmul
@@ -46,9 +51,32 @@ SHAPES = {"t5_base": dict(D=768, inner=768, F=2048), "d_model_4096": dict(D=4096
 ACT = "gelu_new"
 
 
-def build_routes(shape, M, dev, with_lm_head):
+LIVE_FRACTIONS = (1.0, 0.52, 0.25)
+LIVE_AT_M = 256
+
+
+def live_pattern(M, frac, dev):
+    """round(M * frac) live rows at fixed, scattered places (tools/t5_rollout_bench.py's pattern)."""
+    n = max(1, round(M * frac))
+    perm = torch.randperm(M, generator=torch.Generator().manual_seed(17))
+    live = torch.zeros(M, dtype=torch.int64)
+    live[perm[:n]] = 1
+    return live.to(dev)
+
+
+def sides_of(M):
+    """route name -> the keywords t5_decode_linear takes on it (None: the unfused route)."""
+    sides = {"fused": {}, "rows": dict(split_rows=True), "unfused": None}
+    if M == LIVE_AT_M:
+        for f in LIVE_FRACTIONS:
+            sides[f"rows_live_{f}"] = dict(split_rows=True, live=f)
+    return sides
+
+
+def build_routes(shape, M, dev, with_lm_head, kw):
     """{call: {"fused": fn(i), "unfused": fn(i), "weight_bytes": n, "launches": (fused, unfused)}}; fn(i)
-    issues call number i on copy i % COPIES."""
+    issues call number i on copy i % COPIES.  kw: what every t5_decode_linear call of "fused" takes on top
+    (split_rows, live)."""
     D, inner, F = shape["D"], shape["inner"], shape["F"]
     g = torch.Generator(device=dev).manual_seed(M + D)
 
@@ -62,7 +90,9 @@ def build_routes(shape, M, dev, with_lm_head):
     ln = [(1.0 + 0.1 * torch.randn(D, generator=g, device=dev)).to(DT) for _ in range(COPIES)]
     h, a, f = buf(D), buf(inner), buf(F)
     o_qkv, o_cq, o_ff, o_d = buf(3 * inner), buf(inner), buf(F), buf(D)
-    lin = P.t5_decode_linear
+    def lin(*a, **k):
+        return P.t5_decode_linear(*a, **k, **kw)
+
     nbytes = {k: v[0].numel() * 2 for k, v in W.items()}
     R = {}
 
@@ -131,12 +161,20 @@ def capture(fn):
 
 
 def run_shape(name, M, dev, reps):
-    routes = build_routes(SHAPES[name], M, dev, with_lm_head=name == "t5_base")
-    graphs = {}
+    sides = sides_of(M)
+    graphs, alive = {}, []
     with torch.no_grad():
-        for call, r in routes.items():
-            for side in ("fused", "unfused"):
-                graphs[(call, side)] = capture(r[side])
+        # every side on tensors of its own, built from the same seed: the same values
+        for side, kw in sides.items():
+            if kw is not None and "live" in kw:
+                kw = dict(kw, live=live_pattern(M, kw["live"], dev))
+            routes = build_routes(SHAPES[name], M, dev, with_lm_head=name == "t5_base" and side in ("fused", "rows", "unfused"),
+                                  kw=kw or {})
+            alive.append(routes)       # a graph holds addresses, not tensors: every side's tensors live until the last replay
+            if side == "fused":
+                calls = routes                                    # the calls, their bytes and launch counts
+            for call, r in routes.items():
+                graphs[(call, side)] = capture(r["unfused" if kw is None else "fused"])
         keys = list(graphs)
         samples = {k: [] for k in keys}
         rng = random.Random(M)
@@ -153,15 +191,23 @@ def run_shape(name, M, dev, reps):
                 e1.synchronize()
                 samples[k].append(e0.elapsed_time(e1) * 1000.0 / CALLS)
     out = {}
-    for call, r in routes.items():
+    for call, r in calls.items():
         row = {"weight_bytes": r["weight_bytes"], "launches_fused": r["launches"][0], "launches_unfused": r["launches"][1]}
-        for side in ("fused", "unfused"):
+        for side in sides:
+            if (call, side) not in samples:
+                continue
             s = samples[(call, side)]
             med = statistics.median(s)
             row[side] = {"us_per_call_median": med, "min": min(s), "max": max(s),
                          "weight_GB_per_s_at_median": r["weight_bytes"] / med / 1e3}
-        row["fused_over_unfused"] = row["fused"]["us_per_call_median"] / row["unfused"]["us_per_call_median"]
-        row["faster"] = "fused" if row["fused_over_unfused"] < 1.0 else "unfused (hipBLASLt and its neighbours)"
+        med = {side: row[side]["us_per_call_median"] for side in sides if side in row}
+        row["fused_over_unfused"] = med["fused"] / med["unfused"]
+        row["rows_over_fused"] = med["rows"] / med["fused"]
+        row["rows_over_unfused"] = med["rows"] / med["unfused"]
+        # the claim of the row split: faster than fused by more than fused's own min-max spread
+        row["rows_beats_fused_by_more_than_fuseds_spread"] = med["fused"] - med["rows"] > row["fused"]["max"] - row["fused"]["min"]
+        names = {"fused": "fused", "rows": "rows", "unfused": "unfused (hipBLASLt and its neighbours)"}
+        row["faster"] = names[min(names, key=med.get)]
         out[call] = row
     return out
 
@@ -197,7 +243,7 @@ def parity(dev, out_path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--rows", default="8,256")
+    ap.add_argument("--rows", default="8,32,64,128,256")
     ap.add_argument("--shapes", default="t5_base,d_model_4096")
     ap.add_argument("--parity", action="store_true")
     ap.add_argument("--out", default=None)
@@ -207,15 +253,16 @@ def main():
     if args.parity:
         return parity(dev, args.out or os.path.join(ROOT, "profiles", "t5_decode_linear_parity.json"))
     result = {"tool": "tools/t5_decode_linear_bench.py", "device": torch.cuda.get_device_name(0), "dtype": "bf16",
-              "shapes": SHAPES, "act": ACT,
+              "shapes": SHAPES, "act": ACT, "rows_geometry": sys.modules[P.__name__ + ".t5_decode_linear"].rows_geometry(),
+              "routes": "fused = trlx_t5_decode_linear; rows = trlx_t5_decode_linear_rows (split_rows=True); rows_live_F = rows "
+                        f"with live= at live fraction F (M {LIVE_AT_M} only); unfused = torch.matmul and its neighbours",
               "timing": f"one captured graph of {CALLS} back-to-back calls per route, rotating over {COPIES} copies of the "
                         f"weights and buffers; routes interleaved and shuffled per repetition; HIP events around one replay / "
                         f"{CALLS}; median of {args.reps} with min-max, microseconds per call"}
     for name in args.shapes.split(","):
         for M in (int(m) for m in args.rows.split(",")):
             result[f"{name}_M{M}"] = run_shape(name, M, dev, args.reps)
-            print(f"{name} M {M}: " + json.dumps({k: (round(v["fused"]["us_per_call_median"], 2),
-                                                      round(v["unfused"]["us_per_call_median"], 2))
+            print(f"{name} M {M}: " + json.dumps({k: {s: round(v[s]["us_per_call_median"], 2) for s in sides_of(M) if s in v}
                                                   for k, v in result[f"{name}_M{M}"].items()}))
             torch.cuda.empty_cache()
     out = args.out or os.path.join(ROOT, "profiles", "t5_decode_linear_bench.json")

@@ -1,6 +1,6 @@
 """The captured decode step of tools/t5_decode_graph_bench.py made autoregressive: the token drawn at
 step t - 1 is fed back through the `shared` embedding table, and the rows that have finished are
-skipped in both attentions.  Four routes, each ONE captured step (torch.cuda.graph) replayed once
+skipped in both attentions.  Six routes, each ONE captured step (torch.cuda.graph) replayed once
 per token:
 
   c0_torch_feedback   the feedback as torch ops (a gather of rec.tokens at an index tensor derived
@@ -22,6 +22,11 @@ per token:
                       c2.  It rounds differently, so it need not record c2's rollout: its drift against
                       c2 is reported by the method of c3's, beside its time and the launches per step
 
+  c5_fused_rows_skip  c4 with split_rows=True and live=rec.unfinished in the six projections of every
+                      layer (trlx_t5_decode_linear_rows): the rows spread over workgroups and the
+                      finished rows' projections skipped on the device.  Per live row it computes c4's
+                      bits; its drift against c2 is reported as c4's
+
 The decoder is the graph bench's (L 12, nH 12, d_kv 64, D 768, F 2048 gated, V 32128, S 512, T 48,
 bf16, at B 256 and B 8) with a `shared` [V, D] table.  The recorder is built with eos_token_id=None
 and rec.unfinished is preset to a fixed pattern, so the sampler never changes it; every route runs at
@@ -33,7 +38,8 @@ rollouts with min-max, in ms per token.  No speed-up is assumed: the output name
 per shape and fraction and says where c2 does not beat c1 or c1 does not beat c0.
 
 --parent-lib PATH: also the A/B of the entries that existed before (trlx_t5_decode_attn, self at
-t 47 and cross at S 512 with the key mask, T5-base B 256) against another build of the library, in
+t 47 and cross at S 512 with the key mask, T5-base B 256; trlx_t5_decode_linear, norm -> qkv at
+T5-base, M 8) against another build of the library, in
 alternating child processes, four runs each: this tree's median must lie inside the other build's
 own min-max spread, else it is reported as a regression with both spreads.
 
@@ -94,22 +100,23 @@ class RolloutDecoder(G.Decoder):
         clock, _, rec, out = state
         return P.t5_decode_embed(self.shared, rec, clock, START, self.layers[0]["ln"][0], out=out)
 
-    def token_fused(self, state):
+    def token_fused(self, state, rows=False):
         clock, caches, rec, out = state
         h, _ = P.t5_decode_embed(self.shared, rec, clock, START, out=(out[0], None))
         kw = dict(live=rec.unfinished)
+        lkw = dict(live=rec.unfinished, split_rows=True) if rows else {}
         for i, (w, blk) in enumerate(zip(self.layers, self.blocks)):
             P.t5_decode_layer_fused(
                 h, blk, lambda q, kn, vn: P.t5_decode_self_attention(q, kn, vn, caches[i], clock, self.table, **kw),
-                lambda q: P.t5_decode_cross_attention(q, w["k_enc"], w["v_enc"], self.mask, **kw), bufs=self.bufs)
+                lambda q: P.t5_decode_cross_attention(q, w["k_enc"], w["v_enc"], self.mask, **kw), bufs=self.bufs, **lkw)
         y = P.t5_rmsnorm(h, self.final_ln)
         logits, ref = torch.matmul(y, self.lm), torch.matmul(y, self.ref_lm)
         P.ppo_sample_step(logits, ref_logits=ref, recorder=rec, u=self.u, out=self.out, top_k=50, top_p=0.95)
         clock.advance()
 
     def token(self, state, route):
-        if route == "c4_fused_projections":
-            return self.token_fused(state)
+        if route in ("c4_fused_projections", "c5_fused_rows_skip"):
+            return self.token_fused(state, rows=route == "c5_fused_rows_skip")
         clock, caches, rec, _ = state
         h, y = self.feed_torch(state) if route == "c0_torch_feedback" else self.feed_kernel(state)
         kw = dict(live=rec.unfinished) if route in ("c2_embed_live_skip", "c3_live_skip_kv8") else {}
@@ -132,11 +139,12 @@ class RolloutDecoder(G.Decoder):
 
 
 EXACT_ROUTES = ("c0_torch_feedback", "c1_decode_embed", "c2_embed_live_skip")   # these record one rollout
-ROUTES = EXACT_ROUTES + ("c3_live_skip_kv8", "c4_fused_projections")
+ROUTES = EXACT_ROUTES + ("c3_live_skip_kv8", "c4_fused_projections", "c5_fused_rows_skip")
 # launches of one step, counted from the step's code: the feedback, 12 (or 8) per layer, the final norm of
 # c4, two lm_head matmuls, the sampler, the clock
 LAUNCHES = {"c0_torch_feedback": None, "c1_decode_embed": 1 + 12 * L + 4, "c2_embed_live_skip": 1 + 12 * L + 4,
-            "c3_live_skip_kv8": 1 + 12 * L + 4, "c4_fused_projections": 1 + 8 * L + 1 + 4}
+            "c3_live_skip_kv8": 1 + 12 * L + 4, "c4_fused_projections": 1 + 8 * L + 1 + 4,
+            "c5_fused_rows_skip": 1 + 8 * L + 1 + 4}
 
 
 def kv8_drift(rec2, rec3):
@@ -189,6 +197,9 @@ def run_shape(B, dev, reps):
                    for r in EXACT_ROUTES[1:] for f in ("tokens", "logprobs", "ref_logprobs"))
         drift = kv8_drift(states["c2_embed_live_skip"][2], states["c3_live_skip_kv8"][2])
         drift4 = kv8_drift(states["c2_embed_live_skip"][2], states["c4_fused_projections"][2])
+        drift5 = kv8_drift(states["c2_embed_live_skip"][2], states["c5_fused_rows_skip"][2])
+        c5_is_c4 = all(torch.equal(getattr(states["c4_fused_projections"][2], f), getattr(states["c5_fused_rows_skip"][2], f))
+                       for f in ("tokens", "logprobs", "ref_logprobs"))
         assert all(states[r][0].t == T and states[r][0].overrun == 0 for r in ROUTES)
         keys = [(r, f) for r in ROUTES for f in FRACTIONS]
         samples = {k: [] for k in keys}
@@ -208,6 +219,8 @@ def run_shape(B, dev, reps):
                 samples[(r, f)].append(e0.elapsed_time(e1) / T)
     res = {"routes_record_the_same_rollout_at_fraction_1": bool(same), "c3_kv8_against_c2_at_fraction_1": drift,
            "c4_fused_projections_against_c2_at_fraction_1": drift4,
+           "c5_fused_rows_skip_against_c2_at_fraction_1": drift5,
+           "c5_records_c4s_rollout_at_fraction_1": bool(c5_is_c4),
            "launches_per_step_counted_from_the_code": LAUNCHES}
     for f in FRACTIONS:
         per = {r: {"ms_per_token_median": statistics.median(samples[(r, f)]), "min": min(samples[(r, f)]),
@@ -221,13 +234,18 @@ def run_shape(B, dev, reps):
         per["c3_over_c2"] = med["c3_live_skip_kv8"] / med["c2_embed_live_skip"]
         per["c4_beats_c2"] = med["c4_fused_projections"] < med["c2_embed_live_skip"]
         per["c4_over_c2"] = med["c4_fused_projections"] / med["c2_embed_live_skip"]
+        per["c5_beats_c4"] = med["c5_fused_rows_skip"] < med["c4_fused_projections"]
+        per["c5_over_c4"] = med["c5_fused_rows_skip"] / med["c4_fused_projections"]
+        per["c5_beats_c2"] = med["c5_fused_rows_skip"] < med["c2_embed_live_skip"]
+        per["c5_over_c2"] = med["c5_fused_rows_skip"] / med["c2_embed_live_skip"]
         res[f"live_{f}"] = per
     return res
 
 
 # ------------------------------------------------------------------ the entries that existed before
 def ab_child():
-    """Per-call µs of trlx_t5_decode_attn (self, cross) on whatever library TRLX_T5_AMD_LIB names."""
+    """Per-call µs of trlx_t5_decode_attn (self, cross) and trlx_t5_decode_linear (norm -> qkv, M 8) on
+    whatever library TRLX_T5_AMD_LIB names."""
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for n in [n for n in _lib.SIGNATURES if not hasattr(lib, n)]:   # an older build lacks the newer entries
         del _lib.SIGNATURES[n]
@@ -251,8 +269,17 @@ def ab_child():
     def cross_attn():
         P.t5_decode_cross_attention(q, k_enc, v_enc, mask)
 
+    h8 = torch.randn(8, D, generator=g, device=dev).to(DT)
+    w_qkv = (torch.randn(3 * INNER, D, generator=g, device=dev) * D ** -0.5).to(DT)
+    ln = (1.0 + 0.1 * torch.randn(D, generator=g, device=dev)).to(DT)
+    o_qkv = torch.empty(8, 3 * INNER, dtype=DT, device=dev)
+
+    def norm_qkv():
+        P.t5_decode_linear(h8, w_qkv, norm_weight=ln, out=o_qkv)
+
     res = {}
-    for name, fn in (("t5_decode_attn_self_B256_t47", self_attn), ("t5_decode_attn_cross_B256_S512", cross_attn)):
+    for name, fn in (("t5_decode_attn_self_B256_t47", self_attn), ("t5_decode_attn_cross_B256_S512", cross_attn),
+                     ("t5_decode_linear_norm_qkv_M8", norm_qkv)):
         for _ in range(20):
             fn()
         per = []

@@ -69,7 +69,9 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
   t5_decode_linear, T5DecodeBlockWeights, t5_decode_layer_fused — opt-in: a decode step's projections
       on a skinny MFMA kernel of our own with the RMSNorm in front, the residual add behind and the
       gated activation behind `wi` in the same launch: a decoder layer's decode step in 8 launches
-      instead of 12 (HF T5Block under generate; every other projection stays hipBLASLt)
+      instead of 12 (HF T5Block under generate; every other projection stays hipBLASLt);
+      split_rows=True spreads the rows over workgroups and live=recorder.unfinished skips the
+      projections of finished rows on the device (trlx_t5_decode_linear_rows)
   PPORolloutStorage, PPORLElement, PPORLBatch
       trlx/pipeline/ppo_pipeline.py, trlx/data/ppo_types.py (device-resident store)
   ILQLRolloutStorage (.from_samples = make_experience, .collate, .create_loader), ILQLElement

@@ -203,6 +203,16 @@ class T5DecodeLinearGeometry(ctypes.Structure):
                                       "max_row_tiles", "max_k", "norm_max_k", "norm_wave_row_max_k", "reserved")]
 
 
+class T5DecodeLinearRowsArgs(ctypes.Structure):
+    """Mirror of trlx_t5_decode_linear_rows_args (include/trlx_t5_amd.h)."""
+    _fields_ = T5DecodeLinearArgs._fields_ + [("live", _c_vp), ("reserved", _c_i64)]
+
+
+class T5DecodeLinearRowsGeometry(ctypes.Structure):
+    """Mirror of TrlxT5DecodeLinearRowsGeometry (include/trlx_t5_amd.h)."""
+    _fields_ = [(n, _c_int) for n in ("threads", "cols_per_block", "rows_per_tile", "rows_per_block", "max_m_live", "reserved")]
+
+
 POLYAK_MAX_TENSORS = 16
 ADAMW_MAX_TENSORS = 32
 ADAMW_CHUNK = 8192  # elements of one tensor per workgroup
@@ -401,6 +411,8 @@ SIGNATURES = {
     "trlx_t5_rmsnorm_geometry": (_c_int, [_c_i64, _c_i64, ctypes.POINTER(T5RmsNormGeometry)]),
     "trlx_t5_decode_linear": (_c_int, [ctypes.POINTER(T5DecodeLinearArgs), _c_vp]),
     "trlx_t5_decode_linear_geometry": (_c_int, [ctypes.POINTER(T5DecodeLinearGeometry)]),
+    "trlx_t5_decode_linear_rows": (_c_int, [ctypes.POINTER(T5DecodeLinearRowsArgs), _c_vp]),
+    "trlx_t5_decode_linear_rows_geometry": (_c_int, [ctypes.POINTER(T5DecodeLinearRowsGeometry)]),
     "trlx_rows_copy": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                 _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_shift_tokens_right": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp]),

@@ -26,20 +26,30 @@ from . import _lib
 from .t5_ff import ACTS, _act_code, _torch_ff_act, t5_ff_act
 from .t5_norm import _torch_rmsnorm, t5_rmsnorm
 
-__all__ = ["t5_decode_linear", "T5DecodeBlockWeights", "t5_decode_layer_fused", "geometry", "COLS_PER_BLOCK", "K_PER_CHUNK",
-           "MAX_K", "NORM_MAX_K"]
+__all__ = ["t5_decode_linear", "T5DecodeBlockWeights", "t5_decode_layer_fused", "geometry", "rows_geometry", "COLS_PER_BLOCK",
+           "K_PER_CHUNK", "MAX_K", "NORM_MAX_K", "ROWS_PER_BLOCK", "MAX_M_LIVE"]
 
 # the kernel's grid (csrc/t5_decode_linear.hip; trlx_t5_decode_linear_geometry reports it)
 COLS_PER_BLOCK = 16     # N (F when gated) is a multiple of this
 K_PER_CHUNK = 32        # K is a multiple of this
 MAX_K = 16384
 NORM_MAX_K = 8192       # with norm_weight: t5_rmsnorm's limit
+# the rows form (csrc/t5_decode_linear_rows.hip; trlx_t5_decode_linear_rows_geometry reports it)
+ROWS_PER_BLOCK = 32     # rows a workgroup owns with split_rows / live
+MAX_M_LIVE = 4096       # the largest B the kernel takes with live
 
 
 def geometry():
     """trlx_t5_decode_linear_geometry as a dict (needs no device)."""
     g = _lib.T5DecodeLinearGeometry()
     _lib.call("trlx_t5_decode_linear_geometry", ctypes.byref(g))
+    return {n: getattr(g, n) for n, _ in g._fields_ if n != "reserved"}
+
+
+def rows_geometry():
+    """trlx_t5_decode_linear_rows_geometry as a dict (needs no device)."""
+    g = _lib.T5DecodeLinearRowsGeometry()
+    _lib.call("trlx_t5_decode_linear_rows_geometry", ctypes.byref(g))
     return {n: getattr(g, n) for n, _ in g._fields_ if n != "reserved"}
 
 
@@ -77,7 +87,21 @@ def _on_grid(t):
             (t.shape[0] == 1 or (t.stride(0) >= t.shape[1] and t.stride(0) % 8 == 0)))
 
 
-def t5_decode_linear(x, weight, *, norm_weight=None, eps=1e-6, residual=None, act=None, gated=False, out=None):
+def _check_live(who, live, B, device):
+    if not isinstance(live, torch.Tensor) or live.dtype != torch.int64 or live.dim() != 1 or live.shape[0] != B \
+            or live.device != device or not live.is_contiguous():
+        got = f"{live.dtype} {tuple(live.shape)} on {live.device}" if isinstance(live, torch.Tensor) else type(live).__name__
+        raise ValueError(f"{who}: live must be a contiguous int64 [{B}] on {device}, got {got}")
+
+
+def _apply_dead_rows(got, live, r2):
+    """The dead-row rule on a result computed for all rows: zeros, or the residual's row."""
+    on = (live != 0)[:, None]
+    return torch.where(on, got, torch.zeros_like(got) if r2 is None else r2.to(got.dtype))
+
+
+def t5_decode_linear(x, weight, *, norm_weight=None, eps=1e-6, residual=None, act=None, gated=False, out=None,
+                     live=None, split_rows=False):
     """out = epilogue(prologue(x) @ weight.T) in one launch, bf16 with fp32 accumulation.
 
     x: [B, K] or [B, 1, K]; rows K unit-stride elements one stride apart are read in place
@@ -94,7 +118,17 @@ def t5_decode_linear(x, weight, *, norm_weight=None, eps=1e-6, residual=None, ac
     allocation beyond `out`, the same arguments at every token: the call can be captured.
     On a CPU device, or for a dtype or shape the kernel does not take by design (anything but bf16, K
     not a multiple of 32 or above 16384, above 8192 with norm_weight, N not a multiple of 16), the
-    same expression runs as t5_rmsnorm, F.linear, the add, t5_ff_act."""
+    same expression runs as t5_rmsnorm, F.linear, the add, t5_ff_act.
+
+    split_rows=True or a `live` takes trlx_t5_decode_linear_rows (csrc/t5_decode_linear_rows.hip): the
+    rows spread over workgroups, ROWS_PER_BLOCK per workgroup, instead of every row in each.  A live
+    row's result has the bits of the default call.  Opt-in: nothing here chooses by B.
+    live: a contiguous int64 [B] on x's device, nonzero = live (the rollout recorder's `unfinished` as
+    it is; B at most MAX_M_LIVE), read on the device, so the call stays the same launch at every token.  A dead row behaves
+    as a zero input row and nothing of x is read for it: zeros in the plain, norm and act forms, the
+    residual's row in the residual form, and left untouched when `out` is the residual.  The torch
+    route computes every row and then applies the same rule.  As with the attentions' `live`, the
+    skip is for a rollout sampled with score_finished=False, where nothing reads a finished row."""
     ts = [t for t in (x, weight, norm_weight, residual, out) if t is not None]
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise TypeError("t5_decode_linear: x, weight, norm_weight, residual and out must be tensors")
@@ -131,9 +165,13 @@ def t5_decode_linear(x, weight, *, norm_weight=None, eps=1e-6, residual=None, ac
     o2 = out if out is None or out.dim() == 2 else out[:, 0, :]
     if o2 is not None and o2.stride(1) != 1:
         raise ValueError("t5_decode_linear: out must have unit element stride")
+    if live is not None:
+        _check_live("t5_decode_linear", live, B, x.device)
 
     if not _kernel_takes(x2, weight, norm_weight, K, N):
         got = _torch_decode_linear(x2, weight, norm_weight, eps, r2, act, gated)
+        if live is not None:
+            got = _apply_dead_rows(got, live, r2)
         if out is None:
             return got.view(*lead, N)
         o2.copy_(got)
@@ -155,12 +193,17 @@ def t5_decode_linear(x, weight, *, norm_weight=None, eps=1e-6, residual=None, ac
         o2 = out.view(B, N)
     elif not _on_grid(o2):
         raise ValueError("t5_decode_linear: out must be 16-byte aligned with a row stride that is a multiple of 8 elements")
-    args = _lib.T5DecodeLinearArgs(
+    fields = dict(
         x=x2.data_ptr(), ld_x=_ld(x2), weight=weight.data_ptr(), ld_w=_ld(weight), norm_weight=_lib.ptr(norm_weight),
         residual=_lib.ptr(r2), ld_residual=N if r2 is None else _ld(r2), out=o2.data_ptr(), ld_out=_ld(o2),
         M=B, K=K, N=N, eps=float(eps), dtype=_lib.BF16, act=_lib.T5_ACT_NONE if act is None else ACTS[act],
         gated=int(bool(gated)))
-    _lib.call("trlx_t5_decode_linear", ctypes.byref(args), _lib.stream_of(x2))
+    if live is not None or split_rows:
+        args = _lib.T5DecodeLinearRowsArgs(live=_lib.ptr(live), reserved=0, **fields)
+        _lib.call("trlx_t5_decode_linear_rows", ctypes.byref(args), _lib.stream_of(x2))
+    else:
+        args = _lib.T5DecodeLinearArgs(**fields)
+        _lib.call("trlx_t5_decode_linear", ctypes.byref(args), _lib.stream_of(x2))
     return out
 
 
@@ -223,22 +266,29 @@ class T5DecodeBlockWeights:
         return {prefix + k: v for k, v in sd.items()}
 
 
-def t5_decode_layer_fused(h, w, self_attention, cross_attention, act="gelu_new", eps=1e-6, bufs=None):
+def t5_decode_layer_fused(h, w, self_attention, cross_attention, act="gelu_new", eps=1e-6, bufs=None, live=None,
+                          split_rows=False):
     """One decoder layer's decode step on the residual stream h [B, D], updated in place, in 8 launches.
 
     w: T5DecodeBlockWeights.  self_attention(q, k_new, v_new) and cross_attention(q) are the caller's
     attention launches (t5_decode_self_attention with its cache, clock, bias table and live rows;
     t5_decode_cross_attention or its kv8 form) and return [B, inner].  bufs: None, or a dict with
     preallocated "qkv" [B, 3 inner], "cq" [B, inner] and "ff" [B, F] so that a captured step allocates
-    nothing in the projections.  Returns h."""
+    nothing in the projections.
+    live, split_rows: passed to the six projections (t5_decode_linear): the rows spread over workgroups,
+    and with live=recorder.unfinished the rows that have finished skipped -- their qkv, cq and ff rows
+    are zeros and their row of h is left as it was.  The attentions take their own `live`.  As theirs,
+    the skip is for score_finished=False: a finished row's h is no longer the layer's output.
+    Returns h."""
     bufs = bufs or {}
     i = w.inner
-    qkv = t5_decode_linear(h, w.qkv, norm_weight=w.ln[0], eps=eps, out=bufs.get("qkv"))
+    kw = dict(live=live, split_rows=split_rows)
+    qkv = t5_decode_linear(h, w.qkv, norm_weight=w.ln[0], eps=eps, out=bufs.get("qkv"), **kw)
     a = self_attention(qkv[:, :i], qkv[:, i:2 * i], qkv[:, 2 * i:])
-    t5_decode_linear(a, w.o, residual=h, out=h)
-    q = t5_decode_linear(h, w.cq, norm_weight=w.ln[1], eps=eps, out=bufs.get("cq"))
+    t5_decode_linear(a, w.o, residual=h, out=h, **kw)
+    q = t5_decode_linear(h, w.cq, norm_weight=w.ln[1], eps=eps, out=bufs.get("cq"), **kw)
     c = cross_attention(q)
-    t5_decode_linear(c, w.co, residual=h, out=h)
-    f = t5_decode_linear(h, w.wi, norm_weight=w.ln[2], eps=eps, act=act, gated=w.gated, out=bufs.get("ff"))
-    t5_decode_linear(f, w.wo, residual=h, out=h)
+    t5_decode_linear(c, w.co, residual=h, out=h, **kw)
+    f = t5_decode_linear(h, w.wi, norm_weight=w.ln[2], eps=eps, act=act, gated=w.gated, out=bufs.get("ff"), **kw)
+    t5_decode_linear(f, w.wo, residual=h, out=h, **kw)
     return h
