@@ -1127,6 +1127,60 @@ int trlx_t5_cross_kv_quantize(const TrlxT5CrossKvQuantArgs* a, void* stream);
 int trlx_t5_decode_attn_kv8(const TrlxT5DecodeAttnArgs* a, const float* k_scale, const float* v_scale,
                             const int64_t* live, void* stream);
 
+/* ---------------------------------------------------------------- encoder keys shared by a prompt's samples
+ * trlx_t5_decode_attn, mode TRLX_T5_ATTN_CROSS, for a rollout that draws G samples per prompt
+ * (num_return_sequences, RLOO / GRPO groups, best-of-G): the encoder's keys and values are kept
+ * once per prompt, [P, ...], and row b = p * G + g of q / out / live is sample g of prompt p — the
+ * order of repeat_interleave(G, dim = 0).  ONE launch, one workgroup per (prompt, head, tile of
+ * queries): each key and value row is loaded once and applied to every query of the tile, so the
+ * K / V bytes per token and the K / V memory are those of trlx_t5_decode_attn divided by G.
+ *   q, out   : [P * G, n_heads * d_kv] of `dtype`; q as a base pointer + row stride ldq as in
+ *              trlx_t5_decode_attn (with P * G == 1 the stride is not read), out contiguous.
+ *   k, v     : [P, n_heads, S, d_kv] of `dtype`, read only, as a base pointer + element strides
+ *              over (p, h, s), unit stride along d_kv: a contiguous [P, nH, S, d] tensor (strides
+ *              nH*S*d, S*d, d) and the projection output [P, S, nH*d] (strides S*nH*d, d, nH*d) are
+ *              both read in place.  The stride of a dimension of size 1 is not read.
+ *   key_mask : int64 [P, S], per prompt, 0 = masked, or NULL.  A masked key's K and V rows are not
+ *              read; a prompt whose keys are all masked gives zeros in all its rows.
+ *   live     : int64 [P * G], 0 or non-zero (the recording step's `unfinished` as it is), or NULL.
+ *              A workgroup whose queries are all dead loads those words, writes zeros to their out
+ *              rows and returns, before any barrier and before it forms an address into q, k, v
+ *              or key_mask.  Otherwise a dead query gets zeros and its q row is not read.  A live
+ *              query is bit-identical to the call without live.
+ * Per query the floating-point operations and their order are those of trlx_t5_decode_attn: out is
+ * bit-identical to trlx_t5_decode_attn on the keys, values and mask repeated G times, whatever the
+ * strides and the tile.  G == 1 is that call.  The launch takes the same arguments at every token:
+ * it captures as it is.
+ * Refused with TRLX_ERR_ARG before any launch: a NULL a / q / k / v / out, a dtype other than
+ * TRLX_F32 / TRLX_BF16, a d_kv other than 64 / 128, P, G, n_heads or S < 1, ldq below n_heads * d_kv
+ * or not a whole number of 16-byte vectors, a stride that is negative or not a whole number of
+ * 16-byte vectors, a head or key stride below d_kv, q / k / v / out not 16-byte aligned, key_mask /
+ * live not 8-byte aligned, a P, G, n_heads or S whose grid would overflow. */
+typedef struct TrlxT5DecodeAttnGroupArgs {
+    const void* q;
+    int64_t ldq;
+    const void* k;
+    int64_t k_stride_p, k_stride_h, k_stride_s;
+    const void* v;
+    int64_t v_stride_p, v_stride_h, v_stride_s;
+    const int64_t* key_mask;          /* [P, S] int64, 0 = masked, or NULL */
+    const int64_t* live;              /* [P * G] int64, 0 = skip, or NULL */
+    void* out;                        /* [P * G, n_heads * d_kv], contiguous */
+    int64_t P;
+    int64_t G;
+    int64_t n_heads;
+    int64_t d_kv;                     /* 64 or 128 */
+    int64_t S;
+    int dtype;                        /* TRLX_F32 / TRLX_BF16: q, k, v, out */
+} TrlxT5DecodeAttnGroupArgs;
+int trlx_t5_decode_attn_group(const TrlxT5DecodeAttnGroupArgs* a, void* stream);
+
+/* The largest query tile trlx_t5_decode_attn_group takes: 0 (the default: the measured choice, 4),
+ * 1, 2, 4 or 8; anything else is refused with TRLX_ERR_ARG.  Process-wide.  A G below the tile
+ * takes the smallest built tile that holds G.  The result does not depend on it; the benchmark
+ * tool sets it to time each built tile. */
+int trlx_t5_decode_attn_group_tile(int64_t tile);
+
 /* The decoder's input row of decode step t, ONE launch — replaces, per generated token, the
  * gather of the token drawn at step t - 1, the `shared` embedding lookup (T5 applies no scale)
  * and layer 0's first T5LayerNorm.  clock == NULL: t is a->t; otherwise t and the capacity are

@@ -27,6 +27,12 @@ per token:
                       finished rows' projections skipped on the device.  Per live row it computes c4's
                       bits; its drift against c2 is reported as c4's
 
+  c2_expanded_G4 / c2_grouped_G4 (their own section of the output, B 256 = 64 prompts x 4 samples):
+                      c2 fed the keys / values of 64 prompts repeat_interleave'd to 256 rows, and c2 with
+                      t5_decode_cross_attention_grouped over the ONE copy of those 64 prompts in all
+                      twelve layers.  The two must record one rollout bit for bit -- asserted before
+                      anything is timed -- and the K / V memory each holds is reported beside its time
+
 The decoder is the graph bench's (L 12, nH 12, d_kv 64, D 768, F 2048 gated, V 32128, S 512, T 48,
 bf16, at B 256 and B 8) with a `shared` [V, D] table.  The recorder is built with eos_token_id=None
 and rec.unfinished is preset to a fixed pattern, so the sampler never changes it; every route runs at
@@ -114,12 +120,21 @@ class RolloutDecoder(G.Decoder):
         P.ppo_sample_step(logits, ref_logits=ref, recorder=rec, u=self.u, out=self.out, top_k=50, top_p=0.95)
         clock.advance()
 
+    def share_prompts(self, G):
+        """The first B / G prompts' keys, values and mask once ([P, ...]) and repeat_interleave'd to B rows."""
+        Pn = self.B // G
+        self.shared_kv = [(w["k_enc"][:Pn].contiguous(), w["v_enc"][:Pn].contiguous()) for w in self.layers]
+        self.expanded_kv = [(k.repeat_interleave(G, 0).contiguous(), v.repeat_interleave(G, 0).contiguous())
+                            for k, v in self.shared_kv]
+        self.shared_mask = self.mask[:Pn].contiguous()
+        self.expanded_mask = self.shared_mask.repeat_interleave(G, 0).contiguous()
+
     def token(self, state, route):
         if route in ("c4_fused_projections", "c5_fused_rows_skip"):
             return self.token_fused(state, rows=route == "c5_fused_rows_skip")
         clock, caches, rec, _ = state
         h, y = self.feed_torch(state) if route == "c0_torch_feedback" else self.feed_kernel(state)
-        kw = dict(live=rec.unfinished) if route in ("c2_embed_live_skip", "c3_live_skip_kv8") else {}
+        kw = dict(live=rec.unfinished) if route in ("c2_embed_live_skip", "c3_live_skip_kv8") + GROUP_ROUTES else {}
         for i, w in enumerate(self.layers):
             qkv = torch.matmul(y, w["qkv"])
             q, kn, vn = (qkv[:, j * INNER:(j + 1) * INNER] for j in range(3))
@@ -127,6 +142,10 @@ class RolloutDecoder(G.Decoder):
             h, y = P.t5_add_rmsnorm(torch.matmul(a, w["o"]), h, w["ln"][1])
             if route == "c3_live_skip_kv8":
                 c = P.t5_decode_cross_attention_kv8(torch.matmul(y, w["cq"]), self.kv8[i], self.mask, **kw)
+            elif route == "c2_expanded_G4":
+                c = P.t5_decode_cross_attention(torch.matmul(y, w["cq"]), *self.expanded_kv[i], self.expanded_mask, **kw)
+            elif route == "c2_grouped_G4":
+                c = P.t5_decode_cross_attention_grouped(torch.matmul(y, w["cq"]), *self.shared_kv[i], self.shared_mask, **kw)
             else:
                 c = P.t5_decode_cross_attention(torch.matmul(y, w["cq"]), w["k_enc"], w["v_enc"], self.mask, **kw)
             h, y = P.t5_add_rmsnorm(torch.matmul(c, w["co"]), h, w["ln"][2])
@@ -138,6 +157,8 @@ class RolloutDecoder(G.Decoder):
         clock.advance()
 
 
+GROUP_ROUTES = ("c2_expanded_G4", "c2_grouped_G4")
+GROUP_G = 4
 EXACT_ROUTES = ("c0_torch_feedback", "c1_decode_embed", "c2_embed_live_skip")   # these record one rollout
 ROUTES = EXACT_ROUTES + ("c3_live_skip_kv8", "c4_fused_projections", "c5_fused_rows_skip")
 # launches of one step, counted from the step's code: the feedback, 12 (or 8) per layer, the final norm of
@@ -242,6 +263,66 @@ def run_shape(B, dev, reps):
     return res
 
 
+def run_grouped(dev, reps, B=256):
+    """c2 at B = P x G = 64 x 4: the expanded keys / values against the one shared copy."""
+    dec = RolloutDecoder(B, dev)
+    dec.share_prompts(GROUP_G)
+    patterns = {f: live_pattern(B, f, dev) for f in FRACTIONS}
+    states, graphs = {}, {}
+    with torch.no_grad():
+        for r in GROUP_ROUTES:
+            st = states[r] = dec.state()
+            dec.token(st, r)                                      # warm-up
+            torch.cuda.synchronize()
+            st[0].reset()
+            graphs[r] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[r]):                     # one stream, a linear chain of launches
+                dec.token(st, r)
+        # before anything is timed: the two record one rollout, bit for bit, at every live fraction
+        for f in FRACTIONS:
+            for r in GROUP_ROUTES:
+                clock, _, rec, _ = states[r]
+                clock.reset()
+                rec.unfinished.copy_(patterns[f][0])
+                for _ in range(T):
+                    graphs[r].replay()
+            torch.cuda.synchronize()
+            a, b = (states[r][2] for r in GROUP_ROUTES)
+            for field in ("tokens", "logprobs", "ref_logprobs"):
+                x, y = getattr(a, field), getattr(b, field)
+                assert torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x,
+                                   y.view(torch.int32) if y.dtype == torch.float32 else y), (f, field)
+        assert all(states[r][0].t == T and states[r][0].overrun == 0 for r in GROUP_ROUTES)
+        keys = [(r, f) for r in GROUP_ROUTES for f in FRACTIONS]
+        samples = {k: [] for k in keys}
+        rng = random.Random(B + GROUP_G)
+        for _ in range(reps):
+            rng.shuffle(keys)
+            for r, f in keys:
+                clock, _, rec, _ = states[r]
+                clock.reset()
+                rec.unfinished.copy_(patterns[f][0])
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(T):
+                    graphs[r].replay()
+                e1.record()
+                e1.synchronize()
+                samples[(r, f)].append(e0.elapsed_time(e1) / T)
+    nbytes = lambda kv: sum(k.numel() * k.element_size() + v.numel() * v.element_size() for k, v in kv)  # noqa: E731
+    res = {"P": B // GROUP_G, "G": GROUP_G, "B": B,
+           "the_two_routes_record_one_rollout_bit_for_bit_at_every_fraction": True,
+           "kv_bytes_held": {"c2_expanded_G4": nbytes(dec.expanded_kv), "c2_grouped_G4": nbytes(dec.shared_kv)}}
+    for f in FRACTIONS:
+        per = {r: {"ms_per_token_median": statistics.median(samples[(r, f)]), "min": min(samples[(r, f)]),
+                   "max": max(samples[(r, f)])} for r in GROUP_ROUTES}
+        per["live_fraction_actual"] = patterns[f][1]
+        per["grouped_over_expanded"] = per["c2_grouped_G4"]["ms_per_token_median"] / per["c2_expanded_G4"]["ms_per_token_median"]
+        per["grouped_beats_expanded"] = per["grouped_over_expanded"] < 1.0
+        res[f"live_{f}"] = per
+    return res
+
+
 # ------------------------------------------------------------------ the entries that existed before
 def ab_child():
     """Per-call µs of trlx_t5_decode_attn (self, cross) and trlx_t5_decode_linear (norm -> qkv, M 8) on
@@ -323,6 +404,8 @@ def main():
     ap.add_argument("--batches", default="256,8")
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--ab-child", action="store_true")
+    ap.add_argument("--only-grouped", action="store_true",
+                    help="run the G 4 section alone and replace it in the --out file, keeping the file's other sections")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "t5_rollout_bench.json"))
     args = ap.parse_args()
     if args.ab_child:
@@ -335,10 +418,15 @@ def main():
         result["existing_entries_ab"] = existing_entries_ab(args.parent_lib)
         print(json.dumps(result["existing_entries_ab"]))
     dev = torch.device("cuda:0")
+    if args.only_grouped:
+        kept = json.load(open(args.out)) if os.path.exists(args.out) else {}
+        result = {**kept, **{k: v for k, v in result.items() if k == "existing_entries_ab"}}
     result["device"] = torch.cuda.get_device_name(0)
-    for B in (int(b) for b in args.batches.split(",")):
+    for B in (() if args.only_grouped else (int(b) for b in args.batches.split(","))):
         result[f"B{B}"] = run_shape(B, dev, args.reps)
         print(f"B {B}: " + json.dumps(result[f"B{B}"]))
+    result["grouped_P64_G4"] = run_grouped(dev, args.reps)
+    print("grouped P 64 x G 4: " + json.dumps(result["grouped_P64_G4"]))
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)

@@ -112,6 +112,17 @@ class T5CrossKvQuantArgs(ctypes.Structure):
     ]
 
 
+class T5DecodeAttnGroupArgs(ctypes.Structure):
+    """Mirror of TrlxT5DecodeAttnGroupArgs (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("q", _c_vp), ("ldq", _c_i64),
+        ("k", _c_vp), ("k_stride_p", _c_i64), ("k_stride_h", _c_i64), ("k_stride_s", _c_i64),
+        ("v", _c_vp), ("v_stride_p", _c_i64), ("v_stride_h", _c_i64), ("v_stride_s", _c_i64),
+        ("key_mask", _c_vp), ("live", _c_vp), ("out", _c_vp),
+        ("P", _c_i64), ("G", _c_i64), ("n_heads", _c_i64), ("d_kv", _c_i64), ("S", _c_i64), ("dtype", _c_int),
+    ]
+
+
 class T5DecodeEmbedArgs(ctypes.Structure):
     """Mirror of TrlxT5DecodeEmbedArgs (include/trlx_t5_amd.h)."""
     _fields_ = [
@@ -396,6 +407,8 @@ SIGNATURES = {
     "trlx_t5_decode_attn_live": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp, _c_vp, _c_vp]),
     "trlx_t5_cross_kv_quantize": (_c_int, [ctypes.POINTER(T5CrossKvQuantArgs), _c_vp]),
     "trlx_t5_decode_attn_kv8": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp, _c_vp, _c_vp, _c_vp]),
+    "trlx_t5_decode_attn_group": (_c_int, [ctypes.POINTER(T5DecodeAttnGroupArgs), _c_vp]),
+    "trlx_t5_decode_attn_group_tile": (_c_int, [_c_i64]),
     "trlx_t5_decode_embed": (_c_int, [ctypes.POINTER(T5DecodeEmbedArgs), _c_vp, _c_vp]),
     "trlx_t5_attention": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp]),
     "trlx_t5_attention_tiles": (_c_int, [ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),

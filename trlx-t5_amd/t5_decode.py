@@ -17,6 +17,10 @@
                              per (row, head), once per rollout: one launch, a T5CrossKV8
   t5_decode_cross_attention_kv8   the cross-attention over those bytes: half the K / V traffic per
                              token, fp32 arithmetic; opt-in and lossy (3 mantissa bits)
+  t5_decode_cross_attention_grouped   the cross-attention of a rollout that draws G samples per
+                             prompt over ONE copy of each prompt's keys / values: K / V bytes per
+                             token and K / V memory divided by G, every row bit-identical to
+                             t5_decode_cross_attention on the repeat_interleave'd tensors
 
 Per layer and generated token HF's eager T5Attention spends, between the projections and `o`, a
 cache append, a [B, nH, 1, t] matmul, compute_bias (arange, bucket formula, embedding lookup,
@@ -38,7 +42,7 @@ from . import _lib
 
 __all__ = ["t5_relative_bias_table", "T5DecodeKVCache", "T5DecodeClock", "t5_decode_self_attention",
            "t5_decode_cross_attention", "t5_decode_embed", "T5CrossKV8", "t5_quantize_cross_kv",
-           "t5_decode_cross_attention_kv8"]
+           "t5_decode_cross_attention_kv8", "t5_decode_cross_attention_grouped"]
 
 KERNEL_DTYPES = (torch.bfloat16, torch.float32)
 KERNEL_D_KV = (64, 128)
@@ -483,6 +487,105 @@ def t5_decode_cross_attention_kv8(q, kv8, key_mask=None, live=None):
     _lib.call("trlx_t5_decode_attn_kv8", ctypes.byref(args), kv8.k_scale.data_ptr(), kv8.v_scale.data_ptr(),
               _lib.ptr(live), _lib.stream_of(out))
     return out
+
+
+# ------------------------------------------------------------------ keys shared by a prompt's samples
+def _group_kv(x, name, n_heads):
+    """x as a [P, nH, S, d] view: [P, nH, S, d] as it is, the projection output [P, S, nH*d] with
+    n_heads= permuted (no copy)."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor, got {type(x).__name__}")
+    if x.dim() == 3:
+        if n_heads is None or int(n_heads) < 1 or x.shape[2] % int(n_heads):
+            raise ValueError(f"{name} is [P, S, nH*d_kv] = {tuple(x.shape)}: pass n_heads= (a divisor of the last dimension)")
+        x = x.unflatten(2, (int(n_heads), x.shape[2] // int(n_heads))).permute(0, 2, 1, 3)
+    elif x.dim() != 4:
+        raise ValueError(f"{name} must be [P, nH, S, d_kv] or [P, S, nH*d_kv] with n_heads=, got {tuple(x.shape)}")
+    if n_heads is not None and int(n_heads) != x.shape[1]:
+        raise ValueError(f"{name} has {x.shape[1]} heads, n_heads = {n_heads}")
+    return x
+
+
+def _group_strides(x):
+    """(tensor, element strides over (p, h, s)) of a [P, nH, S, d] view for trlx_t5_decode_attn_group:
+    read in place when d has unit stride and the base and the other strides are whole 16-byte
+    vectors, else copied once.  The stride of a dimension of size 1 is passed as 0."""
+    d, vec = x.shape[3], 16 // x.element_size()
+    st = [x.stride(i) if x.shape[i] > 1 else 0 for i in range(3)]
+    if x.stride(3) != 1 or x.data_ptr() % 16 or any(s < 0 or s % vec for s in st) or \
+            (x.shape[1] > 1 and st[1] < d) or (x.shape[2] > 1 and st[2] < d):
+        x = x.contiguous()
+        st = [x.stride(i) if x.shape[i] > 1 else 0 for i in range(3)]
+    return x, st
+
+
+def t5_decode_cross_attention_grouped(q, k_enc, v_enc, key_mask=None, live=None, n_heads=None):
+    """t5_decode_cross_attention for a rollout that draws G samples per prompt, over ONE copy of
+    each prompt's keys and values (trlx_t5_decode_attn_group).  Returns [P*G, nH*d_kv].
+
+    Row b = p * G + g of q, live and the result is sample g of prompt p: the order of
+    repeat_interleave(G, dim=0), which is how HF expands num_return_sequences.  Every row has the
+    bits of t5_decode_cross_attention(q, k_enc.repeat_interleave(G, 0).contiguous(), v_enc..., the
+    mask repeated likewise): per query the kernel executes that kernel's floating-point operations
+    in that kernel's order.  A key or value row is loaded once per (prompt, head, tile of queries)
+    instead of once per sample, so K / V bytes per token and K / V memory drop by G.
+
+    q: [P*G, nH*d_kv], [P*G, 1, nH*d_kv] or a row-strided view such as a slice of a fused projection,
+    read in place as in t5_decode_cross_attention.  k_enc, v_enc: [P, nH, S, d_kv] (contiguous or
+    HF's transposed view of the projection) or the projection output [P, S, nH*d_kv] with n_heads=;
+    both are read in place through their strides, no .contiguous() is needed.  G = q.shape[0] //
+    P; a batch that is not a whole multiple of P raises ValueError; G = 1 is the existing call.
+    key_mask: int64 [P, S], per prompt, 0 = masked, or None; masked rows are not read; a fully
+    masked prompt gives zeros in all its rows.  live: None or a contiguous int64 [P*G] tensor
+    (PPORolloutRecorder.unfinished as it is): a dead row gets zeros and its q is not read, a prompt
+    whose rows are all dead has none of its keys read, live rows keep the bits of the call without
+    `live`.  The launch takes the same arguments at every token and can be captured.
+    Tensors that are not on a ROCm device, another dtype or d_kv: whatever
+    t5_decode_cross_attention does for the repeat_interleave'd operands.
+    Runs on the current stream, no host sync; only the output is allocated."""
+    k, v = _group_kv(k_enc, "k_enc", n_heads), _group_kv(v_enc, "v_enc", n_heads)
+    if k.shape != v.shape or k.dtype != v.dtype or k.device != v.device:
+        raise ValueError(f"k_enc and v_enc differ: {tuple(k.shape)} {k.dtype} on {k.device}, {tuple(v.shape)} "
+                         f"{v.dtype} on {v.device}")
+    P, nH, S, d = k.shape
+    if min(P, nH, S) < 1:
+        raise ValueError(f"k_enc holds no key: shape {tuple(k.shape)}")
+    if not isinstance(q, torch.Tensor):
+        raise TypeError(f"expected a tensor, got {type(q).__name__}")
+    B = q.shape[0] if q.dim() else 0
+    if B < P or B % P:
+        raise ValueError(f"q has {B} rows, k_enc {P} prompts: the batch must be a whole multiple of the prompts "
+                         f"(row p * G + g is sample g of prompt p)")
+    G = B // P
+    _check_q(q, B, nH, d, k.dtype, k.device)
+    if key_mask is not None:
+        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (P, S) or key_mask.dtype != torch.int64 \
+                or key_mask.device != k.device:
+            raise ValueError(f"key_mask must be int64 [P, S] = [{P}, {S}] on {k.device}")
+    if live is not None:
+        _check_live(live, B, k.dtype, d, k.device)
+    if not k.is_cuda or not _kernel_takes(k.dtype, d):
+        return t5_decode_cross_attention(
+            q, k.repeat_interleave(G, 0).contiguous(), v.repeat_interleave(G, 0).contiguous(),
+            None if key_mask is None else key_mask.repeat_interleave(G, 0), live)
+    _lib.require_cuda(k, q)
+    if key_mask is not None and not key_mask.is_contiguous():
+        key_mask = key_mask.contiguous()
+    (k, k_st), (v, v_st) = _group_strides(k), _group_strides(v)
+    q2, ldq = _rows(q, "q", B, nH, d)
+    out = torch.empty(B, nH * d, dtype=k.dtype, device=k.device)
+    args = _lib.T5DecodeAttnGroupArgs(
+        q=q2.data_ptr(), ldq=ldq, k=k.data_ptr(), k_stride_p=k_st[0], k_stride_h=k_st[1], k_stride_s=k_st[2],
+        v=v.data_ptr(), v_stride_p=v_st[0], v_stride_h=v_st[1], v_stride_s=v_st[2], key_mask=_lib.ptr(key_mask),
+        live=_lib.ptr(live), out=out.data_ptr(), P=P, G=G, n_heads=nH, d_kv=d, S=S, dtype=_lib.dtype_code(k))
+    _lib.call("trlx_t5_decode_attn_group", ctypes.byref(args), _lib.stream_of(out))
+    return out
+
+
+def t5_decode_cross_attention_group_tile(tile=0):
+    """The largest query tile of t5_decode_cross_attention_grouped: 0 (the default, the measured
+    choice), 1, 2, 4 or 8.  Process-wide; the result does not depend on it.  For the benchmark tool."""
+    _lib.call("trlx_t5_decode_attn_group_tile", int(tile))
 
 
 EMBED_MAX_D = 8192   # the row tile of csrc/t5_rmsnorm.hip
