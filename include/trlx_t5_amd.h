@@ -1181,6 +1181,62 @@ int trlx_t5_decode_attn_group(const TrlxT5DecodeAttnGroupArgs* a, void* stream);
  * tool sets it to time each built tile. */
 int trlx_t5_decode_attn_group_tile(int64_t tile);
 
+/* ---------------------------------------------------------------- encoder keys split across workgroups
+ * trlx_t5_decode_attn_group with the S keys of a (row, head) cut into X ranges, each walked by a
+ * workgroup of its own: for the shapes where P * n_heads * tiles workgroups leave the chip
+ * under-filled (few rows, few live rows) or S is long.  Opt-in: no other entry calls it.  The
+ * arguments are trlx_t5_decode_attn_group's (G == 1 is the plain cross-attention) plus
+ *   splits    : 0 = the X trlx_t5_decode_attn_split_plan returns for the shape, or 1 ... 8.
+ *   workspace : device memory, 16-byte aligned, at least trlx_t5_decode_attn_split_workspace_bytes(
+ *               P * G, n_heads, d_kv, X) bytes for the X taken; fp32 states [P * G, n_heads, ranges,
+ *               d_kv + 2].  Scratch: nothing is kept in it between calls and it needs no
+ *               initialisation; two calls in flight on different streams need a workspace each.
+ * TWO launches in stream order, no atomics, no counters, no spinning:
+ *   k_t5_decode_attn_split_part, grid (P * n_heads, tiles, ranges): the grouped kernel restricted to
+ *     the keys [x * C, min(S, (x + 1) * C)), C = ceil(S / X) rounded up to a multiple of the
+ *     kernel's NG groups (so key j is walked by group j % NG as in the unsplit kernel); only the
+ *     ranges = ceil(S / C) non-empty ranges are launched.  Per live query it writes the
+ *     unnormalised fp32 state (M, L, o[d_kv]); M = -inf, L = 0 when the range held no live key.
+ *     A tile whose queries are all dead writes no state and forms no address into q, k, v or
+ *     key_mask; a masked key's K and V rows are not read.
+ *   k_t5_decode_attn_split_merge: M = max M_x; for every x with M_x != -inf, in split order,
+ *     w = expf(M_x - M), L = fmaf(L_x, w, L), o = fmaf(o_x, w, o); out = o / L, or zeros when no key
+ *     was live; one rounding.  A row with live[b] == 0 gets zeros and its states are not read.
+ * The result is bit-reproducible and depends on X and on nothing else: not on P, the strides or
+ * the query tile (trlx_t5_decode_attn_group_tile applies here as it does there).  X == 1 forwards to
+ * trlx_t5_decode_attn_group: its bits.  For X > 1 the bits differ from the unsplit call's (the
+ * groups are weighed against their range's maximum first), within the rounding of fp32 sums;
+ * with a key_mask that leaves live keys in one range only they are the unsplit call's.  The
+ * launches take the same arguments at every token: the call captures as it is.
+ * Refused with TRLX_ERR_ARG before any launch: everything trlx_t5_decode_attn_group refuses, a
+ * P * G * n_heads past 2^31 - 1, splits outside 0 ... 8, a workspace that is NULL, not 16-byte
+ * aligned or smaller than the X taken needs (X == 1 included). */
+int trlx_t5_decode_attn_split(const TrlxT5DecodeAttnGroupArgs* a, int64_t splits, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
+/* Bytes of workspace for `rows` = P * G rows at `splits` ranges: rows * n_heads * splits *
+ * (d_kv + 2) * 4.  0 for rows or n_heads < 1, a d_kv other than 64 / 128, splits outside 1 ... 8. */
+int64_t trlx_t5_decode_attn_split_workspace_bytes(int64_t rows, int64_t n_heads, int64_t d_kv, int64_t splits);
+
+/* The key ranges of trlx_t5_decode_attn_split for (dtype, d_kv, S) at `splits` (1 ... 8) ranges.  A host
+ * function, no device needed.  TRLX_ERR_ARG (and a zeroed *g) for a NULL g, a dtype / d_kv the
+ * kernels do not take, S < 1, splits outside 1 ... 8. */
+typedef struct TrlxT5DecodeAttnSplitGeometry {
+    int64_t NG;          /* groups of a workgroup: 32 / 16 / 16 / 8 for bf16-64 / bf16-128 / fp32-64 / fp32-128 */
+    int64_t C;           /* keys a range: ceil(S / splits) rounded up to a multiple of NG */
+    int64_t ranges;      /* non-empty ranges = ceil(S / C) <= splits: the grid's z and the states a (row, head) */
+    int64_t tile;        /* the largest query tile in force (trlx_t5_decode_attn_group_tile) */
+    int64_t max_splits;  /* 8 */
+} TrlxT5DecodeAttnSplitGeometry;
+int trlx_t5_decode_attn_split_geometry(int dtype, int64_t d_kv, int64_t S, int64_t splits,
+                                       TrlxT5DecodeAttnSplitGeometry* g);
+
+/* The X trlx_t5_decode_attn_split takes for splits == 0: a pure function of these arguments (it
+ * looks neither at live nor at the device, so a shape always gives the same bits), in 1 ... 8, set
+ * from measurements (profiles/t5_cross_split_bench.json).  1 for arguments the entry
+ * would refuse. */
+int trlx_t5_decode_attn_split_plan(int dtype, int64_t P, int64_t G, int64_t n_heads, int64_t d_kv, int64_t S);
+
 /* The decoder's input row of decode step t, ONE launch — replaces, per generated token, the
  * gather of the token drawn at step t - 1, the `shared` embedding lookup (T5 applies no scale)
  * and layer 0's first T5LayerNorm.  clock == NULL: t is a->t; otherwise t and the capacity are

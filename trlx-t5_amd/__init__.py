@@ -56,6 +56,9 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
       per prompt (num_return_sequences, RLOO / GRPO groups) over one copy of each prompt's keys and
       values: K / V bytes per token and K / V memory divided by G, every row bit-identical to
       t5_decode_cross_attention on the expanded tensors
+  t5_decode_cross_attention_split (+ _split_plan, _split_geometry) — opt-in: the same call with the
+      encoder keys of a (row, head) cut into ranges walked by workgroups of their own and merged by
+      a second launch, for few rows, few live rows or long prompts; the plan is set from measurements
   t5_attention, t5_relative_bias_offsets — T5's attention over whole sequences (encoder
       self-attention, teacher-forced decoder self- and cross-attention) as one flash-attention
       launch on MFMA: bias, key mask and causal rule inside, no [Tq, S] tensor
@@ -102,7 +105,9 @@ from .value_head import ValueHead, value_head, value_head_splits
 from .value_head import make_head as make_value_head
 from .sampling import PPOLogitsProcessors, ppo_sample_step
 from .t5_decode import (T5CrossKV8, T5DecodeClock, T5DecodeKVCache, t5_decode_cross_attention,
-                        t5_decode_cross_attention_grouped, t5_decode_cross_attention_kv8, t5_decode_embed,
+                        t5_decode_cross_attention_grouped, t5_decode_cross_attention_kv8,
+                        t5_decode_cross_attention_split, t5_decode_cross_attention_split_geometry,
+                        t5_decode_cross_attention_split_plan, t5_decode_embed,
                         t5_decode_self_attention, t5_quantize_cross_kv, t5_relative_bias_table)
 from .t5_attention import t5_attention, t5_attention_train, t5_relative_bias_buckets, t5_relative_bias_offsets
 from .t5_ff import T5FeedForward, t5_ff_act, t5_ff_act_packed
@@ -127,7 +132,8 @@ __all__ = [
     "FusedAdamW", "adamw_step", "clip_grad_norm_", "schedule_table",
     "T5DecodeKVCache", "T5DecodeClock", "t5_decode_self_attention", "t5_decode_cross_attention", "t5_relative_bias_table",
     "t5_decode_embed", "T5CrossKV8", "t5_quantize_cross_kv", "t5_decode_cross_attention_kv8",
-    "t5_decode_cross_attention_grouped",
+    "t5_decode_cross_attention_grouped", "t5_decode_cross_attention_split", "t5_decode_cross_attention_split_plan",
+    "t5_decode_cross_attention_split_geometry",
     "t5_attention", "t5_relative_bias_offsets", "t5_attention_train", "t5_relative_bias_buckets",
     "t5_ff_act", "t5_ff_act_packed", "T5FeedForward",
     "t5_rmsnorm", "t5_add_rmsnorm", "T5LayerNorm",

@@ -123,6 +123,11 @@ class T5DecodeAttnGroupArgs(ctypes.Structure):
     ]
 
 
+class T5DecodeAttnSplitGeometry(ctypes.Structure):
+    """Mirror of TrlxT5DecodeAttnSplitGeometry (include/trlx_t5_amd.h)."""
+    _fields_ = [("NG", _c_i64), ("C", _c_i64), ("ranges", _c_i64), ("tile", _c_i64), ("max_splits", _c_i64)]
+
+
 class T5DecodeEmbedArgs(ctypes.Structure):
     """Mirror of TrlxT5DecodeEmbedArgs (include/trlx_t5_amd.h)."""
     _fields_ = [
@@ -409,6 +414,11 @@ SIGNATURES = {
     "trlx_t5_decode_attn_kv8": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp, _c_vp, _c_vp, _c_vp]),
     "trlx_t5_decode_attn_group": (_c_int, [ctypes.POINTER(T5DecodeAttnGroupArgs), _c_vp]),
     "trlx_t5_decode_attn_group_tile": (_c_int, [_c_i64]),
+    "trlx_t5_decode_attn_split": (_c_int, [ctypes.POINTER(T5DecodeAttnGroupArgs), _c_i64, _c_vp, _c_i64, _c_vp]),
+    "trlx_t5_decode_attn_split_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    "trlx_t5_decode_attn_split_geometry": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64,
+                                                    ctypes.POINTER(T5DecodeAttnSplitGeometry)]),
+    "trlx_t5_decode_attn_split_plan": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64]),
     "trlx_t5_decode_embed": (_c_int, [ctypes.POINTER(T5DecodeEmbedArgs), _c_vp, _c_vp]),
     "trlx_t5_attention": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp]),
     "trlx_t5_attention_tiles": (_c_int, [ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),

@@ -243,6 +243,9 @@ static t5_group_kernel_t t5_group_pick(int dtype, int64_t d_kv, int gt, bool mas
 constexpr int kT5GDefaultTile = 4;
 static TuneKnob g_group_tile = {0};   // 0: kT5GDefaultTile
 
+// host only: the cap in force, for trlx_t5_decode_attn_split (t5_decode_attn_split.hip), which tiles as this entry does
+int t5_group_tile_cap() { return g_group_tile ? int(g_group_tile) : kT5GDefaultTile; }
+
 }  // namespace trlx
 
 using namespace trlx;

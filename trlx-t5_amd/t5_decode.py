@@ -588,6 +588,110 @@ def t5_decode_cross_attention_group_tile(tile=0):
     _lib.call("trlx_t5_decode_attn_group_tile", int(tile))
 
 
+# ------------------------------------------------------------------ keys split across workgroups
+SPLIT_MAX = 8            # the largest `splits` trlx_t5_decode_attn_split takes
+_SPLIT_WORKSPACES = {}   # (device, bytes) -> uint8 tensor, allocated on first use and reused
+
+
+def t5_decode_cross_attention_split_geometry(dtype, d_kv, S, splits):
+    """trlx_t5_decode_attn_split_geometry as a dict (needs no device): NG groups of a workgroup, C
+    keys a range (ceil(S / splits) rounded up to a multiple of NG), `ranges` = ceil(S / C) non-empty
+    ranges, the query tile cap in force and max_splits."""
+    code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}.get(dtype, -1)
+    g = _lib.T5DecodeAttnSplitGeometry()
+    _lib.call("trlx_t5_decode_attn_split_geometry", code, int(d_kv), int(S), int(splits), ctypes.byref(g))
+    return {k: int(getattr(g, k)) for k, _ in g._fields_}
+
+
+def t5_decode_cross_attention_split_plan(dtype, P, G, n_heads, d_kv, S):
+    """The `splits` t5_decode_cross_attention_split takes by default for a shape
+    (trlx_t5_decode_attn_split_plan): a pure function of the arguments, in 1 ... SPLIT_MAX, set from
+    measurements; 1 for a dtype or d_kv the kernels do not take.  Needs no device."""
+    code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}.get(dtype, -1)
+    return int(_lib.query("trlx_t5_decode_attn_split_plan", code, int(P), int(G), int(n_heads), int(d_kv), int(S)))
+
+
+def t5_decode_cross_attention_split_workspace_bytes(rows, n_heads, d_kv, splits):
+    """trlx_t5_decode_attn_split_workspace_bytes: rows * n_heads * splits * (d_kv + 2) * 4."""
+    return int(_lib.query("trlx_t5_decode_attn_split_workspace_bytes", int(rows), int(n_heads), int(d_kv), int(splits)))
+
+
+def _split_workspace(device, nbytes):
+    key = (device, nbytes)
+    ws = _SPLIT_WORKSPACES.get(key)
+    if ws is None:
+        ws = _SPLIT_WORKSPACES[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def t5_decode_cross_attention_split(q, k_enc, v_enc, key_mask=None, live=None, n_heads=None, groups=1, splits=None,
+                                    workspace=None):
+    """t5_decode_cross_attention_grouped with the S keys of every (row, head) cut into `splits`
+    ranges, each walked by a workgroup of its own (trlx_t5_decode_attn_split): two launches, a partial
+    pass that writes unnormalised fp32 states to a workspace and a merge.  For the shapes where the
+    one-workgroup-per-(prompt, head, tile) grid leaves the chip under-filled.  Returns [P*G, nH*d_kv].
+
+    q, k_enc, v_enc, key_mask, live, n_heads: as in t5_decode_cross_attention_grouped, with the same
+    checks and the same in-place reading through strides.  groups: G, the samples a prompt; k_enc
+    holds P = q.shape[0] // groups prompts and row p * G + g is sample g of prompt p.  groups=1 is
+    the plain cross-attention.  splits: None = t5_decode_cross_attention_split_plan for the shape, or
+    1 ... SPLIT_MAX; 1 is the grouped call, bit for bit.  For splits > 1 the result is
+    bit-reproducible and depends on `splits` alone (not on P, the layout or the query tile), but is
+    not the grouped call's bits: the merge order differs.
+    workspace: None, or a contiguous tensor on the device of at least
+    t5_decode_cross_attention_split_workspace_bytes(P*G, nH, d_kv, splits) bytes, 16-byte aligned.
+    With None one is allocated on first use per (device, size) and reused by every later call, so
+    nothing but the output is allocated per call and the call can be captured (call it once outside
+    the capture first); calls that may run concurrently on different streams must pass workspaces
+    of their own.  Tensors that are not on a ROCm device, another dtype or d_kv: what
+    t5_decode_cross_attention_grouped does.  Runs on the current stream, no host sync."""
+    k, v = _group_kv(k_enc, "k_enc", n_heads), _group_kv(v_enc, "v_enc", n_heads)
+    if k.shape != v.shape or k.dtype != v.dtype or k.device != v.device:
+        raise ValueError(f"k_enc and v_enc differ: {tuple(k.shape)} {k.dtype} on {k.device}, {tuple(v.shape)} "
+                         f"{v.dtype} on {v.device}")
+    P, nH, S, d = k.shape
+    if min(P, nH, S) < 1:
+        raise ValueError(f"k_enc holds no key: shape {tuple(k.shape)}")
+    if not isinstance(q, torch.Tensor):
+        raise TypeError(f"expected a tensor, got {type(q).__name__}")
+    G = int(groups)
+    B = q.shape[0] if q.dim() else 0
+    if G < 1 or B != P * G:
+        raise ValueError(f"q has {B} rows, k_enc {P} prompts, groups = {groups}: the batch must be prompts * groups "
+                         f"(row p * G + g is sample g of prompt p)")
+    if splits is not None and not 1 <= int(splits) <= SPLIT_MAX:
+        raise ValueError(f"splits = {splits}: None (the plan) or 1 ... {SPLIT_MAX}")
+    _check_q(q, B, nH, d, k.dtype, k.device)
+    if key_mask is not None:
+        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (P, S) or key_mask.dtype != torch.int64 \
+                or key_mask.device != k.device:
+            raise ValueError(f"key_mask must be int64 [P, S] = [{P}, {S}] on {k.device}")
+    if live is not None:
+        _check_live(live, B, k.dtype, d, k.device)
+    if not k.is_cuda or not _kernel_takes(k.dtype, d):
+        return t5_decode_cross_attention_grouped(q, k_enc, v_enc, key_mask, live, n_heads)
+    _lib.require_cuda(k, q)
+    X = int(splits) if splits is not None else t5_decode_cross_attention_split_plan(k.dtype, P, G, nH, d, S)
+    need = t5_decode_cross_attention_split_workspace_bytes(B, nH, d, X)
+    if workspace is None:
+        workspace = _split_workspace(k.device, need)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != k.device or not workspace.is_contiguous() \
+            or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {k.device}")
+    if key_mask is not None and not key_mask.is_contiguous():
+        key_mask = key_mask.contiguous()
+    (k, k_st), (v, v_st) = _group_strides(k), _group_strides(v)
+    q2, ldq = _rows(q, "q", B, nH, d)
+    out = torch.empty(B, nH * d, dtype=k.dtype, device=k.device)
+    args = _lib.T5DecodeAttnGroupArgs(
+        q=q2.data_ptr(), ldq=ldq, k=k.data_ptr(), k_stride_p=k_st[0], k_stride_h=k_st[1], k_stride_s=k_st[2],
+        v=v.data_ptr(), v_stride_p=v_st[0], v_stride_h=v_st[1], v_stride_s=v_st[2], key_mask=_lib.ptr(key_mask),
+        live=_lib.ptr(live), out=out.data_ptr(), P=P, G=G, n_heads=nH, d_kv=d, S=S, dtype=_lib.dtype_code(k))
+    _lib.call("trlx_t5_decode_attn_split", ctypes.byref(args), X, workspace.data_ptr(),
+              workspace.numel() * workspace.element_size(), _lib.stream_of(out))
+    return out
+
+
 EMBED_MAX_D = 8192   # the row tile of csrc/t5_rmsnorm.hip
 
 
