@@ -10,9 +10,17 @@ import __graft_entry__  # noqa: E402
 
 __graft_entry__.load_package()
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from trlx_t5_amd.modeling import _allreduce_moments, moments_to_mean_var  # noqa: E402
+
+
+def as_tensors(d):
+    """The parent's view of a worker's result.  Workers put numpy arrays on the queue (pickled
+    by value): a torch CPU tensor travels as a shared-memory fd that the parent fetches from
+    the worker when it unpickles, which fails once the worker has exited."""
+    return {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in d.items()}
 
 
 def whiten_stats_worker(rank, world, port, xs, q):
@@ -51,9 +59,10 @@ def hot_path_step_worker(rank, world, port, inputs, q, loss_norm="rank", mode="s
         loss, stats, dlogits, dvalues = hp.step(*args, lengths=sh["lengths"], mask=sh["mask"])
     hp.wait_stats()
     torch.cuda.synchronize()
-    q.put((rank, {"lp": hp.lp_old.cpu(), "rewards": hp.rewards.cpu(), "adv_stats": hp.adv_stats.cpu(),
-                  "loss": loss.cpu(), "dlogits": dlogits.float().cpu(), "dvalues": dvalues.cpu(),
-                  "stats": stats.cpu(), "returns": hp.returns.cpu(), "adv_raw": hp.adv_raw.cpu()}))
+    out = {"lp": hp.lp_old, "rewards": hp.rewards, "adv_stats": hp.adv_stats, "loss": loss,
+           "dlogits": dlogits.float(), "dvalues": dvalues, "stats": stats, "returns": hp.returns,
+           "adv_raw": hp.adv_raw}
+    q.put((rank, {k: v.cpu().numpy() for k, v in out.items()}))  # by value: see as_tensors
     dist.barrier()
     dist.destroy_process_group()
 
@@ -77,7 +86,7 @@ def ctl_step_worker(rank, world, port, inputs, scores_seq, scale, q):
         hp.step(sh["logits"], sh["ref_logits"], sh["new_logits"], sh["labels"], sh["old_values"], sh["values"],
                 s.chunk(world)[rank].contiguous().to(dev))
         torch.cuda.synchronize()
-        out.append({"rewards": hp.rewards.cpu(), "state": ctl.host(), "approx_kl": float(hp.stats[8])})
+        out.append({"rewards": hp.rewards.cpu().numpy(), "state": ctl.host(), "approx_kl": float(hp.stats[8])})
     q.put((rank, out))
     dist.barrier()
     dist.destroy_process_group()

@@ -64,7 +64,7 @@ def test_dp2_step_global_whitening(lengths, mode):
     var = ((adv.double() - mu) ** 2).mean()
     advw = ((adv.double() - mu) * torch.rsqrt(var + 1e-8)).float()
     for r in range(world):
-        got = res[r]
+        got = dist_workers.as_tensors(res[r])
         rows = slice(r * B // world, (r + 1) * B // world)
         torch.testing.assert_close(got["lp"], lp[rows], rtol=1e-5, atol=1e-5)
         torch.testing.assert_close(got["rewards"], rewards[rows], rtol=1e-5, atol=1e-5)
@@ -123,7 +123,7 @@ def test_dp2_device_state(scale):
             sr = sr / (running.std if scale == "running" else ref_std[r])
             sr = torch.clip(sr, -10, 10)
             want = orc.kl_penalty_rewards(lp[rows], ref_lp[rows], betas[r], sr)
-            got = res[r][i]
+            got = dist_workers.as_tensors(res[r][i])
             torch.testing.assert_close(got["rewards"], want, rtol=1e-5, atol=1e-5)
             assert got["state"]["std"] == pytest.approx(float(running.std), rel=1e-5)
             assert got["state"]["count"] == pytest.approx(float(running.count), rel=1e-12)
@@ -171,6 +171,7 @@ def test_dp2_step_global_loss_norm():
     new_lp = orc.logprobs_from_logits(xg, x["labels"])
     loss, _ = orc.ppo_loss(new_lp, vg, lp, x["old_values"], advw, ret, m)
     loss.backward()
+    res = {r: dist_workers.as_tensors(res[r]) for r in range(world)}
     for r in range(world):
         got = res[r]
         rows = slice(r * B // world, (r + 1) * B // world)

@@ -129,6 +129,7 @@ def test_dp2_record_large_offset(off):
     for p in ps:
         p.join(timeout=60)
         assert p.exitcode == 0
+    res = {r: dist_workers.as_tensors(res[r]) for r in range(world)}
     a = torch.cat([res[r]["adv_raw"] for r in range(world)]).double()
     n = a.numel()
     m2 = float(((a - a.mean()) ** 2).sum())
