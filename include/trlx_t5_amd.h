@@ -1181,6 +1181,29 @@ int trlx_t5_decode_attn_group(const TrlxT5DecodeAttnGroupArgs* a, void* stream);
  * tool sets it to time each built tile. */
 int trlx_t5_decode_attn_group_tile(int64_t tile);
 
+/* ---------------------------------------------------------------- a prompt's samples as an MFMA tile
+ * trlx_t5_decode_attn_group on matrix instructions, opt-in, for groups of 8 to 64 samples: the
+ * argument block and its meaning are that entry's (row p * G + g is sample g of prompt p, k / v read
+ * in place through the (p, h, s) strides, key_mask per prompt, live per row, out contiguous), bf16
+ * only.  ONE launch, grid (P * n_heads, ceil(G / 16)), no atomics, no workspace: a workgroup takes a
+ * (prompt, head, tile of 16 queries) and its W waves walk the 32-key blocks w, w + W, ... each on
+ * its own — scores as K·Q^T and P·V as V^T·P^T on v_mfma_f32_16x16x32_bf16, fp32 online softmax,
+ * P rounded to bf16 un-normalised, the waves' states merged in wave order, one rounding of the
+ * result.  Each key and value row is read once per 16 samples and the per-key arithmetic does not
+ * grow with G.  Masked keys, a fully masked prompt, dead rows and dead tiles behave as in
+ * trlx_t5_decode_attn_group (not read; zeros).
+ * The result is NOT bit-equal to trlx_t5_decode_attn_group (P is rounded to bf16, the sums run in
+ * another order); it is bit-reproducible, and a row's bits depend only on its own q, the prompt's
+ * keys, values and mask, and S: not on G, the row's place in its tile, P, the strides or the other
+ * rows' live words.  The launch takes the same arguments at every token: it captures as it is.
+ * Refused with TRLX_ERR_ARG before any launch: everything trlx_t5_decode_attn_group refuses, and
+ * TRLX_F32. */
+int trlx_t5_decode_attn_group_mma(const TrlxT5DecodeAttnGroupArgs* a, void* stream);
+
+/* W, the waves of a workgroup of trlx_t5_decode_attn_group_mma at this d_kv (a round of all waves is
+ * 32 * W keys); 0 for a d_kv the entry does not take.  Needs no device. */
+int trlx_t5_decode_attn_group_mma_waves(int64_t d_kv);
+
 /* ---------------------------------------------------------------- encoder keys split across workgroups
  * trlx_t5_decode_attn_group with the S keys of a (row, head) cut into X ranges, each walked by a
  * workgroup of its own: for the shapes where P * n_heads * tiles workgroups leave the chip

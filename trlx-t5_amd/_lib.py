@@ -414,6 +414,8 @@ SIGNATURES = {
     "trlx_t5_decode_attn_kv8": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp, _c_vp, _c_vp, _c_vp]),
     "trlx_t5_decode_attn_group": (_c_int, [ctypes.POINTER(T5DecodeAttnGroupArgs), _c_vp]),
     "trlx_t5_decode_attn_group_tile": (_c_int, [_c_i64]),
+    "trlx_t5_decode_attn_group_mma": (_c_int, [ctypes.POINTER(T5DecodeAttnGroupArgs), _c_vp]),
+    "trlx_t5_decode_attn_group_mma_waves": (_c_int, [_c_i64]),
     "trlx_t5_decode_attn_split": (_c_int, [ctypes.POINTER(T5DecodeAttnGroupArgs), _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_t5_decode_attn_split_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
     "trlx_t5_decode_attn_split_geometry": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64,

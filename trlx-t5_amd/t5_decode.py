@@ -519,6 +519,49 @@ def _group_strides(x):
     return x, st
 
 
+def _group_launch(entry, q, k, v, key_mask, live, dims):
+    """One launch of a grouped entry (trlx_t5_decode_attn_group or _group_mma) on checked operands."""
+    P, nH, S, d, B, G = dims
+    _lib.require_cuda(k, q)
+    if key_mask is not None and not key_mask.is_contiguous():
+        key_mask = key_mask.contiguous()
+    (k, k_st), (v, v_st) = _group_strides(k), _group_strides(v)
+    q2, ldq = _rows(q, "q", B, nH, d)
+    out = torch.empty(B, nH * d, dtype=k.dtype, device=k.device)
+    args = _lib.T5DecodeAttnGroupArgs(
+        q=q2.data_ptr(), ldq=ldq, k=k.data_ptr(), k_stride_p=k_st[0], k_stride_h=k_st[1], k_stride_s=k_st[2],
+        v=v.data_ptr(), v_stride_p=v_st[0], v_stride_h=v_st[1], v_stride_s=v_st[2], key_mask=_lib.ptr(key_mask),
+        live=_lib.ptr(live), out=out.data_ptr(), P=P, G=G, n_heads=nH, d_kv=d, S=S, dtype=_lib.dtype_code(k))
+    _lib.call(entry, ctypes.byref(args), _lib.stream_of(out))
+    return out
+
+
+def _group_checked(q, k_enc, v_enc, key_mask, live, n_heads):
+    """The operand checks the grouped calls share: (k, v) as [P, nH, S, d] views and (P, nH, S, d, B, G)."""
+    k, v = _group_kv(k_enc, "k_enc", n_heads), _group_kv(v_enc, "v_enc", n_heads)
+    if k.shape != v.shape or k.dtype != v.dtype or k.device != v.device:
+        raise ValueError(f"k_enc and v_enc differ: {tuple(k.shape)} {k.dtype} on {k.device}, {tuple(v.shape)} "
+                         f"{v.dtype} on {v.device}")
+    P, nH, S, d = k.shape
+    if min(P, nH, S) < 1:
+        raise ValueError(f"k_enc holds no key: shape {tuple(k.shape)}")
+    if not isinstance(q, torch.Tensor):
+        raise TypeError(f"expected a tensor, got {type(q).__name__}")
+    B = q.shape[0] if q.dim() else 0
+    if B < P or B % P:
+        raise ValueError(f"q has {B} rows, k_enc {P} prompts: the batch must be a whole multiple of the prompts "
+                         f"(row p * G + g is sample g of prompt p)")
+    G = B // P
+    _check_q(q, B, nH, d, k.dtype, k.device)
+    if key_mask is not None:
+        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (P, S) or key_mask.dtype != torch.int64 \
+                or key_mask.device != k.device:
+            raise ValueError(f"key_mask must be int64 [P, S] = [{P}, {S}] on {k.device}")
+    if live is not None:
+        _check_live(live, B, k.dtype, d, k.device)
+    return k, v, (P, nH, S, d, B, G)
+
+
 def t5_decode_cross_attention_grouped(q, k_enc, v_enc, key_mask=None, live=None, n_heads=None):
     """t5_decode_cross_attention for a rollout that draws G samples per prompt, over ONE copy of
     each prompt's keys and values (trlx_t5_decode_attn_group).  Returns [P*G, nH*d_kv].
@@ -543,43 +586,39 @@ def t5_decode_cross_attention_grouped(q, k_enc, v_enc, key_mask=None, live=None,
     Tensors that are not on a ROCm device, another dtype or d_kv: whatever
     t5_decode_cross_attention does for the repeat_interleave'd operands.
     Runs on the current stream, no host sync; only the output is allocated."""
-    k, v = _group_kv(k_enc, "k_enc", n_heads), _group_kv(v_enc, "v_enc", n_heads)
-    if k.shape != v.shape or k.dtype != v.dtype or k.device != v.device:
-        raise ValueError(f"k_enc and v_enc differ: {tuple(k.shape)} {k.dtype} on {k.device}, {tuple(v.shape)} "
-                         f"{v.dtype} on {v.device}")
-    P, nH, S, d = k.shape
-    if min(P, nH, S) < 1:
-        raise ValueError(f"k_enc holds no key: shape {tuple(k.shape)}")
-    if not isinstance(q, torch.Tensor):
-        raise TypeError(f"expected a tensor, got {type(q).__name__}")
-    B = q.shape[0] if q.dim() else 0
-    if B < P or B % P:
-        raise ValueError(f"q has {B} rows, k_enc {P} prompts: the batch must be a whole multiple of the prompts "
-                         f"(row p * G + g is sample g of prompt p)")
-    G = B // P
-    _check_q(q, B, nH, d, k.dtype, k.device)
-    if key_mask is not None:
-        if not isinstance(key_mask, torch.Tensor) or tuple(key_mask.shape) != (P, S) or key_mask.dtype != torch.int64 \
-                or key_mask.device != k.device:
-            raise ValueError(f"key_mask must be int64 [P, S] = [{P}, {S}] on {k.device}")
-    if live is not None:
-        _check_live(live, B, k.dtype, d, k.device)
+    k, v, (P, nH, S, d, B, G) = _group_checked(q, k_enc, v_enc, key_mask, live, n_heads)
     if not k.is_cuda or not _kernel_takes(k.dtype, d):
         return t5_decode_cross_attention(
             q, k.repeat_interleave(G, 0).contiguous(), v.repeat_interleave(G, 0).contiguous(),
             None if key_mask is None else key_mask.repeat_interleave(G, 0), live)
-    _lib.require_cuda(k, q)
-    if key_mask is not None and not key_mask.is_contiguous():
-        key_mask = key_mask.contiguous()
-    (k, k_st), (v, v_st) = _group_strides(k), _group_strides(v)
-    q2, ldq = _rows(q, "q", B, nH, d)
-    out = torch.empty(B, nH * d, dtype=k.dtype, device=k.device)
-    args = _lib.T5DecodeAttnGroupArgs(
-        q=q2.data_ptr(), ldq=ldq, k=k.data_ptr(), k_stride_p=k_st[0], k_stride_h=k_st[1], k_stride_s=k_st[2],
-        v=v.data_ptr(), v_stride_p=v_st[0], v_stride_h=v_st[1], v_stride_s=v_st[2], key_mask=_lib.ptr(key_mask),
-        live=_lib.ptr(live), out=out.data_ptr(), P=P, G=G, n_heads=nH, d_kv=d, S=S, dtype=_lib.dtype_code(k))
-    _lib.call("trlx_t5_decode_attn_group", ctypes.byref(args), _lib.stream_of(out))
-    return out
+    return _group_launch("trlx_t5_decode_attn_group", q, k, v, key_mask, live, (P, nH, S, d, B, G))
+
+
+def t5_decode_cross_attention_grouped_mma(q, k_enc, v_enc, key_mask=None, live=None, n_heads=None):
+    """t5_decode_cross_attention_grouped on matrix instructions (trlx_t5_decode_attn_group_mma), opt-in,
+    for groups of 8 to 64 samples per prompt.  Same operands, same checks, same in-place reading of
+    q, k_enc and v_enc, same meaning of key_mask and live; returns [P*G, nH*d_kv].
+
+    A workgroup takes 16 of a prompt's samples as the columns of an MFMA tile: a key or value row is
+    read once per 16 samples and the arithmetic per key does not grow with G.  The result is not
+    bit-equal to the grouped call (the softmax weights are rounded to bf16 before P·V, as in
+    t5_attention, and the sums run in another order); against the float64 result its error is within
+    2 * torch's eager bf16 error + one bf16 ulp.  It is bit-reproducible, and a row's bits depend only on
+    its own q, the prompt's keys, values and mask, and S: not on G, the row's place in the group,
+    the other rows' `live`, P or the strides, so a rollout stays reproducible as rows finish.
+    bf16 with d_kv 64 or 128 on a ROCm device; anything else (fp32, another d_kv, CPU tensors) goes
+    to t5_decode_cross_attention_grouped.  One launch, same arguments at every token: capturable.
+    Runs on the current stream, no host sync; only the output is allocated."""
+    k, v, dims = _group_checked(q, k_enc, v_enc, key_mask, live, n_heads)
+    if not k.is_cuda or k.dtype != torch.bfloat16 or not _kernel_takes(k.dtype, dims[3]):
+        return t5_decode_cross_attention_grouped(q, k_enc, v_enc, key_mask, live, n_heads)
+    return _group_launch("trlx_t5_decode_attn_group_mma", q, k, v, key_mask, live, dims)
+
+
+def t5_decode_cross_attention_grouped_mma_waves(d_kv):
+    """W, the waves per workgroup of t5_decode_cross_attention_grouped_mma at this d_kv: a round of all
+    waves covers 32 * W keys.  0 for a d_kv the kernel does not take.  Needs no device."""
+    return int(_lib.query("trlx_t5_decode_attn_group_mma_waves", int(d_kv)))
 
 
 def t5_decode_cross_attention_group_tile(tile=0):
