@@ -982,7 +982,7 @@ int trlx_ppo_sample_proc_dev(const TrlxPpoSampleProcArgs* a, const TrlxPpoSample
  * finfo.min gives the plain average of the values there).  Fixed summation order: the result is
  * bit-reproducible and does not depend on B or on the strides.
  * Refused with TRLX_ERR_ARG before any launch: a dtype other than TRLX_F32 / TRLX_BF16, a d_kv
- * other than 64 / 128, a NULL q / k / v / out (self: k_new / v_new), t outside [0, max_len), a row
+ * other than 64 / 128 / 256, a NULL q / k / v / out (self: k_new / v_new), t outside [0, max_len), a row
  * stride below n_heads * d_kv or not a whole number of 16-byte vectors, a q / k_new / v_new / k / v
  * / out that is not 16-byte aligned, a pointer of the other mode that is not NULL, B, n_heads or
  * max_len < 1. */
@@ -1002,7 +1002,7 @@ typedef struct TrlxT5DecodeAttnArgs {
     void* out;                        /* [B, n_heads * d_kv] */
     int64_t B;
     int64_t n_heads;
-    int64_t d_kv;                     /* 64 or 128 */
+    int64_t d_kv;                     /* 64, 128 or 256 */
     int64_t max_len;                  /* self: cache columns; cross: S */
     int64_t t;                        /* self: the column of the new token, kv_len = t + 1 */
     int dtype;                        /* TRLX_F32 / TRLX_BF16: q, k_new, v_new, k, v, out */
@@ -1309,7 +1309,8 @@ int trlx_t5_decode_embed(const TrlxT5DecodeEmbedArgs* a, const int64_t* clock, v
  * T5Attention between the q / k / v projections and the `o` projection (a [B, nH, Tq, S] matmul,
  * compute_bias, the additive mask, an fp32 softmax cast back, a second matmul) with ONE launch
  * that never holds a [Tq, S] tensor: a flash-attention forward on gfx950 MFMA, one workgroup per
- * (batch row, head, block of query rows).  bf16 only, d_kv 64 or 128.
+ * (batch row, head, block of query rows).  bf16 only, d_kv 64, 128 or 256 (256: its own kernel,
+ * csrc/t5_attention_d256.hip, one wave per SIMD; the same semantics).
  *   score[i, j] = q_i · k_j + bias_by_offset[h, (j - i) + (Tq - 1)]        (no 1/sqrt(d) scaling)
  *   out[b, i, h, :] = sum_j softmax_j(score[i, :]) * v_j   over the keys j that are not excluded
  *   q        : [B, Tq, n_heads, d_kv] as a base pointer + element strides for batch, position and
@@ -1333,12 +1334,13 @@ int trlx_t5_decode_embed(const TrlxT5DecodeEmbedArgs* a, const int64_t* clock, v
  * summation order depends on (d_kv, Tq, S, the flags, the mask row) only: the result is
  * bit-reproducible and does not depend on B or on the strides.
  * Refused with TRLX_ERR_ARG before any launch, `out` untouched: a dtype other than TRLX_BF16, a
- * d_kv other than 64 / 128, a NULL q / k / v / out, a base that is not 16-byte aligned, a stride
+ * d_kv other than 64 / 128 / 256, a NULL q / k / v / out, a base that is not 16-byte aligned, a stride
  * that is negative or no multiple of 8 elements, a position or head stride below d_kv, out rows
  * that overlap, causal with Tq != S, B, n_heads, Tq or S outside [1, 2^30], more than 2^31 - 1
  * workgroups, an operand whose last element lies beyond 2^61 elements from its base.
- * trlx_t5_attention_tiles reports the kernel's tile sizes (query rows per workgroup, keys per
- * LDS tile); either pointer may be NULL. */
+ * trlx_t5_attention_tiles reports the d_kv 64 / 128 kernel's tile sizes (query rows per workgroup,
+ * keys per LDS tile); either pointer may be NULL.  trlx_t5_attention_tiles_d reports those of the
+ * kernel that serves `d_kv` (64, 128, 256; TRLX_ERR_ARG otherwise).  Neither needs a device. */
 typedef struct TrlxT5AttentionArgs {
     const void* q;
     int64_t q_stride_b, q_stride_t, q_stride_h;
@@ -1352,7 +1354,7 @@ typedef struct TrlxT5AttentionArgs {
     const int64_t* key_mask;          /* [B, S] int64, 0 = excluded, or NULL */
     int64_t B;
     int64_t n_heads;
-    int64_t d_kv;                     /* 64 or 128 */
+    int64_t d_kv;                     /* 64, 128 or 256 */
     int64_t Tq;
     int64_t S;
     int dtype;                        /* TRLX_BF16 */
@@ -1360,10 +1362,11 @@ typedef struct TrlxT5AttentionArgs {
 } TrlxT5AttentionArgs;
 int trlx_t5_attention(const TrlxT5AttentionArgs* a, void* stream);
 int trlx_t5_attention_tiles(int* q_tile, int* kv_tile);
+int trlx_t5_attention_tiles_d(int64_t d_kv, int* q_tile, int* kv_tile);
 
 /* The same launch, keeping the row statistics the backward needs.  `out` is bit-identical to
  * trlx_t5_attention's on the same arguments (the same kernel, one more store per query), and the
- * refusals are the same, plus a NULL or misaligned `lse`.
+ * refusals are the same, plus a NULL or misaligned `lse` and d_kv 256 (no backward takes it yet).
  *   lse : fp32 [B, n_heads, Tq], contiguous.  lse[b, h, i] = m_i + log(l_i) (natural log), m_i the
  *         largest live score of query i and l_i = sum_j exp(score[i, j] - m_i) over its live keys,
  *         so that exp(score[i, j] - lse) is the softmax weight.  A query with no live key gets +inf:

@@ -12,7 +12,9 @@ inside 5 % is reported as "tie".  FLOPs: 4·nH·d·sum_b Tq·S_live(b) (causal: 
 Byte model of the fused call: q and out once, K and V once per query block of Q_TILE rows (live
 keys only), the mask row once per workgroup, the bias window per tile.  One JSON record is printed
 and written to --out.
-GPU-box tool:  python tools/t5_attention_bench.py [--reps N] [--out FILE] [--only NAME]"""
+--set d256: the UL2-like shapes (nH 16, d_kv 256: k_t5_attention_d256, its tiles from tiles(256))
+in place of the nine above; each route's min-max stands beside its median.
+GPU-box tool:  python tools/t5_attention_bench.py [--reps N] [--out FILE] [--only NAME] [--set d256]"""
 import argparse
 import json
 import os
@@ -41,6 +43,15 @@ SHAPES = {
     "nH32_d128_enc_B32_S512": ("encoder", 32, 32, 128, 512, 512, False),
     "nH32_d128_enc_B32_S512_leftpad": ("encoder", 32, 32, 128, 512, 512, True),
 }
+# UL2-like (nH 16, d_kv 256), sized to fit
+SHAPES_D256 = {
+    "ul2_enc_B16_S512": ("encoder", 16, 16, 256, 512, 512, False),
+    "ul2_enc_B16_S512_leftpad": ("encoder", 16, 16, 256, 512, 512, True),
+    "ul2_enc_B64_S512": ("encoder", 64, 16, 256, 512, 512, False),
+    "ul2_enc_B64_S512_leftpad": ("encoder", 64, 16, 256, 512, 512, True),
+    "ul2_cross_B64_128x512": ("cross", 64, 16, 256, 128, 512, False),
+    "ul2_dec_causal_B64_T128": ("decoder", 64, 16, 256, 128, 128, False),
+}
 
 
 def interleaved(fns, reps, warmup, stream, rng):
@@ -64,7 +75,7 @@ def interleaved(fns, reps, warmup, stream, rng):
 
 def summary(ms):
     s = sorted(ms)
-    return {"median_ms": round(s[len(s) // 2], 4), "min_ms": round(s[0], 4), "n": len(s)}
+    return {"median_ms": round(s[len(s) // 2], 4), "min_ms": round(s[0], 4), "max_ms": round(s[-1], 4), "n": len(s)}
 
 
 def fastest(ms):
@@ -76,6 +87,7 @@ def fastest(ms):
 
 def bench(mode, B, nH, d, Tq, S, padded, dev, reps, warmup, stream, rng):
     dtype = torch.bfloat16
+    QT, KT = P.t5_attention.tiles(d)   # of the kernel that serves d (the byte model below)
     g = torch.Generator(device=dev).manual_seed(Tq * 1000 + S + B)
     s = d ** -0.25
     q = (torch.randn(B, Tq, nH * d, generator=g, device=dev) * s).to(dtype)      # the projections' outputs
@@ -143,15 +155,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None, help="one shape's name")
+    ap.add_argument("--set", default="default", choices=("default", "d256"), help="d256: the UL2-like shapes")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream(dev)
     rng = random.Random(0)
-    print(f"t5_attention tiles: Q_TILE {QT}, KV_TILE {KT}", file=sys.stderr, flush=True)
+    shapes = SHAPES_D256 if args.set == "d256" else SHAPES
+    qt, kt = P.t5_attention.tiles(256) if args.set == "d256" else (QT, KT)
+    print(f"t5_attention tiles: Q_TILE {qt}, KV_TILE {kt}", file=sys.stderr, flush=True)
     rec = {"tool": "t5_attention_bench", "device": torch.cuda.get_device_name(0), "reps": args.reps, "dtype": "bf16",
-           "compute_units": torch.cuda.get_device_properties(0).multi_processor_count, "Q_TILE": QT, "KV_TILE": KT,
+           "compute_units": torch.cuda.get_device_properties(0).multi_processor_count, "Q_TILE": qt, "KV_TILE": kt,
            "shapes": {}}
-    for name, shape in SHAPES.items():
+    for name, shape in shapes.items():
         if args.only and name != args.only:
             continue
         rec["shapes"][name] = bench(*shape, dev, args.reps, args.warmup, stream, rng)

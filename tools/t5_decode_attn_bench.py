@@ -34,6 +34,9 @@ SELF_T = (0, 24, 47)
 MAX_LEN = 48
 CROSS_S = 512
 NUM_BUCKETS, MAX_DISTANCE = 32, 128
+# --set d256: UL2-like heads (nH 16, d_kv 256), self t 0 / 64 / 127 of max_len 128, cross S 512
+MODELS_D256 = [("ul2_B128", 128, 16, 256), ("ul2_B8", 8, 16, 256)]
+SELF_T_D256, MAX_LEN_D256 = (0, 64, 127), 128
 
 
 def interleaved(fns, reps, warmup, stream):
@@ -170,14 +173,19 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--set", default="default", choices=("default", "d256"), help="d256: the UL2-like rows")
     args = ap.parse_args()
+    global MAX_LEN
+    models, self_t = MODELS, SELF_T
+    if args.set == "d256":
+        models, self_t, MAX_LEN = MODELS_D256, SELF_T_D256, MAX_LEN_D256
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream(dev)
     dtype = torch.bfloat16
     rec = {"tool": "t5_decode_attn_bench", "device": torch.cuda.get_device_name(0), "reps": args.reps,
            "dtype": "bf16", "compute_units": torch.cuda.get_device_properties(0).multi_processor_count, "shapes": {}}
-    for name, B, nH, d in MODELS:
-        for t in SELF_T:
+    for name, B, nH, d in models:
+        for t in self_t:
             ms, model, keep = bench_self(B, nH, d, t, dtype, dev, args.reps, args.warmup, stream)
             rec["shapes"][f"{name}_self_t{t}"] = record(ms, model, keep, B=B, nH=nH, d_kv=d, t=t, workgroups=B * nH)
         for padded in (False, True):

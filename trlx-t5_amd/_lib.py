@@ -424,6 +424,7 @@ SIGNATURES = {
     "trlx_t5_decode_embed": (_c_int, [ctypes.POINTER(T5DecodeEmbedArgs), _c_vp, _c_vp]),
     "trlx_t5_attention": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp]),
     "trlx_t5_attention_tiles": (_c_int, [ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),
+    "trlx_t5_attention_tiles_d": (_c_int, [_c_i64, ctypes.POINTER(_c_int), ctypes.POINTER(_c_int)]),
     "trlx_t5_attention_fwd_lse": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp, _c_vp]),
     "trlx_t5_attention_bwd": (_c_int, [ctypes.POINTER(T5AttentionBwdArgs), _c_vp]),
     "trlx_t5_attention_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),

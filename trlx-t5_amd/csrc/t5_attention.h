@@ -37,6 +37,27 @@ __device__ __forceinline__ ta_bf16x8 ta_tr_frag(const unsigned char* p0, int str
     return __builtin_bit_cast(ta_bf16x8, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
+// the forward kernels' argument block (t5_attention.hip builds it after the checks)
+struct TaArgs {
+    const uint16_t* q;
+    const uint16_t* k;
+    const uint16_t* v;
+    uint16_t* out;
+    const float* bias;     // [nH, Tq + S - 1] or NULL
+    const int64_t* mask;   // [B, S] or NULL
+    int64_t q_sb, q_st, q_sh, k_sb, k_st, k_sh, v_sb, v_st, v_sh, o_sb, o_st, o_sh;
+    int nH, Tq, S, nqb;
+};
+
+// d_kv 256 (t5_attention_d256.hip): its tiles, and the launch of the instantiation for `flags` on
+// arguments ta_forward has checked; grid = B * nH * ceil(Tq / kTa256QTile) workgroups
+constexpr int kTa256QTile = 128;
+#ifndef TRLX_TA256_KV_TILE
+#define TRLX_TA256_KV_TILE 32   // 64 builds the other candidate of DESIGN §3 (it spills: not shipped)
+#endif
+constexpr int kTa256KVTile = TRLX_TA256_KV_TILE;
+int ta_launch_d256(const TaArgs& k, int flags, unsigned grid, void* stream);
+
 static inline bool ta_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // one operand's strides: whole 16-byte vectors, rows of d_kv elements that do not overlap, and the

@@ -33,18 +33,9 @@ constexpr int kTaQTile = 128;   // query rows per workgroup (32 per wave)
 constexpr int kTaKVTile = 64;   // keys per LDS tile
 constexpr int kTaBiasWin = kTaQTile + kTaKVTile;   // offsets (key - query) a tile can meet, rounded up
 
-struct TaArgs {
-    const uint16_t* q;
-    const uint16_t* k;
-    const uint16_t* v;
-    uint16_t* out;
-    const float* bias;     // [nH, Tq + S - 1] or NULL
-    const int64_t* mask;   // [B, S] or NULL
-    int64_t q_sb, q_st, q_sh, k_sb, k_st, k_sh, v_sb, v_st, v_sh, o_sb, o_st, o_sh;
-    int nH, Tq, S, nqb;
-};
+static_assert(kTa256QTile == kTaQTile, "ta_forward counts the query blocks of both kernels with kTaQTile");
 
-// the same arguments plus the row statistics' destination (trlx_t5_attention_fwd_lse)
+// the arguments (TaArgs, t5_attention.h) plus the row statistics' destination (trlx_t5_attention_fwd_lse)
 struct TaArgsLse : TaArgs {
     float* lse;            // [B, nH, Tq] fp32
 };
@@ -307,14 +298,22 @@ extern "C" int trlx_t5_attention_tiles(int* q_tile, int* kv_tile) {
     return TRLX_OK;
 }
 
+extern "C" int trlx_t5_attention_tiles_d(int64_t d_kv, int* q_tile, int* kv_tile) {
+    TRLX_REQUIRE(d_kv == 64 || d_kv == 128 || d_kv == 256, TRLX_ERR_ARG, "t5 attention tiles: d_kv %lld (64, 128, 256)",
+                 (long long)d_kv);
+    if (q_tile) *q_tile = d_kv == 256 ? kTa256QTile : kTaQTile;
+    if (kv_tile) *kv_tile = d_kv == 256 ? kTa256KVTile : kTaKVTile;
+    return TRLX_OK;
+}
+
 // the checks and the launch of both entries; with_lse picks the instantiations that also write lse
 static int ta_forward(const TrlxT5AttentionArgs* a, float* lse, bool with_lse, void* stream) {
     TRLX_REQUIRE(a, TRLX_ERR_ARG, "t5 attention: NULL arguments");
     TRLX_REQUIRE(!with_lse || (lse && (reinterpret_cast<uintptr_t>(lse) & 3u) == 0), TRLX_ERR_ARG,
                  "t5 attention: lse is NULL or not aligned to 4 bytes");
     TRLX_REQUIRE(a->dtype == TRLX_BF16, TRLX_ERR_ARG, "t5 attention: dtype %d (bf16 only)", a->dtype);
-    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128, TRLX_ERR_ARG, "t5 attention: d_kv %lld (64 and 128 only)",
-                 (long long)a->d_kv);
+    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128 || (a->d_kv == 256 && !with_lse), TRLX_ERR_ARG,
+                 "t5 attention: d_kv %lld (64 and 128; 256 in the forward without lse)", (long long)a->d_kv);
     const int64_t lim = int64_t(1) << 30;
     TRLX_REQUIRE(a->B >= 1 && a->n_heads >= 1 && a->Tq >= 1 && a->S >= 1 && a->B <= lim && a->n_heads <= lim &&
                      a->Tq <= lim && a->S <= lim,
@@ -373,6 +372,7 @@ static int ta_forward(const TrlxT5AttentionArgs* a, float* lse, bool with_lse, v
     k.S = int(a->S);
     k.nqb = int(nqb);
     const int flags = (a->bias_by_offset ? kTaBias : 0) | (a->key_mask ? kTaMask : 0) | (a->causal ? kTaCausal : 0);
+    if (a->d_kv == 256) return ta_launch_d256(k, flags, unsigned(grid), stream);
     if (with_lse) {
         TaArgsLse kl;
         static_cast<TaArgs&>(kl) = k;

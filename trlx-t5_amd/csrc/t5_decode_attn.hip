@@ -94,6 +94,7 @@ __global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn(
     constexpr int KPW = kWave / LPR;           // key rows per wave-wide load
     constexpr int NG = kT5Waves * KPW;         // groups per workgroup
     static_assert(DKV % EPV == 0 && kWave % LPR == 0 && LPR >= 2, "row geometry");
+    static_assert(DKV / 2 <= kT5Threads, "the merge and the zero store take d_kv / 2 threads");
     __shared__ float s_acc[NG * DKV];
     __shared__ float s_m[NG];
     __shared__ float s_l[NG];
@@ -236,8 +237,12 @@ static t5_kernel_t t5_pick_mode(int mode) {
                               : k_t5_decode_attn<DT, DKV, kT5CrossMasked>;
 }
 static t5_kernel_t t5_pick(int dtype, int64_t d_kv, int mode) {
-    if (dtype == TRLX_BF16) return d_kv == 64 ? t5_pick_mode<BF16T, 64>(mode) : t5_pick_mode<BF16T, 128>(mode);
-    return d_kv == 64 ? t5_pick_mode<F32T, 64>(mode) : t5_pick_mode<F32T, 128>(mode);
+    // d_kv 256: 32 lanes a bf16 row (2 rows a wave-wide load, 8 groups), a whole wave an fp32 row (4 groups)
+    if (dtype == TRLX_BF16)
+        return d_kv == 256 ? t5_pick_mode<BF16T, 256>(mode)
+               : d_kv == 64 ? t5_pick_mode<BF16T, 64>(mode) : t5_pick_mode<BF16T, 128>(mode);
+    return d_kv == 256 ? t5_pick_mode<F32T, 256>(mode)
+           : d_kv == 64 ? t5_pick_mode<F32T, 64>(mode) : t5_pick_mode<F32T, 128>(mode);
 }
 
 static bool t5_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -251,13 +256,13 @@ static int t5_decode_attn_prepare(const TrlxT5DecodeAttnArgs* a, bool dev, T5Att
     TRLX_REQUIRE(a, TRLX_ERR_ARG, "t5 decode attention: NULL arguments");
     TRLX_REQUIRE(a->dtype == TRLX_BF16 || a->dtype == TRLX_F32, TRLX_ERR_ARG,
                  "t5 decode attention: dtype %d (bf16 and fp32 only)", a->dtype);
-    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128, TRLX_ERR_ARG, "t5 decode attention: d_kv %lld (64 and 128 only)",
-                 (long long)a->d_kv);
+    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128 || a->d_kv == 256, TRLX_ERR_ARG,
+                 "t5 decode attention: d_kv %lld (64, 128 and 256 only)", (long long)a->d_kv);
     TRLX_REQUIRE(a->mode == TRLX_T5_ATTN_SELF || a->mode == TRLX_T5_ATTN_CROSS, TRLX_ERR_ARG,
                  "t5 decode attention: mode %d", a->mode);
     const bool self = a->mode == TRLX_T5_ATTN_SELF;
     TRLX_REQUIRE(a->B >= 1 && a->n_heads >= 1 && a->max_len >= 1 && a->B * a->n_heads <= 0x7fffffffLL &&
-                     a->max_len <= 0x7fffffffLL / 128 && a->n_heads <= 0x7fffffffLL / 128,
+                     a->max_len <= 0x7fffffffLL / 128 && a->n_heads <= 0x7fffffffLL / (a->d_kv > 128 ? a->d_kv : 128),
                  TRLX_ERR_ARG, "t5 decode attention: B %lld, heads %lld, max_len %lld", (long long)a->B,
                  (long long)a->n_heads, (long long)a->max_len);
     TRLX_REQUIRE(a->q && a->k && a->v && a->out, TRLX_ERR_ARG, "t5 decode attention: NULL q / K / V / out");
@@ -323,8 +328,10 @@ extern "C" int trlx_t5_decode_attn(const TrlxT5DecodeAttnArgs* a, void* stream) 
 typedef void (*t5_clock_kernel_t)(const T5AttnDevArgs);
 static t5_clock_kernel_t t5_pick_clock(int dtype, int64_t d_kv) {
     if (dtype == TRLX_BF16)
-        return d_kv == 64 ? k_t5_decode_attn<BF16T, 64, kT5Self, true> : k_t5_decode_attn<BF16T, 128, kT5Self, true>;
-    return d_kv == 64 ? k_t5_decode_attn<F32T, 64, kT5Self, true> : k_t5_decode_attn<F32T, 128, kT5Self, true>;
+        return d_kv == 256 ? k_t5_decode_attn<BF16T, 256, kT5Self, true>
+               : d_kv == 64 ? k_t5_decode_attn<BF16T, 64, kT5Self, true> : k_t5_decode_attn<BF16T, 128, kT5Self, true>;
+    return d_kv == 256 ? k_t5_decode_attn<F32T, 256, kT5Self, true>
+           : d_kv == 64 ? k_t5_decode_attn<F32T, 64, kT5Self, true> : k_t5_decode_attn<F32T, 128, kT5Self, true>;
 }
 
 extern "C" int trlx_t5_decode_attn_dev(const TrlxT5DecodeAttnArgs* a, const int64_t* clock, void* stream) {
@@ -354,8 +361,10 @@ static t5_live_kernel_t t5_pick_live_mode(int mode, bool clock) {
 }
 static t5_live_kernel_t t5_pick_live(int dtype, int64_t d_kv, int mode, bool clock) {
     if (dtype == TRLX_BF16)
-        return d_kv == 64 ? t5_pick_live_mode<BF16T, 64>(mode, clock) : t5_pick_live_mode<BF16T, 128>(mode, clock);
-    return d_kv == 64 ? t5_pick_live_mode<F32T, 64>(mode, clock) : t5_pick_live_mode<F32T, 128>(mode, clock);
+        return d_kv == 256 ? t5_pick_live_mode<BF16T, 256>(mode, clock)
+               : d_kv == 64 ? t5_pick_live_mode<BF16T, 64>(mode, clock) : t5_pick_live_mode<BF16T, 128>(mode, clock);
+    return d_kv == 256 ? t5_pick_live_mode<F32T, 256>(mode, clock)
+           : d_kv == 64 ? t5_pick_live_mode<F32T, 64>(mode, clock) : t5_pick_live_mode<F32T, 128>(mode, clock);
 }
 
 extern "C" int trlx_t5_decode_attn_live(const TrlxT5DecodeAttnArgs* a, const int64_t* live, const int64_t* clock,

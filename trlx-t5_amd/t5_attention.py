@@ -23,8 +23,11 @@ T5 does not scale the scores by 1/sqrt(d_kv).  `t5_attention` is forward only; t
 teacher-forced passes take `t5_attention_train`, whose backward recomputes the scores per tile and
 saves nothing of size Tq x S either (no dropout: the reference trains with dropout off).
 
-Kernel shapes: bfloat16 with d_kv 64 / 128.  For any other dtype or d_kv the call evaluates the
-same result as torch expressions in HF's op order (`_torch_attention`).
+Kernel shapes: bfloat16 with d_kv 64 / 128, and 256 (the UL2 head size) in a forward kernel of its
+own (csrc/t5_attention_d256.hip: one wave per SIMD, tiles `tiles(256)`).  For any other dtype or
+d_kv the call evaluates the same result as torch expressions in HF's op order (`_torch_attention`).
+`t5_attention_train` has no d_kv 256 backward yet: there it runs those torch expressions under
+autograd.
 """
 import ctypes
 import math
@@ -33,10 +36,11 @@ import torch
 
 from . import _lib
 
-__all__ = ["t5_relative_bias_offsets", "t5_relative_bias_buckets", "t5_attention", "t5_attention_train", "Q_TILE",
-           "KV_TILE", "BWD_DQ_Q_TILE", "BWD_DQ_KV_TILE", "BWD_DKV_K_TILE", "BWD_DKV_Q_TILE"]
+__all__ = ["t5_relative_bias_offsets", "t5_relative_bias_buckets", "t5_attention", "t5_attention_train", "tiles",
+           "Q_TILE", "KV_TILE", "BWD_DQ_Q_TILE", "BWD_DQ_KV_TILE", "BWD_DKV_K_TILE", "BWD_DKV_Q_TILE"]
 
-# the kernel's tiles (kTaQTile, kTaKVTile in csrc/t5_attention.hip; trlx_t5_attention_tiles reports them)
+# the d_kv 64 / 128 kernel's tiles (kTaQTile, kTaKVTile in csrc/t5_attention.hip; trlx_t5_attention_tiles
+# reports them); tiles(d_kv) has those of every kernel
 Q_TILE = 128    # query rows per workgroup
 KV_TILE = 64    # keys per LDS tile
 # the backward's tiles (csrc/t5_attention_bwd.hip; trlx_t5_attention_bwd_tiles reports them)
@@ -45,7 +49,17 @@ BWD_DQ_KV_TILE = 64     # dq kernel: keys per LDS tile
 BWD_DKV_K_TILE = 128    # dk / dv kernel: keys per workgroup
 BWD_DKV_Q_TILE = 64     # dk / dv kernel: query rows per LDS tile
 KERNEL_DTYPES = (torch.bfloat16,)
-KERNEL_D_KV = (64, 128)
+KERNEL_D_KV = (64, 128, 256)       # t5_attention (the forward)
+TRAIN_KERNEL_D_KV = (64, 128)      # t5_attention_train (forward with lse + backward)
+_TILES = {64: (Q_TILE, KV_TILE), 128: (Q_TILE, KV_TILE), 256: (128, 32)}   # trlx_t5_attention_tiles_d
+
+
+def tiles(d_kv):
+    """(query rows per workgroup, keys per LDS tile) of the forward kernel that serves `d_kv`;
+    ValueError for a d_kv no kernel takes.  What trlx_t5_attention_tiles_d reports."""
+    if d_kv not in _TILES:
+        raise ValueError(f"no t5_attention kernel for d_kv {d_kv} (kernels: {KERNEL_D_KV})")
+    return _TILES[d_kv]
 
 
 def t5_relative_bias_buckets(Tq, S, bidirectional, num_buckets=32, max_distance=128, device=None):
@@ -202,8 +216,8 @@ def t5_attention(q, k, v, *, bias=None, key_mask=None, causal=False, n_heads=Non
         raise RuntimeError("t5_attention is forward only: call it under torch.no_grad(), or take the torch fallback "
                            "t5_attention.torch_fallback(q, k, v, bias, key_mask, causal) on [B, T, nH, d_kv] operands "
                            "(or HF's T5Attention) where a backward is needed")
-    if q4.dtype not in KERNEL_DTYPES or d not in KERNEL_D_KV:
-        return _torch_attention(q4, k4, v4, bias, key_mask, bool(causal))
+    if q4.dtype not in KERNEL_DTYPES or d not in KERNEL_D_KV or (d == 256 and not q4.is_cuda):
+        return _torch_attention(q4, k4, v4, bias, key_mask, bool(causal))   # d_kv 256 off the GPU: as before its kernel
     _lib.require_cuda(q4)
     return _kernel_forward(_in_place(q4), _in_place(k4), _in_place(v4), bias, key_mask, causal, False)[0]
 
@@ -293,7 +307,8 @@ def t5_attention_train(q, k, v, *, bias=None, key_mask=None, causal=False, n_hea
     (trlx_t5_attention_bwd: dq, dk, dv bit-reproducible, the bias gradient summed with fp32 atomics
     and not).  The incoming gradient is read in place when it meets the stride rules, else copied
     once.  No double backward.  Under torch.no_grad(), or with nothing that requires grad, this is
-    `t5_attention`.  For other dtypes, other d_kv or CPU tensors the same torch expressions as
+    `t5_attention`.  For other dtypes, other d_kv (256 included: the d_kv 256 kernel is forward
+    only, a backward for it is not built) or CPU tensors the same torch expressions as
     `t5_attention`'s run under autograd; float64 operands stay in float64 throughout, softmax
     included, and may come with a float64 bias table."""
     q4, k4, v4, (B, Tq, nH, d, S) = _checked(q, k, v, bias, key_mask, causal, n_heads, layout, f64_bias=True)
@@ -304,7 +319,7 @@ def t5_attention_train(q, k, v, *, bias=None, key_mask=None, causal=False, n_hea
         return t5_attention(q, k, v, bias=bias, key_mask=key_mask, causal=causal, n_heads=n_heads, layout=layout)
     if q4.dtype == torch.float64:   # no kernel either way: all of it in float64 (a float64 bias table is taken too)
         return _torch_attention(q4, k4, v4, bias, key_mask, bool(causal), softmax_dtype=torch.float64)
-    if q4.dtype not in KERNEL_DTYPES or d not in KERNEL_D_KV or not q4.is_cuda:
+    if q4.dtype not in KERNEL_DTYPES or d not in TRAIN_KERNEL_D_KV or not q4.is_cuda:
         return _torch_attention(q4, k4, v4, bias, key_mask, bool(causal))
     return _T5AttentionFn.apply(q4, k4, v4, bias, key_mask, bool(causal))
 
@@ -312,6 +327,7 @@ def t5_attention_train(q, k, v, *, bias=None, key_mask=None, causal=False, n_hea
 # the package exports the function under the module's name: keep the tiles reachable either way
 t5_attention.Q_TILE = Q_TILE
 t5_attention.KV_TILE = KV_TILE
+t5_attention.tiles = tiles
 t5_attention.torch_fallback = _torch_attention
 t5_attention_train.DQ_Q_TILE = BWD_DQ_Q_TILE
 t5_attention_train.DQ_KV_TILE = BWD_DQ_KV_TILE

@@ -29,8 +29,10 @@ does that in one launch with one workgroup per (batch row, head): fp32 dot produ
 online fp32 softmax, fp32 P·V, one rounding.  T5 does not scale the scores by 1/sqrt(d_kv).
 Forward only: generation runs under no_grad.
 
-Kernel shapes: bfloat16 / float32 with d_kv 64 / 128.  For any other dtype or d_kv the two
-functions evaluate the same step as torch expressions (`_torch_self_attention`,
+Kernel shapes: bfloat16 / float32 with d_kv 64 / 128 / 256 (256, the UL2 head size: 32 lanes a
+bf16 key row, a whole wave an fp32 one) for the self- and the cross-attention, host t, t=clock and
+live= alike; the kv8, grouped and split calls take d_kv 64 / 128.  For any other dtype or d_kv the
+two functions evaluate the same step as torch expressions (`_torch_self_attention`,
 `_torch_cross_attention`, HF's op order).
 """
 import ctypes
@@ -45,7 +47,8 @@ __all__ = ["t5_relative_bias_table", "T5DecodeKVCache", "T5DecodeClock", "t5_dec
            "t5_decode_cross_attention_kv8", "t5_decode_cross_attention_grouped"]
 
 KERNEL_DTYPES = (torch.bfloat16, torch.float32)
-KERNEL_D_KV = (64, 128)
+KERNEL_D_KV = (64, 128)            # the kv8, grouped, grouped-MMA and split calls
+BASE_KERNEL_D_KV = (64, 128, 256)  # t5_decode_self_attention / t5_decode_cross_attention (t=clock and live= included)
 
 
 def t5_relative_bias_table(weight, max_len, num_buckets=32, max_distance=128):
@@ -173,6 +176,10 @@ def _check_q(q, B, nH, d, dtype, device):
 
 
 def _kernel_takes(dtype, d):
+    return dtype in KERNEL_DTYPES and d in BASE_KERNEL_D_KV
+
+
+def _group_kernel_takes(dtype, d):
     return dtype in KERNEL_DTYPES and d in KERNEL_D_KV
 
 
@@ -184,7 +191,7 @@ def _check_live(live, B, dtype, d, device):
         raise ValueError(f"live must be a contiguous int64 [B] = [{B}] tensor on {device}, got {live.dtype} "
                          f"{tuple(live.shape)} on {live.device}")
     if not _kernel_takes(dtype, d):
-        raise ValueError(f"live= needs the kernel ({KERNEL_DTYPES}, d_kv in {KERNEL_D_KV}); got {dtype}, d_kv {d}")
+        raise ValueError(f"live= needs the kernel ({KERNEL_DTYPES}, d_kv in {BASE_KERNEL_D_KV}); got {dtype}, d_kv {d}")
 
 
 def _torch_self_attention(q, k_new, v_new, cache, t, bias_table):
@@ -244,7 +251,7 @@ def t5_decode_self_attention(q, k_new, v_new, cache, t, bias_table=None, live=No
         if clock.device != cache.device:
             raise ValueError(f"the clock is on {clock.device}, the cache on {cache.device}")
         if not _kernel_takes(cache.dtype, d):
-            raise ValueError(f"t=clock needs the kernel ({KERNEL_DTYPES}, d_kv in {KERNEL_D_KV}); the torch "
+            raise ValueError(f"t=clock needs the kernel ({KERNEL_DTYPES}, d_kv in {BASE_KERNEL_D_KV}); the torch "
                              f"fallback for {cache.dtype}, d_kv {d} slices by a host t and cannot be captured")
         t = 0
     else:
@@ -587,7 +594,7 @@ def t5_decode_cross_attention_grouped(q, k_enc, v_enc, key_mask=None, live=None,
     t5_decode_cross_attention does for the repeat_interleave'd operands.
     Runs on the current stream, no host sync; only the output is allocated."""
     k, v, (P, nH, S, d, B, G) = _group_checked(q, k_enc, v_enc, key_mask, live, n_heads)
-    if not k.is_cuda or not _kernel_takes(k.dtype, d):
+    if not k.is_cuda or not _group_kernel_takes(k.dtype, d):
         return t5_decode_cross_attention(
             q, k.repeat_interleave(G, 0).contiguous(), v.repeat_interleave(G, 0).contiguous(),
             None if key_mask is None else key_mask.repeat_interleave(G, 0), live)
@@ -610,7 +617,7 @@ def t5_decode_cross_attention_grouped_mma(q, k_enc, v_enc, key_mask=None, live=N
     to t5_decode_cross_attention_grouped.  One launch, same arguments at every token: capturable.
     Runs on the current stream, no host sync; only the output is allocated."""
     k, v, dims = _group_checked(q, k_enc, v_enc, key_mask, live, n_heads)
-    if not k.is_cuda or k.dtype != torch.bfloat16 or not _kernel_takes(k.dtype, dims[3]):
+    if not k.is_cuda or k.dtype != torch.bfloat16 or not _group_kernel_takes(k.dtype, dims[3]):
         return t5_decode_cross_attention_grouped(q, k_enc, v_enc, key_mask, live, n_heads)
     return _group_launch("trlx_t5_decode_attn_group_mma", q, k, v, key_mask, live, dims)
 
@@ -707,7 +714,7 @@ def t5_decode_cross_attention_split(q, k_enc, v_enc, key_mask=None, live=None, n
             raise ValueError(f"key_mask must be int64 [P, S] = [{P}, {S}] on {k.device}")
     if live is not None:
         _check_live(live, B, k.dtype, d, k.device)
-    if not k.is_cuda or not _kernel_takes(k.dtype, d):
+    if not k.is_cuda or not _group_kernel_takes(k.dtype, d):
         return t5_decode_cross_attention_grouped(q, k_enc, v_enc, key_mask, live, n_heads)
     _lib.require_cuda(k, q)
     X = int(splits) if splits is not None else t5_decode_cross_attention_split_plan(k.dtype, P, G, nH, d, S)
