@@ -21,13 +21,17 @@ Shapes: T5-base (nH 12, d 64) with P * G = 256 at G 1, 2, 4, 8, S 512, full and 
 the lower b median at T5-base P 64 x G 4, S 512, full: `tile_decision` holds both numbers.
 
 --parent-lib PATH: the A/B of the entries that existed before (trlx_t5_decode_attn, cross at B 256
-S 512 with the key mask and self at B 256 t 47, T5-base) against another build of the library, in
-alternating child processes, four runs each: this tree's median must lie inside the other build's
-own min-max spread, else it is reported as a regression with both spreads.
+S 512 with the key mask and self at B 256 t 47; the grouped entry at P 64 x G 4, S 512; the split
+entry at P 2 x G 4, S 2048, X 8; all T5-base) against another build of the library, in alternating
+child processes, four runs each: this tree's median must lie inside the other build's own min-max
+spread, else it is reported as a regression with both spreads.  Each child also prints SHA-256
+digests of those entries' outputs on small seeded inputs (`ab_bits`); they must be the same in every
+child of both builds and go to `bits_ab`.
 
     python tools/t5_cross_group_bench.py [--reps N] [--out FILE] [--parent-lib other/libtrlx_t5_amd.so]"""
 import argparse
 import ctypes
+import hashlib
 import json
 import os
 import random
@@ -151,9 +155,64 @@ def bench_shape(Pn, G, nH, d, padded, dev, reps, warmup, rng):
 
 
 # ------------------------------------------------------------------ the entries that existed before
+def ab_bits(dev):
+    """SHA-256 of the outputs of the plain, grouped and split entries on fixed seeded inputs: bf16 and
+    fp32, d_kv 64 and 128 (256 too for the plain entry), nH 2, P 2 x G 5 (at tile 4 a remainder tile,
+    at tile 8 the second park round), S = 2 NG + 3 (the two-in-flight loop ends on its second slot;
+    at X 2 the second range is a remainder), with and without the key mask, and with no live, a dead
+    row, and the four dead rows of a whole tile."""
+    def digest(t):
+        return hashlib.sha256(t.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
+
+    out, Pn, G, nH = {}, 2, 5, 2
+    B = Pn * G
+    tile = P.t5_decode.t5_decode_cross_attention_group_tile
+    for dtype, epv in ((torch.bfloat16, 8), (torch.float32, 4)):
+        for d in (64, 128, 256):
+            Sk = 2 * 4 * (64 // (d // epv)) + 3
+            g = torch.Generator(device=dev).manual_seed(1000 + d + epv)
+            q = (torch.randn(B, nH * d, generator=g, device=dev) * d ** -0.25).to(dtype)
+            K = (torch.randn(Pn, nH, Sk, d, generator=g, device=dev) * d ** -0.25).to(dtype)
+            V = torch.randn(Pn, nH, Sk, d, generator=g, device=dev).to(dtype)
+            mask = (torch.rand(Pn, Sk, generator=g, device=dev) > 0.3).long()
+            mask[0, Sk - 5:] = 0
+            lives = {"all": None, "dead_row": torch.ones(B, dtype=torch.int64, device=dev),
+                     "dead_tile": torch.ones(B, dtype=torch.int64, device=dev)}
+            lives["dead_row"][3] = 0
+            lives["dead_tile"][:4] = 0
+            Kx, Vx = K.repeat_interleave(G, 0).contiguous(), V.repeat_interleave(G, 0).contiguous()
+            T = Sk + 1
+            kn = (torch.randn(B, nH * d, generator=g, device=dev) * d ** -0.25).to(dtype)
+            vn = torch.randn(B, nH * d, generator=g, device=dev).to(dtype)
+            table = P.t5_relative_bias_table(torch.randn(32, nH, generator=g, device=dev), T)
+            for mname, m in (("nomask", None), ("mask", mask)):
+                for lname, lv in lives.items():
+                    key = f"{str(dtype)[6:]}_d{d}_{mname}_{lname}"
+                    mx = None if m is None else m.repeat_interleave(G, 0).contiguous()
+                    out["cross_" + key] = digest(P.t5_decode_cross_attention(q, Kx, Vx, mx, lv))
+                    if d == 256:
+                        continue
+                    for t in TILES:
+                        tile(t)
+                        try:
+                            out[f"grouped_tile{t}_" + key] = digest(P.t5_decode_cross_attention_grouped(q, K, V, m, lv))
+                            out[f"split_X2_tile{t}_" + key] = digest(
+                                P.t5_decode_cross_attention_split(q, K, V, m, lv, groups=G, splits=2))
+                        finally:
+                            tile(0)
+            for lname in ("all", "dead_row"):
+                cache = P.T5DecodeKVCache(B, nH, d, T, dtype, dev)
+                cache.k.copy_(torch.cat([Kx, Kx[:, :, :1]], 2))
+                cache.v.copy_(torch.cat([Vx, Vx[:, :, :1]], 2))
+                o = P.t5_decode_self_attention(q, kn, vn, cache, T - 1, table, lives[lname])
+                out[f"self_{str(dtype)[6:]}_d{d}_{lname}"] = digest(o) + digest(cache.k)[:16] + digest(cache.v)[:16]
+    return out
+
+
 def ab_child():
-    """Per-call us of trlx_t5_decode_attn (cross B 256 S 512 masked, self B 256 t 47) on whatever library
-    TRLX_T5_AMD_LIB names."""
+    """Per-call us of trlx_t5_decode_attn (cross B 256 S 512 masked, self B 256 t 47), of the grouped
+    entry (P 64 x G 4, S 512) and of the split entry (P 2 x G 4, S 2048, X 8) on whatever library
+    TRLX_T5_AMD_LIB names, and ab_bits of it."""
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for n in [n for n in _lib.SIGNATURES if not hasattr(lib, n)]:   # an older build lacks the newer entries
         del _lib.SIGNATURES[n]
@@ -171,9 +230,15 @@ def ab_child():
     v_enc = torch.randn(B, nH, S, d, generator=g, device=dev).to(torch.bfloat16)
     mask = torch.ones(B, S, dtype=torch.int64, device=dev)
     mask[:, S - 37:] = 0
+    kg, vg = k_enc[:64], v_enc[:64]                                        # P 64 x G 4
+    k2 = (torch.randn(2, nH, 2048, d, generator=g, device=dev) * d ** -0.25).to(torch.bfloat16)
+    v2 = torch.randn(2, nH, 2048, d, generator=g, device=dev).to(torch.bfloat16)
     res = {}
     for name, fn in (("t5_decode_attn_cross_B256_S512", lambda: P.t5_decode_cross_attention(q, k_enc, v_enc, mask)),
-                     ("t5_decode_attn_self_B256_t47", lambda: P.t5_decode_self_attention(q, kn, vn, cache, t, table))):
+                     ("t5_decode_attn_self_B256_t47", lambda: P.t5_decode_self_attention(q, kn, vn, cache, t, table)),
+                     ("t5_decode_attn_group_P64_G4_S512", lambda: P.t5_decode_cross_attention_grouped(q, kg, vg)),
+                     ("t5_decode_attn_split_P2_G4_S2048_X8",
+                      lambda: P.t5_decode_cross_attention_split(q[:8], k2, v2, groups=4, splits=8))):
         for _ in range(20):
             fn()
         per = []
@@ -187,11 +252,13 @@ def ab_child():
             per.append(e0.elapsed_time(e1) * 1000.0 / 20)
         res[name] = statistics.median(per)
     print("AB_CHILD " + json.dumps(res))
+    print("AB_BITS " + json.dumps(ab_bits(dev)))
 
 
 def existing_entries_ab(parent_lib, runs=4):
     sides = {"parent": os.path.abspath(parent_lib), "this_tree": _lib.LIB_PATH}
     got = {s: {} for s in sides}
+    bits = {s: [] for s in sides}
     for _ in range(runs):
         for side, lib in sides.items():   # alternating child processes
             env = dict(os.environ, TRLX_T5_AMD_LIB=lib)
@@ -200,6 +267,7 @@ def existing_entries_ab(parent_lib, runs=4):
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("AB_CHILD ")][-1]
             for k, v in json.loads(line[len("AB_CHILD "):]).items():
                 got[side].setdefault(k, []).append(v)
+            bits[side].append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("AB_BITS ")][-1][len("AB_BITS "):]))
     out = {"unit": "us per call (HIP events around 20 calls, median of 30), one figure per child process",
            "criterion": "this tree's median inside the parent's own min-max spread"}
     for k in got["parent"]:
@@ -208,6 +276,12 @@ def existing_entries_ab(parent_lib, runs=4):
         out[k] = {"parent": p, "this_tree": c, "parent_spread": [min(p), max(p)], "this_tree_spread": [min(c), max(c)],
                   "this_tree_median": med, "inside_parent_spread": min(p) <= med <= max(p),
                   "verdict": "inside" if min(p) <= med <= max(p) else ("faster" if med < min(p) else "REGRESSION")}
+    same = all(b == bits["parent"][0] for s in sides for b in bits[s])
+    out["bits_ab"] = {"what": ab_bits.__doc__.split(":")[0], "cases": len(bits["parent"][0]),
+                      "equal_in_every_child_of_both_builds": same,
+                      "differing": sorted({k for s in sides for b in bits[s] for k in b if b[k] != bits["parent"][0].get(k)}),
+                      "sha256": bits["this_tree"][0]}
+    assert same, f"outputs differ between the builds: {out['bits_ab']['differing']}"
     return out
 
 

@@ -9,7 +9,7 @@
 // by 2^-e (exact in fp32), rounds to e4m3fn in integer arithmetic and stores 8 bytes.  The
 // rounding restates torch's cast (c10 fp8e4m3fn_from_fp32_value) step for step, so the bytes are
 // torch's for every input, ties and subnormals included; v_cvt_pk_fp8_f32 is not used.
-#include "common.h"
+#include "t5_decode_row.h"
 
 namespace trlx {
 
@@ -189,10 +189,11 @@ extern "C" int trlx_t5_cross_kv_quantize(const TrlxT5CrossKvQuantArgs* a, void* 
 // (v_cvt_pk_f32_fp8); the arithmetic is the bf16 kernel's: fp32 dot, butterfly inside the group,
 // times k_scale, online fp32 softmax, fp32 P·V; v_scale multiplies at the merge, before the
 // division and the one rounding.  Same fixed merge order.  Kernels and an argument block of their
-// own in a translation unit of their own: t5_decode_attn.hip and its code object are as they were.
+// own in a translation unit of their own; the geometry and the stores are t5_decode_row.h's.  The
+// step and the merge are written out here: they differ from the shared ones in the scale, in
+// unpacking V late and in what a skipped group is known by, and folded into the shared forms the
+// masked kernels went from 96 to 97 / 98 VGPRs, from 5 waves a SIMD to 4.
 constexpr int kKv8Flight = 4;
-constexpr int kT5Threads = 256;   // as in t5_decode_attn.hip
-constexpr int kT5Waves = kT5Threads / kWave;
 
 struct T5AttnKv8Args {
     const void* q;
@@ -221,12 +222,11 @@ __device__ __forceinline__ void kv8_unpack(const vec4u& v, float (&f)[16]) {
 }
 
 template <int DKV, bool MASKED, bool LIVE>
-__global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn_kv8(const T5AttnKv8Args args) {
+__global__ __launch_bounds__(kT5RowThreads) void k_t5_decode_attn_kv8(const T5AttnKv8Args args) {
     const T5AttnKv8Args& a = args;
     constexpr int EPV = 16;
-    constexpr int LPR = DKV / EPV;
-    constexpr int KPW = kWave / LPR;
-    constexpr int NG = kT5Waves * KPW;
+    typedef T5RowGeom<EPV, DKV> Geom;
+    constexpr int LPR = Geom::LPR, KPW = Geom::KPW, NG = Geom::NG;
     constexpr int NF = kKv8Flight;
     __shared__ float s_acc[NG * DKV];
     __shared__ float s_m[NG];
@@ -236,8 +236,7 @@ __global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn_kv8(const T5AttnK
     const int b = bh / a.nH, h = bh - b * a.nH;
     if constexpr (LIVE) {
         if (args.live[b] == 0) {   // block-uniform: zeros to out[b, h, :]
-            if (threadIdx.x < DKV / 2)
-                *reinterpret_cast<uint32_t*>(static_cast<uint16_t*>(a.out) + int64_t(bh) * DKV + 2 * threadIdx.x) = 0u;
+            t5_zero_row<uint16_t, DKV>(a.out, int64_t(bh) * DKV);
             return;
         }
     }
@@ -279,7 +278,7 @@ __global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn_kv8(const T5AttnK
         const float mn = fmaxf(m, s);
         const float sc = expf(m - mn), p = expf(s - mn);
         l = fmaf(l, sc, p);
-        kv8_unpack(vv, vf);
+        kv8_unpack(vv, vf);   // 16 values: unpacked only here, or the masked kernels lose a wave of occupancy
 #pragma unroll
         for (int e = 0; e < EPV; ++e) acc[e] = fmaf(acc[e], sc, p * vf[e]);
         m = mn;
@@ -331,7 +330,7 @@ __global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn_kv8(const T5AttnK
         const bool any = L > 0.f || L != L;   // no live key at all: zeros
         o0 = any ? (o0 * vs) / L : 0.f;
         o1 = any ? (o1 * vs) / L : 0.f;
-        *reinterpret_cast<uint32_t*>(static_cast<uint16_t*>(a.out) + int64_t(bh) * DKV + d) = pack_bf2(o0, o1);
+        t5_store_pair<uint16_t>(a.out, int64_t(bh) * DKV + d, o0, o1);
     }
 }
 
@@ -387,6 +386,6 @@ extern "C" int trlx_t5_decode_attn_kv8(const TrlxT5DecodeAttnArgs* a, const floa
     k.live = live;
     const bool masked = a->key_mask != nullptr;
     hipLaunchKernelGGL(a->d_kv == 64 ? t5_pick_kv8_d<64>(masked, live != nullptr) : t5_pick_kv8_d<128>(masked, live != nullptr),
-                       dim3(unsigned(a->B * a->n_heads)), dim3(kT5Threads), 0, (hipStream_t)stream, k);
+                       dim3(unsigned(a->B * a->n_heads)), dim3(kT5RowThreads), 0, (hipStream_t)stream, k);
     return check_launch("k_t5_decode_attn_kv8");
 }

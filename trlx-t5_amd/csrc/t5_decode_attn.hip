@@ -8,7 +8,9 @@
 // the group and keeps its own online-softmax state (running max, running sum, its slice of P·V in
 // fp32): no cross-group traffic inside the loop.  The 4 waves x KPW groups walk the cached columns
 // round-robin, two columns per group in flight.  At the end every group parks its state in LDS and
-// d_kv / 2 threads merge the groups in a fixed order, divide and round once.
+// d_kv / 2 threads merge the groups in a fixed order, divide and round once.  The geometry, the
+// per-key step, the merge and the stores are those of t5_decode_row.h, which the fp8, grouped and
+// split kernels share.
 //
 // Self-attention: group 0 holds k_new / v_new of this (row, head) in registers, stores them to
 // column t of the cache and attends to them FROM THE REGISTERS; the loop reads columns 0..t-1
@@ -16,12 +18,9 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "common.h"
+#include "t5_decode_row.h"
 
 namespace trlx {
-
-constexpr int kT5Threads = 256;
-constexpr int kT5Waves = kT5Threads / kWave;
 
 enum { kT5Self = 0, kT5Cross = 1, kT5CrossMasked = 2 };
 
@@ -53,22 +52,6 @@ __device__ __forceinline__ const T5AttnArgs& t5_args(const T5AttnArgs& a) { retu
 __device__ __forceinline__ const T5AttnArgs& t5_args(const T5AttnDevArgs& a) { return a.a; }
 __device__ __forceinline__ const T5AttnArgs& t5_args(const T5AttnLiveArgs& a) { return a.a; }
 
-// zeros to out[b, h, :]: what a dead step and a skipped row store
-template <class E, int DKV>
-__device__ __forceinline__ void t5_zero_out(void* out, int bh) {
-    if (threadIdx.x < DKV / 2) {
-        const int64_t o = int64_t(bh) * DKV + 2 * threadIdx.x;
-        if (sizeof(E) == 2) {
-            *reinterpret_cast<uint32_t*>(static_cast<uint16_t*>(out) + o) = 0u;
-        } else {
-            float2 z;
-            z.x = 0.f;
-            z.y = 0.f;
-            *reinterpret_cast<float2*>(static_cast<float*>(out) + o) = z;
-        }
-    }
-}
-
 template <class DT>
 __device__ __forceinline__ vec4u t5_ld(const typename DT::elem_t* p) {
     return *reinterpret_cast<const vec4u*>(p);
@@ -84,17 +67,14 @@ __device__ __forceinline__ vec4u t5_ld(const typename DT::elem_t* p) {
 // q, k_new, v_new, the cache, the mask or the bias: column t of a skipped row stays unwritten.  A
 // row with live[b] != 0 runs the code below unchanged.  LIVE = false compiles to the kernel without it.
 template <class DT, int DKV, int MODE, bool DEVT = false, bool LIVE = false>
-__global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn(
+__global__ __launch_bounds__(kT5RowThreads) void k_t5_decode_attn(
     const std::conditional_t<LIVE, T5AttnLiveArgs, std::conditional_t<DEVT, T5AttnDevArgs, T5AttnArgs>> args) {
     static_assert(!DEVT || MODE == kT5Self, "only the self-attention reads t");
     const T5AttnArgs& a = t5_args(args);
     typedef typename DT::elem_t E;
     constexpr int EPV = DT::kEPV;
-    constexpr int LPR = DKV / EPV;             // lanes per key row
-    constexpr int KPW = kWave / LPR;           // key rows per wave-wide load
-    constexpr int NG = kT5Waves * KPW;         // groups per workgroup
-    static_assert(DKV % EPV == 0 && kWave % LPR == 0 && LPR >= 2, "row geometry");
-    static_assert(DKV / 2 <= kT5Threads, "the merge and the zero store take d_kv / 2 threads");
+    typedef T5RowGeom<EPV, DKV> Geom;
+    constexpr int LPR = Geom::LPR, KPW = Geom::KPW, NG = Geom::NG;
     __shared__ float s_acc[NG * DKV];
     __shared__ float s_m[NG];
     __shared__ float s_l[NG];
@@ -107,7 +87,7 @@ __global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn(
     const int col = h * DKV + sl * EPV;
     if constexpr (LIVE) {
         if (args.live[b] == 0) {   // block-uniform
-            t5_zero_out<E, DKV>(a.out, bh);
+            t5_zero_row<E, DKV>(a.out, int64_t(bh) * DKV);
             return;
         }
     }
@@ -116,7 +96,7 @@ __global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn(
         const int64_t tc = args.clock[TRLX_CLOCK_T], cap = args.clock[TRLX_CLOCK_CAP];
         const int64_t lim = cap < int64_t(a.max_len) ? cap : int64_t(a.max_len);
         if (tc < 0 || tc >= lim) {   // block-uniform
-            t5_zero_out<E, DKV>(a.out, bh);
+            t5_zero_row<E, DKV>(a.out, int64_t(bh) * DKV);
             return;
         }
         t_clock = int(tc);
@@ -141,23 +121,12 @@ __global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn(
 #pragma unroll
     for (int e = 0; e < EPV; ++e) acc[e] = 0.f;
 
-    // one key: fp32 dot over the row (butterfly inside the group), the online max / sum, P·V
+    // one key, its score plus the bias bj
     auto step = [&](const vec4u& kv, const vec4u& vv, float bj) {
         float kf[EPV], vf[EPV];
         DT::unpack(kv, kf);
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < EPV; ++e) s = fmaf(qf[e], kf[e], s);
-#pragma unroll
-        for (int off = LPR / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
-        s += bj;
-        const float mn = fmaxf(m, s);
-        const float sc = expf(m - mn), p = expf(s - mn);
-        l = fmaf(l, sc, p);
         DT::unpack(vv, vf);
-#pragma unroll
-        for (int e = 0; e < EPV; ++e) acc[e] = fmaf(acc[e], sc, p * vf[e]);
-        m = mn;
+        t5_row_step<LPR>(qf, kf, vf, m, l, acc, T5ScoreAdd{bj});
     };
 
     const int n = MODE == kT5Self ? t : a.max_len;   // columns read from memory: [0, n)
@@ -193,39 +162,13 @@ __global__ __launch_bounds__(kT5Threads) void k_t5_decode_attn(
     }
 
     // merge: every group parks (m, l, its slice of P·V); d_kv / 2 threads combine them in group order
-#pragma unroll
-    for (int e = 0; e < EPV; ++e) s_acc[gg * DKV + sl * EPV + e] = acc[e];
-    if (sl == 0) {
-        s_m[gg] = m;
-        s_l[gg] = l;
-    }
+    t5_row_park<DKV>(s_m, s_l, s_acc, gg, sl, m, l, acc);
     __syncthreads();
     if (threadIdx.x < DKV / 2) {
         const int d = 2 * threadIdx.x;
-        float M = s_m[0];
-        for (int g = 1; g < NG; ++g) M = fmaxf(M, s_m[g]);
-        float L = 0.f, o0 = 0.f, o1 = 0.f;
-        for (int g = 0; g < NG; ++g) {
-            const float mg = s_m[g];
-            if (mg == -INFINITY) continue;   // a group that saw no live key
-            const float w = expf(mg - M);
-            L = fmaf(s_l[g], w, L);
-            o0 = fmaf(s_acc[g * DKV + d], w, o0);
-            o1 = fmaf(s_acc[g * DKV + d + 1], w, o1);
-        }
-        // no live key at all (a fully masked row): zeros
-        const bool any = L > 0.f || L != L;
-        o0 = any ? o0 / L : 0.f;
-        o1 = any ? o1 / L : 0.f;
-        const int64_t o = int64_t(bh) * DKV + d;
-        if (sizeof(E) == 2) {
-            *reinterpret_cast<uint32_t*>(static_cast<uint16_t*>(a.out) + o) = pack_bf2(o0, o1);
-        } else {
-            float2 r;
-            r.x = o0;
-            r.y = o1;
-            *reinterpret_cast<float2*>(static_cast<float*>(a.out) + o) = r;
-        }
+        T5RowState r = t5_row_merge<NG, DKV>(s_m, s_l, s_acc, d);
+        t5_row_divide(r.L, r.o0, r.o1);
+        t5_store_pair<E>(a.out, int64_t(bh) * DKV + d, r.o0, r.o1);
     }
 }
 
@@ -320,7 +263,7 @@ extern "C" int trlx_t5_decode_attn(const TrlxT5DecodeAttnArgs* a, void* stream) 
     const int rc = t5_decode_attn_prepare(a, false, &k);
     if (rc) return rc;
     const int mode = a->mode == TRLX_T5_ATTN_SELF ? kT5Self : a->key_mask ? kT5CrossMasked : kT5Cross;
-    hipLaunchKernelGGL(t5_pick(a->dtype, a->d_kv, mode), dim3(unsigned(a->B * a->n_heads)), dim3(kT5Threads), 0,
+    hipLaunchKernelGGL(t5_pick(a->dtype, a->d_kv, mode), dim3(unsigned(a->B * a->n_heads)), dim3(kT5RowThreads), 0,
                        (hipStream_t)stream, k);
     return check_launch("k_t5_decode_attn");
 }
@@ -346,7 +289,7 @@ extern "C" int trlx_t5_decode_attn_dev(const TrlxT5DecodeAttnArgs* a, const int6
     const int rc = t5_decode_attn_prepare(a, true, &k.a);
     if (rc) return rc;
     k.clock = clock;
-    hipLaunchKernelGGL(t5_pick_clock(a->dtype, a->d_kv), dim3(unsigned(a->B * a->n_heads)), dim3(kT5Threads), 0,
+    hipLaunchKernelGGL(t5_pick_clock(a->dtype, a->d_kv), dim3(unsigned(a->B * a->n_heads)), dim3(kT5RowThreads), 0,
                        (hipStream_t)stream, k);
     return check_launch("k_t5_decode_attn<clock>");
 }
@@ -385,6 +328,6 @@ extern "C" int trlx_t5_decode_attn_live(const TrlxT5DecodeAttnArgs* a, const int
     k.live = live;
     const int mode = a->mode == TRLX_T5_ATTN_SELF ? kT5Self : a->key_mask ? kT5CrossMasked : kT5Cross;
     hipLaunchKernelGGL(t5_pick_live(a->dtype, a->d_kv, mode, clock != nullptr), dim3(unsigned(a->B * a->n_heads)),
-                       dim3(kT5Threads), 0, (hipStream_t)stream, k);
+                       dim3(kT5RowThreads), 0, (hipStream_t)stream, k);
     return check_launch("k_t5_decode_attn<live>");
 }

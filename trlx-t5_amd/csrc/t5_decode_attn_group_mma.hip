@@ -39,6 +39,7 @@
 // zero Q fragments (their rows are not read); MFMA columns are independent, so a row's bits depend
 // on its own q, the prompt's keys, values and mask, and S, and on nothing else.
 #include "t5_attention.h"
+#include "t5_decode_group_check.h"
 
 #ifndef TRLX_T5GM_WAVES_D64
 #define TRLX_T5GM_WAVES_D64 8
@@ -292,41 +293,9 @@ extern "C" int trlx_t5_decode_attn_group_mma_waves(int64_t d_kv) {
 }
 
 extern "C" int trlx_t5_decode_attn_group_mma(const TrlxT5DecodeAttnGroupArgs* a, void* stream) {
-    TRLX_REQUIRE(a, TRLX_ERR_ARG, "t5 grouped mma decode attention: NULL arguments");
-    TRLX_REQUIRE(a->dtype == TRLX_BF16, TRLX_ERR_ARG, "t5 grouped mma decode attention: dtype %d (bf16 only)", a->dtype);
-    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128, TRLX_ERR_ARG, "t5 grouped mma decode attention: d_kv %lld (64 and 128 only)",
-                 (long long)a->d_kv);
-    TRLX_REQUIRE(a->P >= 1 && a->G >= 1 && a->n_heads >= 1 && a->S >= 1, TRLX_ERR_ARG,
-                 "t5 grouped mma decode attention: P %lld, G %lld, heads %lld, S %lld (all >= 1)", (long long)a->P,
-                 (long long)a->G, (long long)a->n_heads, (long long)a->S);
-    // the grid is (P * heads, ceil(G / 16)); rows, heads and keys are 32-bit in the kernel
-    TRLX_REQUIRE(a->P <= 0x7fffffffLL && a->G <= 0x7fffffffLL && a->n_heads <= 0x7fffffffLL / 128 &&
-                     a->S <= 0x7fffffffLL / 128 && a->P * a->n_heads <= 0x7fffffffLL && a->P * a->G <= 0x7fffffffLL,
-                 TRLX_ERR_ARG, "t5 grouped mma decode attention: P %lld, G %lld, heads %lld, S %lld overflow the grid",
-                 (long long)a->P, (long long)a->G, (long long)a->n_heads, (long long)a->S);
-    TRLX_REQUIRE(a->q && a->k && a->v && a->out, TRLX_ERR_ARG, "t5 grouped mma decode attention: NULL q / K / V / out");
-    const int64_t inner = a->n_heads * a->d_kv;
-    const int64_t ldq = a->P * a->G == 1 ? inner : a->ldq;   // a single row has no stride to speak of
-    TRLX_REQUIRE(ldq >= inner && ldq % 8 == 0, TRLX_ERR_ARG,
-                 "t5 grouped mma decode attention: q row stride %lld (>= heads * d_kv = %lld, whole 16-byte vectors)",
-                 (long long)ldq, (long long)inner);
-    // a dimension of size 1 has no stride to speak of
-    const int64_t st[6] = {a->P > 1 ? a->k_stride_p : 0, a->n_heads > 1 ? a->k_stride_h : 0, a->S > 1 ? a->k_stride_s : 0,
-                           a->P > 1 ? a->v_stride_p : 0, a->n_heads > 1 ? a->v_stride_h : 0, a->S > 1 ? a->v_stride_s : 0};
-    for (int i = 0; i < 6; ++i)
-        TRLX_REQUIRE(st[i] >= 0 && st[i] % 8 == 0, TRLX_ERR_ARG,
-                     "t5 grouped mma decode attention: stride %lld (non-negative, whole 16-byte vectors)", (long long)st[i]);
-    TRLX_REQUIRE((a->S == 1 || (st[2] >= a->d_kv && st[5] >= a->d_kv)) &&
-                     (a->n_heads == 1 || (st[1] >= a->d_kv && st[4] >= a->d_kv)),
-                 TRLX_ERR_ARG, "t5 grouped mma decode attention: key and head strides must be at least d_kv");
-    auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
-    TRLX_REQUIRE(!mis(a->q, 15) && !mis(a->k, 15) && !mis(a->v, 15) && !mis(a->out, 15), TRLX_ERR_ARG,
-                 "t5 grouped mma decode attention: q, K, V and out must be 16-byte aligned");
-    TRLX_REQUIRE(!mis(a->key_mask, 7) && !mis(a->live, 7), TRLX_ERR_ARG,
-                 "t5 grouped mma decode attention: key_mask and live must be 8-byte aligned");
-    const int64_t tiles = (a->G + kGmQ - 1) / kGmQ;
-    TRLX_REQUIRE(tiles <= 65535, TRLX_ERR_ARG, "t5 grouped mma decode attention: G %lld gives %lld query tiles (at most 65535)",
-                 (long long)a->G, (long long)tiles);
+    T5GroupChecked c;   // the grid is (P * heads, ceil(G / 16))
+    const int rc = t5_group_check(a, "t5 grouped mma decode attention", false, false, kGmQ, &c);
+    if (rc) return rc;
     T5GmArgs k = {};
     k.q = static_cast<const uint16_t*>(a->q);
     k.k = static_cast<const uint16_t*>(a->k);
@@ -334,14 +303,14 @@ extern "C" int trlx_t5_decode_attn_group_mma(const TrlxT5DecodeAttnGroupArgs* a,
     k.mask = a->key_mask;
     k.live = a->live;
     k.out = static_cast<uint16_t*>(a->out);
-    k.ldq = ldq;
-    k.k_sp = st[0], k.k_sh = st[1], k.k_ss = st[2];
-    k.v_sp = st[3], k.v_sh = st[4], k.v_ss = st[5];
+    k.ldq = c.ldq;
+    k.k_sp = c.st[0], k.k_sh = c.st[1], k.k_ss = c.st[2];
+    k.v_sp = c.st[3], k.v_sh = c.st[4], k.v_ss = c.st[5];
     k.nH = int(a->n_heads);
     k.G = int(a->G);
     k.S = int(a->S);
     const bool masked = a->key_mask != nullptr, live = a->live != nullptr;
-    const dim3 grid(unsigned(a->P * a->n_heads), unsigned(tiles));
+    const dim3 grid(unsigned(a->P * a->n_heads), unsigned(c.tiles));
     if (a->d_kv == 64)
         hipLaunchKernelGGL((t5_gm_pick<64, kGmWaves64>(masked, live)), grid, dim3(kGmWaves64 * kWave), 0, (hipStream_t)stream, k);
     else
