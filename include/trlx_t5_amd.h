@@ -1366,7 +1366,8 @@ int trlx_t5_attention_tiles_d(int64_t d_kv, int* q_tile, int* kv_tile);
 
 /* The same launch, keeping the row statistics the backward needs.  `out` is bit-identical to
  * trlx_t5_attention's on the same arguments (the same kernel, one more store per query), and the
- * refusals are the same, plus a NULL or misaligned `lse` and d_kv 256 (no backward takes it yet).
+ * refusals are the same, plus a NULL or misaligned `lse`.  d_kv 256 is served by its own kernel's
+ * instantiations with the store (csrc/t5_attention_d256.hip), as the forward is.
  *   lse : fp32 [B, n_heads, Tq], contiguous.  lse[b, h, i] = m_i + log(l_i) (natural log), m_i the
  *         largest live score of query i and l_i = sum_j exp(score[i, j] - m_i) over its live keys,
  *         so that exp(score[i, j] - lse) is the softmax weight.  A query with no live key gets +inf:
@@ -1375,8 +1376,10 @@ int trlx_t5_attention_fwd_lse(const TrlxT5AttentionArgs* a, float* lse, void* st
 
 /* ---------------------------------------------------------------- T5 full-sequence attention, backward
  * The gradients of trlx_t5_attention (no dropout: the reference trains with dropout off) from
- * q, k, v, out, lse and dout, holding nothing of size Tq x S.  bf16 only, d_kv 64 or 128, both
- * products and their transposes on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  With
+ * q, k, v, out, lse and dout, holding nothing of size Tq x S.  bf16 only, d_kv 64, 128 or 256, both
+ * products and their transposes on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (256: kernels
+ * of their own, csrc/t5_attention_bwd_d256.hip, the dk / dv one on v_mfma_f32_16x16x32_bf16 with 16
+ * keys a wave; the same semantics).  With
  * s = q_i · k_j + bias (unscaled) over the keys that are not excluded:
  *   P = exp(s - lse)      delta_i = sum_d dout_i · out_i      dP = dout · v^T      dS = P (dP - delta)
  *   dv = P^T · dout       dk = dS^T · q                       dq = dS · k
@@ -1409,9 +1412,10 @@ int trlx_t5_attention_fwd_lse(const TrlxT5AttentionArgs* a, float* lse, void* st
  * fused buffer, are told apart exactly when their sizes and strides are equal and refused
  * otherwise), a missing or short workspace.  dbias, lse and the workspace are the caller's to keep
  * apart from the rest.
- * trlx_t5_attention_bwd_tiles reports the tiles: the dq kernel's query rows per workgroup and keys
- * per LDS tile, the dk / dv kernel's keys per workgroup and query rows per LDS tile; any pointer
- * may be NULL.  Not built: dropout, fp32 / fp16, other d_kv, causal with a cached prefix, a double
+ * trlx_t5_attention_bwd_tiles reports the d_kv 64 / 128 kernels' tiles: the dq kernel's query rows
+ * per workgroup and keys per LDS tile, the dk / dv kernel's keys per workgroup and query rows per
+ * LDS tile; any pointer may be NULL.  trlx_t5_attention_bwd_tiles_d reports those of the kernels
+ * that serve `d_kv` (64, 128, 256; TRLX_ERR_ARG otherwise).  Neither needs a device.  Not built: dropout, fp32 / fp16, other d_kv, causal with a cached prefix, a double
  * backward, a single-kernel backward with atomically accumulated dq. */
 typedef struct TrlxT5AttentionBwdArgs {
     const void* q;
@@ -1438,7 +1442,7 @@ typedef struct TrlxT5AttentionBwdArgs {
     int64_t workspace_bytes;
     int64_t B;
     int64_t n_heads;
-    int64_t d_kv;                     /* 64 or 128 */
+    int64_t d_kv;                     /* 64, 128 or 256 */
     int64_t Tq;
     int64_t S;
     int dtype;                        /* TRLX_BF16 */
@@ -1447,6 +1451,7 @@ typedef struct TrlxT5AttentionBwdArgs {
 int trlx_t5_attention_bwd(const TrlxT5AttentionBwdArgs* a, void* stream);
 int64_t trlx_t5_attention_bwd_workspace_bytes(int64_t B, int64_t n_heads, int64_t Tq);
 int trlx_t5_attention_bwd_tiles(int* dq_q_tile, int* dq_kv_tile, int* dkv_k_tile, int* dkv_q_tile);
+int trlx_t5_attention_bwd_tiles_d(int64_t d_kv, int* dq_q_tile, int* dq_kv_tile, int* dkv_k_tile, int* dkv_q_tile);
 
 /* ---------------------------------------------------------------- T5 feed-forward activation
  * What sits between the projections of HF's T5LayerFF, forward and backward, one launch each:

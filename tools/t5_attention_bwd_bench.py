@@ -1,5 +1,5 @@
 """T5's full-sequence attention, forward + backward, three routes, at tools/t5_attention_bench.py's
-nine shapes.
+nine shapes, or with --set d256 at its six UL2 shapes (nH 16, d_kv 256: csrc/t5_attention_bwd_d256.hip).
 
   eager   HF's eager op sequence under autograd: matmul, position_bias = weight-table gathered to
           [1, nH, Tq, S] plus the additive finfo.min mask, fp32 softmax cast back, matmul; autograd
@@ -20,12 +20,12 @@ Peak memory: the rise of torch.cuda.max_memory_allocated over one forward + back
 operands and dO already allocated.
 
 --forward-ab PARENT_LIB: the existing forward against an earlier build of the library.  The fused
-forward (t5_attention under no_grad) at two encoder shapes in alternating child processes, four
+forward (t5_attention under no_grad) at two shapes of the set in alternating child processes, four
 each, TRLX_T5_AMD_LIB naming the library; the new library's median of medians has to lie inside the
 earlier library's own min-max spread.  Recorded as "forward_ab".
 
 One JSON record is printed and written to --out.
-GPU-box tool:  python tools/t5_attention_bwd_bench.py [--reps N] [--out FILE] [--only NAME] [--forward-ab LIB]"""
+GPU-box tool:  python tools/t5_attention_bwd_bench.py [--reps N] [--out FILE] [--only NAME] [--set d256] [--forward-ab LIB]"""
 import argparse
 import json
 import os
@@ -35,7 +35,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-AB_SHAPES = ("t5base_enc_B64_S512", "t5base_enc_B256_S512_leftpad")
+AB_SHAPES = {"default": ("t5base_enc_B64_S512", "t5base_enc_B256_S512_leftpad"),
+             "d256": ("ul2_enc_B16_S512", "ul2_cross_B64_128x512")}
 
 
 def _load():
@@ -144,23 +145,28 @@ def bench(torch, P, fb, mode, B, nH, d, Tq, S, padded, dev, reps, warmup, stream
     return rec
 
 
-def forward_child(reps, warmup):
-    """The fused forward alone at AB_SHAPES with whichever library TRLX_T5_AMD_LIB names: one JSON line."""
+def shapes_of(fb, which):
+    return fb.SHAPES_D256 if which == "d256" else fb.SHAPES
+
+
+def forward_child(reps, warmup, which):
+    """The fused forward alone at AB_SHAPES[which] with whichever library TRLX_T5_AMD_LIB names: one JSON line."""
     torch, P = _load()
     import t5_attention_bench as fb
     dev = torch.device("cuda:0")
     stream = torch.cuda.current_stream(dev)
     rng = random.Random(0)
     out = {}
-    for name in AB_SHAPES:
-        out[name] = fb.bench(*fb.SHAPES[name], dev, reps, warmup, stream, rng)["fused"]["median_ms"]
+    for name in AB_SHAPES[which]:
+        out[name] = fb.bench(*shapes_of(fb, which)[name], dev, reps, warmup, stream, rng)["fused"]["median_ms"]
     print("FORWARD_AB " + json.dumps(out), flush=True)
 
 
-def forward_ab(parent_lib, reps, warmup, runs=4):
+def forward_ab(parent_lib, reps, warmup, shape_set, runs=4):
     """Alternating child processes, `runs` each; a child that fails ends the A/B (nothing more is started)."""
     parent_lib = os.path.abspath(parent_lib)
-    got = {"parent": {n: [] for n in AB_SHAPES}, "new": {n: [] for n in AB_SHAPES}}
+    names = AB_SHAPES[shape_set]
+    got = {"parent": {n: [] for n in names}, "new": {n: [] for n in names}}
     for _ in range(runs):
         for which in ("parent", "new"):
             env = dict(os.environ)
@@ -168,14 +174,14 @@ def forward_ab(parent_lib, reps, warmup, runs=4):
             if which == "parent":
                 env["TRLX_T5_AMD_LIB"] = parent_lib
             txt = subprocess.run([sys.executable, os.path.abspath(__file__), "--forward-child", "--reps", str(reps),
-                                  "--warmup", str(warmup)], env=env, check=True, timeout=300,
+                                  "--warmup", str(warmup), "--set", shape_set], env=env, check=True, timeout=300,
                                  stdout=subprocess.PIPE, text=True).stdout
             line = [ln for ln in txt.splitlines() if ln.startswith("FORWARD_AB ")][-1]
             for n, ms in json.loads(line[len("FORWARD_AB "):]).items():
                 got[which][n].append(ms)
     rec = {"what": "t5_attention forward (tools/t5_attention_bench.py's fused route) with the earlier library and with "
                    "this one, alternating child processes, medians of %d per run" % reps, "runs_each": runs, "shapes": {}}
-    for n in AB_SHAPES:
+    for n in names:
         p, w = sorted(got["parent"][n]), sorted(got["new"][n])
         med = (w[len(w) // 2 - 1] + w[len(w) // 2]) / 2 if len(w) % 2 == 0 else w[len(w) // 2]
         rec["shapes"][n] = {"parent_median_ms": got["parent"][n], "new_median_ms": got["new"][n],
@@ -190,14 +196,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None, help="one shape's name")
+    ap.add_argument("--set", default="default", choices=("default", "d256"), help="d256: the UL2-like shapes")
     ap.add_argument("--forward-ab", default=None, metavar="PARENT_LIB")
     ap.add_argument("--forward-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     if args.forward_child:
-        return forward_child(args.reps, args.warmup)
+        return forward_child(args.reps, args.warmup, args.set)
     # the A/B's children come first: this process has not opened the GPU yet
-    ab = forward_ab(args.forward_ab, args.reps, args.warmup) if args.forward_ab else None
+    ab = forward_ab(args.forward_ab, args.reps, args.warmup, args.set) if args.forward_ab else None
     torch, P = _load()
     import t5_attention_bench as fb
     TR = P.t5_attention_train
@@ -206,10 +213,10 @@ def main():
     rng = random.Random(0)
     rec = {"tool": "t5_attention_bwd_bench", "device": torch.cuda.get_device_name(0), "reps": args.reps, "dtype": "bf16",
            "compute_units": torch.cuda.get_device_properties(0).multi_processor_count,
-           "tiles": {"dq_q": TR.DQ_Q_TILE, "dq_kv": TR.DQ_KV_TILE, "dkv_k": TR.DKV_K_TILE, "dkv_q": TR.DKV_Q_TILE},
+           "set": args.set, "tiles": dict(zip(("dq_q", "dq_kv", "dkv_k", "dkv_q"), TR.tiles(256 if args.set == "d256" else 64))),
            "flop_model": "flop = 3.5 x forward_flop; forward_flop = 4 nH d sum_b Tq S_live(b) (causal: j <= i)",
            "shapes": {}}
-    for name, shape in fb.SHAPES.items():
+    for name, shape in shapes_of(fb, args.set).items():
         if args.only and name != args.only:
             continue
         rec["shapes"][name] = bench(torch, P, fb, *shape, dev, args.reps, args.warmup, stream, rng)

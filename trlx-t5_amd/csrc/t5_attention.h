@@ -49,14 +49,48 @@ struct TaArgs {
     int nH, Tq, S, nqb;
 };
 
+// the arguments plus the row statistics' destination (trlx_t5_attention_fwd_lse)
+struct TaArgsLse : TaArgs {
+    float* lse;            // [B, nH, Tq] fp32
+};
+
 // d_kv 256 (t5_attention_d256.hip): its tiles, and the launch of the instantiation for `flags` on
-// arguments ta_forward has checked; grid = B * nH * ceil(Tq / kTa256QTile) workgroups
+// arguments ta_forward has checked; grid = B * nH * ceil(Tq / kTa256QTile) workgroups.  `lse`
+// non-NULL picks the instantiations that also write the row statistics.
 constexpr int kTa256QTile = 128;
 #ifndef TRLX_TA256_KV_TILE
 #define TRLX_TA256_KV_TILE 32   // 64 builds the other candidate of DESIGN §3 (it spills: not shipped)
 #endif
 constexpr int kTa256KVTile = TRLX_TA256_KV_TILE;
-int ta_launch_d256(const TaArgs& k, int flags, unsigned grid, void* stream);
+int ta_launch_d256(const TaArgs& k, int flags, unsigned grid, float* lse, void* stream);
+
+// the backward kernels' argument block (trlx_t5_attention_bwd builds it after the checks)
+struct TbArgs {
+    const uint16_t* q;
+    const uint16_t* k;
+    const uint16_t* v;
+    const uint16_t* o;
+    const uint16_t* dout;
+    uint16_t* dq;
+    uint16_t* dk;
+    uint16_t* dv;
+    const float* lse;      // [B, nH, Tq]
+    float* delta;          // [B, nH, Tq]
+    const float* bias;     // [nH, Tq + S - 1] or NULL
+    const int64_t* mask;   // [B, S] or NULL
+    float* dbias;          // [nH, Tq + S - 1] or NULL
+    int64_t q_sb, q_st, q_sh, k_sb, k_st, k_sh, v_sb, v_st, v_sh, o_sb, o_st, o_sh, do_sb, do_st, do_sh;
+    int64_t dq_sb, dq_st, dq_sh, dk_sb, dk_st, dk_sh, dv_sb, dv_st, dv_sh;
+    int nH, Tq, S, nblk;
+};
+
+// d_kv 256 backward (t5_attention_bwd_d256.hip): its tiles, and the dk / dv and dq launches on
+// arguments trlx_t5_attention_bwd has checked, after its delta launch and its zeroing of dbias
+constexpr int kTb256DqQTile = 128;   // dq: query rows per workgroup (32 per wave)
+constexpr int kTb256DqKVTile = 32;   // dq: keys per LDS tile
+constexpr int kTb256KvKTile = 64;    // dkv: keys per workgroup (16 per wave)
+constexpr int kTb256KvQTile = 32;    // dkv: query rows per LDS tile
+int tb_launch_d256(TbArgs k, int flags, unsigned grid_k, unsigned grid_q, void* stream);
 
 static inline bool ta_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

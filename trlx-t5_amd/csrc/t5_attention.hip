@@ -35,11 +35,6 @@ constexpr int kTaBiasWin = kTaQTile + kTaKVTile;   // offsets (key - query) a ti
 
 static_assert(kTa256QTile == kTaQTile, "ta_forward counts the query blocks of both kernels with kTaQTile");
 
-// the arguments (TaArgs, t5_attention.h) plus the row statistics' destination (trlx_t5_attention_fwd_lse)
-struct TaArgsLse : TaArgs {
-    float* lse;            // [B, nH, Tq] fp32
-};
-
 template <int DKV, int FLAGS, bool LSE = false>
 __global__ __launch_bounds__(kTaThreads, 2) void k_t5_attention(const std::conditional_t<LSE, TaArgsLse, TaArgs> a) {
     constexpr bool BIAS = FLAGS & kTaBias, MASK = FLAGS & kTaMask, CAUSAL = FLAGS & kTaCausal;
@@ -312,8 +307,8 @@ static int ta_forward(const TrlxT5AttentionArgs* a, float* lse, bool with_lse, v
     TRLX_REQUIRE(!with_lse || (lse && (reinterpret_cast<uintptr_t>(lse) & 3u) == 0), TRLX_ERR_ARG,
                  "t5 attention: lse is NULL or not aligned to 4 bytes");
     TRLX_REQUIRE(a->dtype == TRLX_BF16, TRLX_ERR_ARG, "t5 attention: dtype %d (bf16 only)", a->dtype);
-    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128 || (a->d_kv == 256 && !with_lse), TRLX_ERR_ARG,
-                 "t5 attention: d_kv %lld (64 and 128; 256 in the forward without lse)", (long long)a->d_kv);
+    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128 || a->d_kv == 256, TRLX_ERR_ARG, "t5 attention: d_kv %lld (64, 128, 256)",
+                 (long long)a->d_kv);
     const int64_t lim = int64_t(1) << 30;
     TRLX_REQUIRE(a->B >= 1 && a->n_heads >= 1 && a->Tq >= 1 && a->S >= 1 && a->B <= lim && a->n_heads <= lim &&
                      a->Tq <= lim && a->S <= lim,
@@ -372,7 +367,7 @@ static int ta_forward(const TrlxT5AttentionArgs* a, float* lse, bool with_lse, v
     k.S = int(a->S);
     k.nqb = int(nqb);
     const int flags = (a->bias_by_offset ? kTaBias : 0) | (a->key_mask ? kTaMask : 0) | (a->causal ? kTaCausal : 0);
-    if (a->d_kv == 256) return ta_launch_d256(k, flags, unsigned(grid), stream);
+    if (a->d_kv == 256) return ta_launch_d256(k, flags, unsigned(grid), with_lse ? lse : nullptr, stream);
     if (with_lse) {
         TaArgsLse kl;
         static_cast<TaArgs&>(kl) = k;

@@ -30,6 +30,9 @@
 // causal diagonal are skipped.  Query rows past Tq are zeros in LDS with lse = +inf.  A query
 // without a live key has lse = +inf, so P = 0 and its dQ row is zeros.
 //
+// d_kv 256 has dk / dv and dq kernels of its own (t5_attention_bwd_d256.hip, tb_launch_d256) behind
+// the same checks; its delta is k_t5_attn_bwd_delta<256>, this file's kernel at 16 k-steps.
+//
 // dbias.  Each dq workgroup adds its dS into an LDS ring of kTbRing offsets (LDS fp32 atomics); the
 // 64 offsets that leave the window when the walk moves on one tile are flushed to the
 // [nH, Tq + S - 1] buffer with global fp32 atomics.  Not bit-reproducible.
@@ -47,25 +50,6 @@ constexpr int kTbKvQTile = 64;    // dkv: query rows per LDS tile
 constexpr int kTbWin = 192;       // offsets (key - query) a 128 x 64 tile pair can meet, rounded up
 constexpr int kTbRing = 256;      // dbias ring in LDS (a power of two >= kTbWin)
 constexpr float kTbL2E = 1.4426950408889634f;
-
-struct TbArgs {
-    const uint16_t* q;
-    const uint16_t* k;
-    const uint16_t* v;
-    const uint16_t* o;
-    const uint16_t* dout;
-    uint16_t* dq;
-    uint16_t* dk;
-    uint16_t* dv;
-    const float* lse;      // [B, nH, Tq]
-    float* delta;          // [B, nH, Tq]
-    const float* bias;     // [nH, Tq + S - 1] or NULL
-    const int64_t* mask;   // [B, S] or NULL
-    float* dbias;          // [nH, Tq + S - 1] or NULL
-    int64_t q_sb, q_st, q_sh, k_sb, k_st, k_sh, v_sb, v_st, v_sh, o_sb, o_st, o_sh, do_sb, do_st, do_sh;
-    int64_t dq_sb, dq_st, dq_sh, dk_sb, dk_st, dk_sh, dv_sb, dv_st, dv_sh;
-    int nH, Tq, S, nblk;
-};
 
 __device__ __forceinline__ ta_bf16x8 tb_zero_frag() { return __builtin_bit_cast(ta_bf16x8, vec4u_make(0, 0, 0, 0)); }
 
@@ -623,6 +607,18 @@ extern "C" int trlx_t5_attention_bwd_tiles(int* dq_q_tile, int* dq_kv_tile, int*
     return TRLX_OK;
 }
 
+extern "C" int trlx_t5_attention_bwd_tiles_d(int64_t d_kv, int* dq_q_tile, int* dq_kv_tile, int* dkv_k_tile,
+                                             int* dkv_q_tile) {
+    TRLX_REQUIRE(d_kv == 64 || d_kv == 128 || d_kv == 256, TRLX_ERR_ARG, "t5 attention bwd tiles: d_kv %lld (64, 128, 256)",
+                 (long long)d_kv);
+    const bool big = d_kv == 256;
+    if (dq_q_tile) *dq_q_tile = big ? kTb256DqQTile : kTbDqQTile;
+    if (dq_kv_tile) *dq_kv_tile = big ? kTb256DqKVTile : kTbDqKVTile;
+    if (dkv_k_tile) *dkv_k_tile = big ? kTb256KvKTile : kTbKvKTile;
+    if (dkv_q_tile) *dkv_q_tile = big ? kTb256KvQTile : kTbKvQTile;
+    return TRLX_OK;
+}
+
 extern "C" int64_t trlx_t5_attention_bwd_workspace_bytes(int64_t B, int64_t n_heads, int64_t Tq) {
     if (!tb_sizes_ok(B, n_heads, Tq)) return -1;
     int64_t n;
@@ -633,13 +629,14 @@ extern "C" int64_t trlx_t5_attention_bwd_workspace_bytes(int64_t B, int64_t n_he
 extern "C" int trlx_t5_attention_bwd(const TrlxT5AttentionBwdArgs* a, void* stream) {
     TRLX_REQUIRE(a, TRLX_ERR_ARG, "t5 attention bwd: NULL arguments");
     TRLX_REQUIRE(a->dtype == TRLX_BF16, TRLX_ERR_ARG, "t5 attention bwd: dtype %d (bf16 only)", a->dtype);
-    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128, TRLX_ERR_ARG, "t5 attention bwd: d_kv %lld (64 and 128 only)",
+    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128 || a->d_kv == 256, TRLX_ERR_ARG, "t5 attention bwd: d_kv %lld (64, 128, 256)",
                  (long long)a->d_kv);
     TRLX_REQUIRE(tb_sizes_ok(a->B, a->n_heads, a->Tq) && a->S >= 1 && a->S <= (int64_t(1) << 30), TRLX_ERR_ARG,
                  "t5 attention bwd: B %lld, heads %lld, Tq %lld, S %lld (each in [1, 2^30])", (long long)a->B,
                  (long long)a->n_heads, (long long)a->Tq, (long long)a->S);
+    const bool big = a->d_kv == 256;
     const int64_t nqb = (a->Tq + kTbDqQTile - 1) / kTbDqQTile;
-    const int64_t nkb = (a->S + kTbKvKTile - 1) / kTbKvKTile;
+    const int64_t nkb = big ? (a->S + kTb256KvKTile - 1) / kTb256KvKTile : (a->S + kTbKvKTile - 1) / kTbKvKTile;
     const int64_t nrb = (a->Tq + 31) / 32;            // delta: one wave per 32 rows
     const int64_t wpb = kTbThreads / kWave;
     int64_t bh, grid_q, grid_k, nwaves;
@@ -747,11 +744,12 @@ extern "C" int trlx_t5_attention_bwd(const TrlxT5AttentionBwdArgs* a, void* stre
     }
     const int flags = (a->bias_by_offset ? kTaBias : 0) | (a->key_mask ? kTaMask : 0) | (a->causal ? kTaCausal : 0);
     {
-        auto fn = a->d_kv == 64 ? k_t5_attn_bwd_delta<64> : k_t5_attn_bwd_delta<128>;
+        auto fn = a->d_kv == 64 ? k_t5_attn_bwd_delta<64> : big ? k_t5_attn_bwd_delta<256> : k_t5_attn_bwd_delta<128>;
         hipLaunchKernelGGL(fn, dim3(unsigned((nwaves + wpb - 1) / wpb)), dim3(kTbThreads), 0, st, k, int(nrb), nwaves);
         const int rc = check_launch("k_t5_attn_bwd_delta");
         if (rc != TRLX_OK) return rc;
     }
+    if (big) return tb_launch_d256(k, flags, unsigned(grid_k), unsigned(grid_q), stream);
     {
         k.nblk = int(nkb);
         tb_kernel_t fn = a->d_kv == 64 ? tb_pick_dkv<64>(flags) : tb_pick_dkv<128>(flags);

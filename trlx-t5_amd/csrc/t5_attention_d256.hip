@@ -26,7 +26,12 @@
 // 32 keys: 32 x (528 + 576) = 35,328 B.  O^T is staged through the same bytes in two passes of 128
 // value columns (128 rows x 272 B) and leaves as whole 16-byte row vectors.  KVT = 64 (70,656 B, O
 // in one pass) is the candidate that was not shipped: four of its instantiations spill.
+//
+// LSE (trlx_t5_attention_fwd_lse): the lane that holds a query also stores lse = m + log(l), +inf for a
+// query with no live key, once after the walk; the instantiations without the flag are unchanged.
 #include <climits>
+
+#include <type_traits>
 
 #include "t5_attention.h"
 
@@ -35,8 +40,8 @@ namespace trlx {
 constexpr int kTdThreads = 256;
 constexpr int kTdD = 256;
 
-template <int KVT, int FLAGS>
-__global__ __launch_bounds__(kTdThreads, 1) void k_t5_attention_d256(const TaArgs a) {
+template <int KVT, int FLAGS, bool LSE = false>
+__global__ __launch_bounds__(kTdThreads, 1) void k_t5_attention_d256(const std::conditional_t<LSE, TaArgsLse, TaArgs> a) {
     constexpr bool BIAS = FLAGS & kTaBias, MASK = FLAGS & kTaMask, CAUSAL = FLAGS & kTaCausal;
     constexpr int QT = kTa256QTile;
     constexpr int CPR = kTdD / 8;                           // 16-byte chunks per row
@@ -251,6 +256,9 @@ __global__ __launch_bounds__(kTdThreads, 1) void k_t5_attention_d256(const TaArg
     // normalise, round once, stage the wave's 32 rows in LDS (OC columns a pass) and store whole rows
     l += __shfl_xor(l, 32, kWave);
     const bool any = l > 0.f || l != l;   // no live key at all: zeros
+    if constexpr (LSE) {   // m + log(l), what the backward rebuilds P from; +inf makes its exp(s - lse) zero
+        if (hh == 0 && qg < a.Tq) a.lse[(int64_t(b) * a.nH + h) * a.Tq + qg] = any ? m + logf(l) : INFINITY;
+    }
     const float rl = any ? l : 1.f;
     unsigned char* sO = smem + wave * 32 * OS;
     uint16_t* obase = a.out + int64_t(b) * a.o_sb + int64_t(h) * a.o_sh;
@@ -282,22 +290,29 @@ __global__ __launch_bounds__(kTdThreads, 1) void k_t5_attention_d256(const TaArg
     }
 }
 
-typedef void (*ta256_kernel_t)(const TaArgs);
-static ta256_kernel_t ta256_pick(int flags) {
+template <bool LSE>
+static auto ta256_pick(int flags) -> void (*)(const std::conditional_t<LSE, TaArgsLse, TaArgs>) {
     switch (flags) {
-        case 0: return k_t5_attention_d256<kTa256KVTile, 0>;
-        case 1: return k_t5_attention_d256<kTa256KVTile, 1>;
-        case 2: return k_t5_attention_d256<kTa256KVTile, 2>;
-        case 3: return k_t5_attention_d256<kTa256KVTile, 3>;
-        case 4: return k_t5_attention_d256<kTa256KVTile, 4>;
-        case 5: return k_t5_attention_d256<kTa256KVTile, 5>;
-        case 6: return k_t5_attention_d256<kTa256KVTile, 6>;
-        default: return k_t5_attention_d256<kTa256KVTile, 7>;
+        case 0: return k_t5_attention_d256<kTa256KVTile, 0, LSE>;
+        case 1: return k_t5_attention_d256<kTa256KVTile, 1, LSE>;
+        case 2: return k_t5_attention_d256<kTa256KVTile, 2, LSE>;
+        case 3: return k_t5_attention_d256<kTa256KVTile, 3, LSE>;
+        case 4: return k_t5_attention_d256<kTa256KVTile, 4, LSE>;
+        case 5: return k_t5_attention_d256<kTa256KVTile, 5, LSE>;
+        case 6: return k_t5_attention_d256<kTa256KVTile, 6, LSE>;
+        default: return k_t5_attention_d256<kTa256KVTile, 7, LSE>;
     }
 }
 
-int ta_launch_d256(const TaArgs& k, int flags, unsigned grid, void* stream) {
-    hipLaunchKernelGGL(ta256_pick(flags), dim3(grid), dim3(kTdThreads), 0, (hipStream_t)stream, k);
+int ta_launch_d256(const TaArgs& k, int flags, unsigned grid, float* lse, void* stream) {
+    if (lse) {
+        TaArgsLse kl;
+        static_cast<TaArgs&>(kl) = k;
+        kl.lse = lse;
+        hipLaunchKernelGGL(ta256_pick<true>(flags), dim3(grid), dim3(kTdThreads), 0, (hipStream_t)stream, kl);
+    } else {
+        hipLaunchKernelGGL(ta256_pick<false>(flags), dim3(grid), dim3(kTdThreads), 0, (hipStream_t)stream, k);
+    }
     return check_launch("k_t5_attention_d256");
 }
 

@@ -8,7 +8,8 @@ with the relative-position bias, the key mask and the causal rule inside the ker
   t5_attention               softmax(q·kᵀ + bias, over the live keys)·v -> [B, Tq, nH*d_kv]
   t5_attention_train         the same under autograd: trlx_t5_attention_fwd_lse forward, saving
                              q, k, v, out and the fp32 row statistics, and trlx_t5_attention_bwd
-                             (csrc/t5_attention_bwd.hip) for dq, dk, dv and the bias table's gradient
+                             (csrc/t5_attention_bwd.hip, at d_kv 256 csrc/t5_attention_bwd_d256.hip)
+                             for dq, dk, dv and the bias table's gradient
 
 The three many-query attentions of a T5 PPO rollout:
   encoder self-attention                 bias = bidirectional table, key_mask = attention_mask
@@ -23,11 +24,11 @@ T5 does not scale the scores by 1/sqrt(d_kv).  `t5_attention` is forward only; t
 teacher-forced passes take `t5_attention_train`, whose backward recomputes the scores per tile and
 saves nothing of size Tq x S either (no dropout: the reference trains with dropout off).
 
-Kernel shapes: bfloat16 with d_kv 64 / 128, and 256 (the UL2 head size) in a forward kernel of its
-own (csrc/t5_attention_d256.hip: one wave per SIMD, tiles `tiles(256)`).  For any other dtype or
-d_kv the call evaluates the same result as torch expressions in HF's op order (`_torch_attention`).
-`t5_attention_train` has no d_kv 256 backward yet: there it runs those torch expressions under
-autograd.
+Kernel shapes: bfloat16 with d_kv 64 / 128, and 256 (the UL2 head size) in kernels of its own
+(csrc/t5_attention_d256.hip and csrc/t5_attention_bwd_d256.hip: one wave per SIMD, tiles `tiles(256)`
+and `t5_attention_train.tiles(256)`).  For any other dtype or d_kv the call evaluates the same
+result as torch expressions in HF's op order (`_torch_attention`), under autograd in
+`t5_attention_train`.
 """
 import ctypes
 import math
@@ -37,21 +38,26 @@ import torch
 from . import _lib
 
 __all__ = ["t5_relative_bias_offsets", "t5_relative_bias_buckets", "t5_attention", "t5_attention_train", "tiles",
+           "bwd_tiles",
            "Q_TILE", "KV_TILE", "BWD_DQ_Q_TILE", "BWD_DQ_KV_TILE", "BWD_DKV_K_TILE", "BWD_DKV_Q_TILE"]
 
 # the d_kv 64 / 128 kernel's tiles (kTaQTile, kTaKVTile in csrc/t5_attention.hip; trlx_t5_attention_tiles
 # reports them); tiles(d_kv) has those of every kernel
 Q_TILE = 128    # query rows per workgroup
 KV_TILE = 64    # keys per LDS tile
-# the backward's tiles (csrc/t5_attention_bwd.hip; trlx_t5_attention_bwd_tiles reports them)
+# the d_kv 64 / 128 backward's tiles (csrc/t5_attention_bwd.hip; trlx_t5_attention_bwd_tiles reports them);
+# bwd_tiles(d_kv) has those of every backward
 BWD_DQ_Q_TILE = 128     # dq kernel: query rows per workgroup
 BWD_DQ_KV_TILE = 64     # dq kernel: keys per LDS tile
 BWD_DKV_K_TILE = 128    # dk / dv kernel: keys per workgroup
 BWD_DKV_Q_TILE = 64     # dk / dv kernel: query rows per LDS tile
 KERNEL_DTYPES = (torch.bfloat16,)
 KERNEL_D_KV = (64, 128, 256)       # t5_attention (the forward)
-TRAIN_KERNEL_D_KV = (64, 128)      # t5_attention_train (forward with lse + backward)
+TRAIN_KERNEL_D_KV = (64, 128, 256)  # t5_attention_train (forward with lse + backward)
 _TILES = {64: (Q_TILE, KV_TILE), 128: (Q_TILE, KV_TILE), 256: (128, 32)}   # trlx_t5_attention_tiles_d
+_BWD_TILES = {64: (BWD_DQ_Q_TILE, BWD_DQ_KV_TILE, BWD_DKV_K_TILE, BWD_DKV_Q_TILE),
+              128: (BWD_DQ_Q_TILE, BWD_DQ_KV_TILE, BWD_DKV_K_TILE, BWD_DKV_Q_TILE),
+              256: (128, 32, 64, 32)}                                       # trlx_t5_attention_bwd_tiles_d
 
 
 def tiles(d_kv):
@@ -60,6 +66,15 @@ def tiles(d_kv):
     if d_kv not in _TILES:
         raise ValueError(f"no t5_attention kernel for d_kv {d_kv} (kernels: {KERNEL_D_KV})")
     return _TILES[d_kv]
+
+
+def bwd_tiles(d_kv):
+    """(dq: query rows per workgroup, keys per LDS tile; dk / dv: keys per workgroup, query rows per
+    LDS tile) of the backward kernels that serve `d_kv`; ValueError for a d_kv without a backward.
+    What trlx_t5_attention_bwd_tiles_d reports.  `t5_attention_train.tiles` is this function."""
+    if d_kv not in _BWD_TILES:
+        raise ValueError(f"no t5_attention_train kernel for d_kv {d_kv} (kernels: {TRAIN_KERNEL_D_KV})")
+    return _BWD_TILES[d_kv]
 
 
 def t5_relative_bias_buckets(Tq, S, bidirectional, num_buckets=32, max_distance=128, device=None):
@@ -307,9 +322,8 @@ def t5_attention_train(q, k, v, *, bias=None, key_mask=None, causal=False, n_hea
     (trlx_t5_attention_bwd: dq, dk, dv bit-reproducible, the bias gradient summed with fp32 atomics
     and not).  The incoming gradient is read in place when it meets the stride rules, else copied
     once.  No double backward.  Under torch.no_grad(), or with nothing that requires grad, this is
-    `t5_attention`.  For other dtypes, other d_kv (256 included: the d_kv 256 kernel is forward
-    only, a backward for it is not built) or CPU tensors the same torch expressions as
-    `t5_attention`'s run under autograd; float64 operands stay in float64 throughout, softmax
+    `t5_attention`.  For other dtypes, other d_kv (not 64, 128 or 256) or CPU tensors the same torch
+    expressions as `t5_attention`'s run under autograd; float64 operands stay in float64 throughout, softmax
     included, and may come with a float64 bias table."""
     q4, k4, v4, (B, Tq, nH, d, S) = _checked(q, k, v, bias, key_mask, causal, n_heads, layout, f64_bias=True)
     needs = torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (q, k, v, bias))
@@ -333,3 +347,4 @@ t5_attention_train.DQ_Q_TILE = BWD_DQ_Q_TILE
 t5_attention_train.DQ_KV_TILE = BWD_DQ_KV_TILE
 t5_attention_train.DKV_K_TILE = BWD_DKV_K_TILE
 t5_attention_train.DKV_Q_TILE = BWD_DKV_Q_TILE
+t5_attention_train.tiles = bwd_tiles
