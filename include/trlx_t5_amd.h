@@ -1376,7 +1376,8 @@ int trlx_t5_attention_fwd_lse(const TrlxT5AttentionArgs* a, float* lse, void* st
 
 /* ---------------------------------------------------------------- T5 full-sequence attention, backward
  * The gradients of trlx_t5_attention (no dropout: the reference trains with dropout off) from
- * q, k, v, out, lse and dout, holding nothing of size Tq x S.  bf16 only, d_kv 64, 128 or 256, both
+ * q, k, v, out, lse and dout, holding nothing of size Tq x S (the ordered bias gradient's partial
+ * rows, trlx_t5_attention_bwd_ordered below, are 1 / 64 of a bf16 score tensor).  bf16 only, d_kv 64, 128 or 256, both
  * products and their transposes on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (256: kernels
  * of their own, csrc/t5_attention_bwd_d256.hip, the dk / dv one on v_mfma_f32_16x16x32_bf16 with 16
  * keys a wave; the same semantics).  With
@@ -1402,7 +1403,8 @@ int trlx_t5_attention_fwd_lse(const TrlxT5AttentionArgs* a, float* lse, void* st
  *   dbias    : fp32 [n_heads, Tq + S - 1], contiguous, or NULL (not computed, nothing paid: the
  *              bias belongs to a frozen layer).  The call zeroes it, then accumulates with LDS and
  *              global fp32 atomics: dbias is NOT bit-reproducible (dq, dk, dv are the same bits
- *              with and without it).  It may be given without bias_by_offset (the bias is 0 then).
+ *              with and without it); trlx_t5_attention_bwd_ordered, below, gives one that is.  It
+ *              may be given without bias_by_offset (the bias is 0 then).
  *   workspace : trlx_t5_attention_bwd_workspace_bytes(B, n_heads, Tq) bytes (delta, fp32
  *              [B, n_heads, Tq]; it does not grow with S), 4-byte aligned; -1 for sizes out of range.
  * Refused with TRLX_ERR_ARG before any launch, every output untouched: the forward's list (for
@@ -1452,6 +1454,31 @@ int trlx_t5_attention_bwd(const TrlxT5AttentionBwdArgs* a, void* stream);
 int64_t trlx_t5_attention_bwd_workspace_bytes(int64_t B, int64_t n_heads, int64_t Tq);
 int trlx_t5_attention_bwd_tiles(int* dq_q_tile, int* dq_kv_tile, int* dkv_k_tile, int* dkv_q_tile);
 int trlx_t5_attention_bwd_tiles_d(int64_t d_kv, int* dq_q_tile, int* dq_kv_tile, int* dkv_k_tile, int* dkv_q_tile);
+
+/* The same backward with an ORDERED bias gradient: no fp32 atomic on global memory, and no LDS atomic
+ * whose arrival order the program does not fix.  dq, dk, dv are trlx_t5_attention_bwd's bits; dbias
+ * is fixed bit for bit by (d_kv, B, Tq, S, the flags, the mask rows) and does not depend on the
+ * strides, on the run or on what dbias and the workspaces held.  In a dq workgroup every (wave,
+ * half-wave) adds its dS into an LDS ring of its own (32 lanes, 32 different offsets an instruction,
+ * a wave's LDS operations in program order); where an offset leaves the window the 8 rings are added
+ * in a fixed order and the sum is stored (a plain store) into the workgroup's own row of
+ * dbias_workspace, fp32 [B, n_heads, ceil(Tq / dq_q_tile), S + dq_q_tile - 1], at the local index
+ * key - (query - first query of the block) + dq_q_tile - 1.  Every entry of every row is stored,
+ * zeros where no live pair lies (the kernel writes them; the workspace is not cleared first).  One
+ * more launch, k_t5_attn_bwd_dbias_finish, adds the rows that hold a table entry in a fixed order
+ * (four slices of the batch; within a slice the query blocks ascending and b ascending within a
+ * block; then the slices 0..3) and stores every element of dbias: no zeroing of dbias on this route.
+ *   dbias_workspace : trlx_t5_attention_bwd_dbias_workspace_bytes(B, n_heads, d_kv, Tq, S) bytes
+ *              = 4 * B * n_heads * ceil(Tq / dq_q_tile) * (S + dq_q_tile - 1), 4-byte aligned; -1 for
+ *              sizes out of range or a d_kv without a kernel.  One row per block of 128 queries,
+ *              not per query: it is not of size Tq x S either, but (S + 127) / (64 S) of one bf16
+ *              score tensor (B 256 T5-base encoder at 512: 31 MB, where dq is 201 MB).
+ * The struct, the checks and the refusals are trlx_t5_attention_bwd's; with a dbias, a NULL, short
+ * or misaligned dbias_workspace is refused with TRLX_ERR_ARG before any launch.  With
+ * a->dbias == NULL the call is trlx_t5_attention_bwd exactly and dbias_workspace may be NULL. */
+int trlx_t5_attention_bwd_ordered(const TrlxT5AttentionBwdArgs* a, void* dbias_workspace, int64_t dbias_workspace_bytes,
+                                  void* stream);
+int64_t trlx_t5_attention_bwd_dbias_workspace_bytes(int64_t B, int64_t n_heads, int64_t d_kv, int64_t Tq, int64_t S);
 
 /* ---------------------------------------------------------------- T5 feed-forward activation
  * What sits between the projections of HF's T5LayerFF, forward and backward, one launch each:

@@ -1,5 +1,6 @@
-"""T5's full-sequence attention, forward + backward, three routes, at tools/t5_attention_bench.py's
-nine shapes, or with --set d256 at its six UL2 shapes (nH 16, d_kv 256: csrc/t5_attention_bwd_d256.hip).
+"""T5's full-sequence attention, forward + backward, three routes (four where the shape has a bias table),
+at tools/t5_attention_bench.py's nine shapes, with --set d256 at its six UL2 shapes (nH 16, d_kv 256:
+csrc/t5_attention_bwd_d256.hip), or with --set both at all of them; --bias-only keeps the shapes with a table.
 
   eager   HF's eager op sequence under autograd: matmul, position_bias = weight-table gathered to
           [1, nH, Tq, S] plus the additive finfo.min mask, fp32 softmax cast back, matmul; autograd
@@ -8,6 +9,9 @@ nine shapes, or with --set d256 at its six UL2 shapes (nH 16, d_kv 256: csrc/t5_
           grad through the table) and scale=1.0
   fused   t5_attention_train (trlx_t5_attention_fwd_lse + trlx_t5_attention_bwd, nothing of size
           Tq x S), the table a differentiable leaf too
+  fused_ordered   the same with bias_grad="ordered" (trlx_t5_attention_bwd_ordered: the bias gradient without
+          atomics, bit-reproducible), on the shapes with a table; "ordered_vs_atomic" is its median over
+          fused's, the yardstick being the atomic route of the same library in the same process
 Each timed call is one forward and one backward from a fixed dO, giving gradients for q, k, v and
 (where the shape has a bias) the [nH, Tq + S - 1] table.  The routes run interleaved in one process
 on the same tensors, their order shuffled per repetition, timed with HIP events after warm-up;
@@ -25,7 +29,8 @@ each, TRLX_T5_AMD_LIB naming the library; the new library's median of medians ha
 earlier library's own min-max spread.  Recorded as "forward_ab".
 
 One JSON record is printed and written to --out.
-GPU-box tool:  python tools/t5_attention_bwd_bench.py [--reps N] [--out FILE] [--only NAME] [--set d256] [--forward-ab LIB]"""
+GPU-box tool:  python tools/t5_attention_bwd_bench.py [--reps N] [--out FILE] [--only NAME] [--set d256|both] [--bias-only]
+               [--forward-ab LIB]"""
 import argparse
 import json
 import os
@@ -56,7 +61,7 @@ def _load():
 
 def summary(ms):
     s = sorted(ms)
-    return {"median_ms": round(s[len(s) // 2], 4), "min_ms": round(s[0], 4), "n": len(s)}
+    return {"median_ms": round(s[len(s) // 2], 4), "min_ms": round(s[0], 4), "max_ms": round(s[-1], 4), "n": len(s)}
 
 
 def fastest(ms):
@@ -117,7 +122,13 @@ def bench(torch, P, fb, mode, B, nH, d, Tq, S, padded, dev, reps, warmup, stream
         out = P.t5_attention_train(q, k, v, bias=table, key_mask=mask, causal=causal, n_heads=nH)
         keep["fused"] = torch.autograd.grad(out, leaves, dout)
 
+    def fused_ordered():
+        out = P.t5_attention_train(q, k, v, bias=table, key_mask=mask, causal=causal, n_heads=nH, bias_grad="ordered")
+        keep["fused_ordered"] = torch.autograd.grad(out, leaves, dout)
+
     fns = {"eager": eager, "sdpa": sdpa, "fused": fused}
+    if table is not None:
+        fns["fused_ordered"] = fused_ordered
     ms = {n: summary(t) for n, t in fb.interleaved(fns, reps, warmup, stream, rng).items()}
     pairs = Tq * (Tq + 1) // 2 * B if causal else int(live.sum()) * Tq
     fwd_flop = 4 * nH * d * pairs
@@ -131,6 +142,10 @@ def bench(torch, P, fb, mode, B, nH, d, Tq, S, padded, dev, reps, warmup, stream
     for other in ("eager", "sdpa"):
         rec[f"max_abs_diff_fused_vs_{other}"] = {n: float((a.float() - b.float()).abs().max())
                                                  for n, a, b in zip(names, keep["fused"], keep[other])}
+    if table is not None:
+        rec["ordered_vs_atomic"] = round(ms["fused_ordered"]["median_ms"] / ms["fused"]["median_ms"], 3)
+        rec["max_abs_diff_ordered_vs_fused"] = {n: float((a.float() - b.float()).abs().max())
+                                                for n, a, b in zip(names, keep["fused_ordered"], keep["fused"])}
     keep.clear()
     for n, fn in fns.items():                                                            # peak memory, one call each
         torch.cuda.synchronize()
@@ -146,6 +161,8 @@ def bench(torch, P, fb, mode, B, nH, d, Tq, S, padded, dev, reps, warmup, stream
 
 
 def shapes_of(fb, which):
+    if which == "both":
+        return {**fb.SHAPES, **fb.SHAPES_D256}
     return fb.SHAPES_D256 if which == "d256" else fb.SHAPES
 
 
@@ -196,7 +213,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None, help="one shape's name")
-    ap.add_argument("--set", default="default", choices=("default", "d256"), help="d256: the UL2-like shapes")
+    ap.add_argument("--set", default="default", choices=("default", "d256", "both"), help="d256: the UL2-like shapes")
+    ap.add_argument("--bias-only", action="store_true", help="only the shapes with a bias table (where dbias is paid)")
     ap.add_argument("--forward-ab", default=None, metavar="PARENT_LIB")
     ap.add_argument("--forward-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -204,7 +222,8 @@ def main():
     if args.forward_child:
         return forward_child(args.reps, args.warmup, args.set)
     # the A/B's children come first: this process has not opened the GPU yet
-    ab = forward_ab(args.forward_ab, args.reps, args.warmup, args.set) if args.forward_ab else None
+    ab = forward_ab(args.forward_ab, args.reps, args.warmup, "default" if args.set == "both" else args.set) \
+        if args.forward_ab else None
     torch, P = _load()
     import t5_attention_bench as fb
     TR = P.t5_attention_train
@@ -217,7 +236,7 @@ def main():
            "flop_model": "flop = 3.5 x forward_flop; forward_flop = 4 nH d sum_b Tq S_live(b) (causal: j <= i)",
            "shapes": {}}
     for name, shape in shapes_of(fb, args.set).items():
-        if args.only and name != args.only:
+        if (args.only and name != args.only) or (args.bias_only and shape[0] == "cross"):
             continue
         rec["shapes"][name] = bench(torch, P, fb, *shape, dev, args.reps, args.warmup, stream, rng)
         torch.cuda.empty_cache()

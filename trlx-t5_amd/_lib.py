@@ -428,6 +428,8 @@ SIGNATURES = {
     "trlx_t5_attention_fwd_lse": (_c_int, [ctypes.POINTER(T5AttentionArgs), _c_vp, _c_vp]),
     "trlx_t5_attention_bwd": (_c_int, [ctypes.POINTER(T5AttentionBwdArgs), _c_vp]),
     "trlx_t5_attention_bwd_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "trlx_t5_attention_bwd_ordered": (_c_int, [ctypes.POINTER(T5AttentionBwdArgs), _c_vp, _c_i64, _c_vp]),
+    "trlx_t5_attention_bwd_dbias_workspace_bytes": (_c_i64, [_c_i64] * 5),
     "trlx_t5_attention_bwd_tiles": (_c_int, [ctypes.POINTER(_c_int)] * 4),
     "trlx_t5_attention_bwd_tiles_d": (_c_int, [_c_i64] + [ctypes.POINTER(_c_int)] * 4),
     "trlx_t5_ff_act_fwd": (_c_int, [ctypes.POINTER(T5FfActArgs), _c_vp]),

@@ -78,19 +78,20 @@ struct TbArgs {
     float* delta;          // [B, nH, Tq]
     const float* bias;     // [nH, Tq + S - 1] or NULL
     const int64_t* mask;   // [B, S] or NULL
-    float* dbias;          // [nH, Tq + S - 1] or NULL
+    float* dbias;          // [nH, Tq + S - 1] or NULL; the ordered dq forms: [B, nH, nblk, S + 127] partial rows
     int64_t q_sb, q_st, q_sh, k_sb, k_st, k_sh, v_sb, v_st, v_sh, o_sb, o_st, o_sh, do_sb, do_st, do_sh;
     int64_t dq_sb, dq_st, dq_sh, dk_sb, dk_st, dk_sh, dv_sb, dv_st, dv_sh;
     int nH, Tq, S, nblk;
 };
 
 // d_kv 256 backward (t5_attention_bwd_d256.hip): its tiles, and the dk / dv and dq launches on
-// arguments trlx_t5_attention_bwd has checked, after its delta launch and its zeroing of dbias
+// arguments trlx_t5_attention_bwd has checked, after its delta launch and its zeroing of dbias.
+// `ordered`: k.dbias is the partial rows of the ordered bias gradient, not the table's gradient.
 constexpr int kTb256DqQTile = 128;   // dq: query rows per workgroup (32 per wave)
 constexpr int kTb256DqKVTile = 32;   // dq: keys per LDS tile
 constexpr int kTb256KvKTile = 64;    // dkv: keys per workgroup (16 per wave)
 constexpr int kTb256KvQTile = 32;    // dkv: query rows per LDS tile
-int tb_launch_d256(TbArgs k, int flags, unsigned grid_k, unsigned grid_q, void* stream);
+int tb_launch_d256(TbArgs k, int flags, unsigned grid_k, unsigned grid_q, bool ordered, void* stream);
 
 static inline bool ta_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

@@ -36,6 +36,11 @@
 // dbias.  Each dq workgroup adds its dS into an LDS ring of kTbRing offsets (LDS fp32 atomics); the
 // 64 offsets that leave the window when the walk moves on one tile are flushed to the
 // [nH, Tq + S - 1] buffer with global fp32 atomics.  Not bit-reproducible.
+// Ordered dbias (trlx_t5_attention_bwd_ordered; the ORD forms of the dq kernels): a ring per (wave,
+// half-wave), summed in program order; the rings are added in a fixed order into the workgroup's own row
+// of a [B, nH, ceil(Tq / 128), S + 127] workspace with plain stores, and k_t5_attn_bwd_dbias_finish adds
+// the rows in a fixed order.  No global atomic; bits fixed by (d_kv, B, Tq, S, the flags, the mask rows).
+// That workspace is 1 / 64 of a bf16 score tensor: the one thing here that grows with Tq x S / 128.
 #include <climits>
 
 #include "t5_attention.h"
@@ -49,6 +54,7 @@ constexpr int kTbKvKTile = 128;   // dkv: keys per workgroup (32 per wave)
 constexpr int kTbKvQTile = 64;    // dkv: query rows per LDS tile
 constexpr int kTbWin = 192;       // offsets (key - query) a 128 x 64 tile pair can meet, rounded up
 constexpr int kTbRing = 256;      // dbias ring in LDS (a power of two >= kTbWin)
+constexpr int kTbRings = 2 * kTbThreads / kWave;   // ordered dbias: a ring per (wave, half-wave)
 constexpr float kTbL2E = 1.4426950408889634f;
 
 __device__ __forceinline__ ta_bf16x8 tb_zero_frag() { return __builtin_bit_cast(ta_bf16x8, vec4u_make(0, 0, 0, 0)); }
@@ -309,8 +315,19 @@ __global__ __launch_bounds__(kTbThreads, DKV == 64 ? 2 : 1) void k_t5_attn_bwd_d
 }
 
 // ------------------------------------------------------------------ dQ (and dbias)
-template <int DKV, int FLAGS, bool DBIAS>
+// ORD (with DBIAS): the ordered bias gradient.  Every (wave, half-wave) adds into a ring of its own,
+// s_db[(2 wave + hh) * kTbRing ...]: within one half-wave the 32 lanes of an instruction hold 32
+// different queries against one key, so 32 different offsets, and a wave's LDS operations retire in
+// program order, so each ring slot is summed in an order the program fixes.  Where the atomic form
+// hands an offset to the global buffer, this one sums the 8 rings (wave 0 half 0, wave 0 half 1, ...)
+// and plain-stores the sum into the workgroup's own row of a.dbias, here the partial rows
+// [B, nH, nblk, S + kTbDqQTile - 1], at the local index key - (query - q0) + kTbDqQTile - 1.  The
+// entries no flush reaches (dead tiles that were never opened, keys past the causal range, a walk of
+// no tile at all) get zeros from `fill`, so every entry of the row is stored exactly once and none
+// depends on what the workspace held; k_t5_attn_bwd_dbias_finish sums the rows.
+template <int DKV, int FLAGS, bool DBIAS, bool ORD = false>
 __global__ __launch_bounds__(kTbThreads, DKV == 64 ? 2 : 1) void k_t5_attn_bwd_dq(const TbArgs a) {
+    static_assert(DBIAS || !ORD, "the ordered form is a dbias form");
     constexpr bool BIAS = FLAGS & kTaBias, MASK = FLAGS & kTaMask, CAUSAL = FLAGS & kTaCausal;
     constexpr int CPR = DKV / 8;                            // 16-byte chunks per row
     constexpr int NC = kTbDqKVTile * CPR / kTbThreads;      // chunks per thread and operand
@@ -324,7 +341,7 @@ __global__ __launch_bounds__(kTbThreads, DKV == 64 ? 2 : 1) void k_t5_attn_bwd_d
                   "dbias ring");
     __shared__ __attribute__((aligned(16))) unsigned char smem[kBytes];
     __shared__ float s_bias[kTbWin];
-    __shared__ float s_db[DBIAS ? kTbRing : 1];
+    __shared__ float s_db[DBIAS ? (ORD ? kTbRings : 1) * kTbRing : 1];
     __shared__ int s_lohi[2];
     unsigned char* sK = smem;
     unsigned char* sV = smem + kTbDqKVTile * LS;
@@ -343,6 +360,10 @@ __global__ __launch_bounds__(kTbThreads, DKV == 64 ? 2 : 1) void k_t5_attn_bwd_d
     const bool wave_live = qw0 < a.Tq;
 
     if (DBIAS) s_db[tid] = 0.f;            // kTbRing == kTbThreads; the first tile's barrier orders it
+    if (ORD) {
+#pragma unroll
+        for (int r = 1; r < kTbRings; ++r) s_db[r * kTbRing + tid] = 0.f;
+    }
 
     // Q^T and dO^T fragments: lane (c, hh) holds row qg, d = 16 kk + 8 hh + 0..7; rows past Tq are clamped
     ta_bf16x8 qf[KK], gf[KK];
@@ -362,7 +383,10 @@ __global__ __launch_bounds__(kTbThreads, DKV == 64 ? 2 : 1) void k_t5_attn_bwd_d
     const uint16_t* kbase = a.k + int64_t(b) * a.k_sb + int64_t(h) * a.k_sh;
     const uint16_t* vbase = a.v + int64_t(b) * a.v_sb + int64_t(h) * a.v_sh;
     const float* brow = BIAS ? a.bias + int64_t(h) * (a.Tq + a.S - 1) : nullptr;
-    float* dbrow = DBIAS ? a.dbias + int64_t(h) * (a.Tq + a.S - 1) : nullptr;
+    const int prl = a.S + kTbDqQTile - 1;   // ORD: entries of a partial row
+    float* dbrow = !DBIAS ? nullptr
+                   : ORD  ? a.dbias + ((int64_t(b) * a.nH + h) * a.nblk + qb) * prl
+                          : a.dbias + int64_t(h) * (a.Tq + a.S - 1);
     const int64_t* mrow = MASK ? a.mask + int64_t(b) * a.S : nullptr;
 
     // keys [0, kend) can matter to this workgroup; the tiles walked are [t_lo, t_hi)
@@ -422,15 +446,30 @@ __global__ __launch_bounds__(kTbThreads, DKV == 64 ? 2 : 1) void k_t5_attn_bwd_d
             br = idx >= 0 && idx < a.Tq + a.S - 1 ? brow[idx] : 0.f;
         }
     };
-    // dbias: ring slot of table index idx, and the hand-over of one index to the global buffer
-    int ring0 = 0;              // table index of the current tile's window entry 0
+    // dbias: ring slot of table index idx (ORD: of the row's local index), and the hand-over of one
+    // index to the global buffer
+    int ring0 = 0;              // table (ORD: local) index of the current tile's window entry 0
     bool ring_open = false;
     auto flush = [&](int idx) __attribute__((always_inline)) {
         float* slot = &s_db[idx & (kTbRing - 1)];
+        if (ORD) {
+            float x = 0.f;
+#pragma unroll
+            for (int r = 0; r < kTbRings; ++r) {
+                x += slot[r * kTbRing];
+                slot[r * kTbRing] = 0.f;
+            }
+            if (idx < prl) dbrow[idx] = x;   // idx >= 0: a window starts at its tile's first key
+            return;
+        }
         const float x = *slot;
         *slot = 0.f;
         if (!(x == 0.f) && idx >= 0 && idx < a.Tq + a.S - 1) atomicAdd(dbrow + idx, x);
     };
+    auto fill = [&](int from, int upto) __attribute__((always_inline)) {   // ORD: zeros for [from, upto)
+        for (int j = from + tid; j < upto; j += kTbThreads) dbrow[j] = 0.f;
+    };
+    const int ring = (2 * wave + hh) * kTbRing;   // ORD: this half-wave's ring
 
     ta_f32x16 dQ[DB];
 #pragma unroll
@@ -439,6 +478,7 @@ __global__ __launch_bounds__(kTbThreads, DKV == 64 ? 2 : 1) void k_t5_attn_bwd_d
         for (int i = 0; i < 16; ++i) dQ[db][i] = 0.f;
 
     if (t_lo < t_hi) prefetch(t_lo);
+    if (ORD) fill(0, t_lo < t_hi ? t_lo * kTbDqKVTile : 0);   // below the first window: zeros
 #pragma unroll 1
     for (int t = t_lo; t < t_hi; ++t) {
         const unsigned long long lm = lmN;
@@ -452,12 +492,17 @@ __global__ __launch_bounds__(kTbThreads, DKV == 64 ? 2 : 1) void k_t5_attn_bwd_d
                 *reinterpret_cast<vec4u*>(sV + row * LS + ch * 16) = vr[n];
             }
             if (BIAS && tid < kTbWin) s_bias[tid] = br;
-            if (DBIAS) {   // the offsets below the new window are complete: hand them over
+            if (DBIAS && !ORD) {   // the offsets below the new window are complete: hand them over
                 const int nb = k0 - q0 - (kTbDqQTile - 1) + (a.Tq - 1);
                 if (ring_open && tid < kTbWin && ring0 + tid < nb) flush(ring0 + tid);
                 ring0 = nb;
                 ring_open = true;
             }
+        }
+        if (ORD) {   // at every tile, a dead one too: the windows follow each other and leave no gap in the row
+            if (ring_open && tid < kTbDqKVTile) flush(ring0 + tid);
+            ring0 = k0;
+            ring_open = true;
         }
         __syncthreads();
         if (t + 1 < t_hi) prefetch(t + 1);
@@ -499,7 +544,7 @@ __global__ __launch_bounds__(kTbThreads, DKV == 64 ? 2 : 1) void k_t5_attn_bwd_d
                     const float p = dead ? 0.f : exp2_fast((s - lse) * kTbL2E);
                     const float ds = dead ? 0.f : p * (dacc[kb][i] - delta);
                     if (DBIAS) {
-                        if (!dead) atomicAdd(&s_db[(ring0 + e) & (kTbRing - 1)], ds);
+                        if (!dead) atomicAdd(&s_db[(ORD ? ring : 0) | ((ring0 + e) & (kTbRing - 1))], ds);
                     }
                     sacc[kb][i] = ds;
                 }
@@ -524,6 +569,7 @@ __global__ __launch_bounds__(kTbThreads, DKV == 64 ? 2 : 1) void k_t5_attn_bwd_d
     }
     if (DBIAS) {
         if (ring_open && tid < kTbWin) flush(ring0 + tid);
+        if (ORD) fill(ring_open ? ring0 + kTbWin : 0, prl);   // past the last window, or a walk of no tile: zeros
     }
 
     // round once, stage the wave's 32 rows in LDS and store whole rows
@@ -549,6 +595,47 @@ __global__ __launch_bounds__(kTbThreads, DKV == 64 ? 2 : 1) void k_t5_attn_bwd_d
     }
 }
 
+// ------------------------------------------------------------------ ordered dbias: the sum of the partial rows
+// dbias[h, idx] = sum over b and the query blocks qb whose row holds idx of part[b, h, qb, idx - base(qb)],
+// base(qb) = Tq - kTbDqQTile - kTbDqQTile * qb (the table index of the row's entry 0).  A workgroup is 64
+// consecutive idx of one head x kTbFinSlices slices of the batch: slice s adds, from +0, the query blocks
+// ascending and, within one block, b = s, s + 4, ... ascending; the slices' sums are added s = 0, 1, 2, 3
+// through LDS (a fixed two-level tree: one level would leave the chip idle at nH (Tq + S - 1) outputs).  The
+// order depends on (B, Tq, S) alone.  A wave reads 64 consecutive floats of one row per load.  Every
+// element of dbias is stored, so the table needs no zeroing on this route.
+constexpr int kTbFinSlices = kTbThreads / kWave;
+__global__ __launch_bounds__(kTbThreads) void k_t5_attn_bwd_dbias_finish(const float* __restrict__ part,
+                                                                        float* __restrict__ dbias, const int B,
+                                                                        const int nH, const int Tq, const int S,
+                                                                        const int nqb, const int nib) {
+    __shared__ float s_sum[kTbFinSlices][kWave];
+    const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int h = blockIdx.x / nib;
+    const int idx = (blockIdx.x % nib) * kWave + lane;
+    const int len = Tq + S - 1, prl = S + kTbDqQTile - 1;
+    float acc = 0.f;
+    if (idx < len) {
+        // the rows that hold idx: 0 <= idx - base(qb) < prl
+        const int l0 = idx - Tq + kTbDqQTile;                                  // the local index in block 0's row
+        const int qlo = l0 >= 0 ? 0 : (-l0 + kTbDqQTile - 1) / kTbDqQTile;
+        const int qhi = min(nqb, l0 >= prl ? 0 : (prl - 1 - l0) / kTbDqQTile + 1);
+        const int64_t bs = int64_t(nH) * nqb * prl;                            // from one batch row to the next
+        for (int qb = qlo; qb < qhi; ++qb) {
+            const float* p = part + (int64_t(h) * nqb + qb) * prl + l0 + qb * kTbDqQTile;
+#pragma unroll 8
+            for (int b = sl; b < B; b += kTbFinSlices) acc += p[b * bs];      // the loads of 8 rows in flight, added in order
+        }
+    }
+    s_sum[sl][lane] = acc;
+    __syncthreads();
+    if (sl == 0 && idx < len) {
+        float x = s_sum[0][lane];
+#pragma unroll
+        for (int s = 1; s < kTbFinSlices; ++s) x += s_sum[s][lane];
+        dbias[int64_t(h) * len + idx] = x;
+    }
+}
+
 typedef void (*tb_kernel_t)(const TbArgs);
 template <int DKV>
 static tb_kernel_t tb_pick_dkv(int flags) {
@@ -563,17 +650,17 @@ static tb_kernel_t tb_pick_dkv(int flags) {
         default: return k_t5_attn_bwd_dkv<DKV, 7>;
     }
 }
-template <int DKV, bool DBIAS>
+template <int DKV, bool DBIAS, bool ORD = false>
 static tb_kernel_t tb_pick_dq(int flags) {
     switch (flags) {
-        case 0: return k_t5_attn_bwd_dq<DKV, 0, DBIAS>;
-        case 1: return k_t5_attn_bwd_dq<DKV, 1, DBIAS>;
-        case 2: return k_t5_attn_bwd_dq<DKV, 2, DBIAS>;
-        case 3: return k_t5_attn_bwd_dq<DKV, 3, DBIAS>;
-        case 4: return k_t5_attn_bwd_dq<DKV, 4, DBIAS>;
-        case 5: return k_t5_attn_bwd_dq<DKV, 5, DBIAS>;
-        case 6: return k_t5_attn_bwd_dq<DKV, 6, DBIAS>;
-        default: return k_t5_attn_bwd_dq<DKV, 7, DBIAS>;
+        case 0: return k_t5_attn_bwd_dq<DKV, 0, DBIAS, ORD>;
+        case 1: return k_t5_attn_bwd_dq<DKV, 1, DBIAS, ORD>;
+        case 2: return k_t5_attn_bwd_dq<DKV, 2, DBIAS, ORD>;
+        case 3: return k_t5_attn_bwd_dq<DKV, 3, DBIAS, ORD>;
+        case 4: return k_t5_attn_bwd_dq<DKV, 4, DBIAS, ORD>;
+        case 5: return k_t5_attn_bwd_dq<DKV, 5, DBIAS, ORD>;
+        case 6: return k_t5_attn_bwd_dq<DKV, 6, DBIAS, ORD>;
+        default: return k_t5_attn_bwd_dq<DKV, 7, DBIAS, ORD>;
     }
 }
 
@@ -594,6 +681,9 @@ static bool tb_sizes_ok(int64_t B, int64_t nH, int64_t Tq) {
     const int64_t lim = int64_t(1) << 30;
     return B >= 1 && nH >= 1 && Tq >= 1 && B <= lim && nH <= lim && Tq <= lim;
 }
+
+static int tb_backward(const TrlxT5AttentionBwdArgs* a, bool ordered, void* dbias_workspace, int64_t dbias_workspace_bytes,
+                       void* stream);
 
 }  // namespace trlx
 
@@ -626,8 +716,32 @@ extern "C" int64_t trlx_t5_attention_bwd_workspace_bytes(int64_t B, int64_t n_he
     return (4 * n + 255) / 256 * 256;   // delta, fp32 [B, nH, Tq]
 }
 
+// the partial rows of the ordered bias gradient: fp32 [B, nH, ceil(Tq / 128), S + 127] (every d_kv's dq
+// kernel takes 128 queries a workgroup)
+extern "C" int64_t trlx_t5_attention_bwd_dbias_workspace_bytes(int64_t B, int64_t n_heads, int64_t d_kv, int64_t Tq, int64_t S) {
+    static_assert(kTb256DqQTile == kTbDqQTile, "one partial-row geometry for every d_kv");
+    if (!(d_kv == 64 || d_kv == 128 || d_kv == 256) || !tb_sizes_ok(B, n_heads, Tq) || S < 1 || S > (int64_t(1) << 30)) return -1;
+    int64_t n;
+    if (__builtin_mul_overflow(B, n_heads, &n) || __builtin_mul_overflow(n, (Tq + kTbDqQTile - 1) / kTbDqQTile, &n) ||
+        __builtin_mul_overflow(n, S + kTbDqQTile - 1, &n) || n > (int64_t(1) << 58))
+        return -1;
+    return 4 * n;
+}
+
 extern "C" int trlx_t5_attention_bwd(const TrlxT5AttentionBwdArgs* a, void* stream) {
+    return tb_backward(a, false, nullptr, 0, stream);
+}
+
+extern "C" int trlx_t5_attention_bwd_ordered(const TrlxT5AttentionBwdArgs* a, void* dbias_workspace,
+                                             int64_t dbias_workspace_bytes, void* stream) {
+    return tb_backward(a, true, dbias_workspace, dbias_workspace_bytes, stream);
+}
+
+// Both entries: the checks, then delta, dk / dv, dq and, on the ordered route with a dbias, the finish.
+int trlx::tb_backward(const TrlxT5AttentionBwdArgs* a, bool ordered, void* dbias_workspace,
+                             int64_t dbias_workspace_bytes, void* stream) {
     TRLX_REQUIRE(a, TRLX_ERR_ARG, "t5 attention bwd: NULL arguments");
+    ordered = ordered && a->dbias;   // without a dbias the ordered entry is the other one exactly
     TRLX_REQUIRE(a->dtype == TRLX_BF16, TRLX_ERR_ARG, "t5 attention bwd: dtype %d (bf16 only)", a->dtype);
     TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128 || a->d_kv == 256, TRLX_ERR_ARG, "t5 attention bwd: d_kv %lld (64, 128, 256)",
                  (long long)a->d_kv);
@@ -709,6 +823,17 @@ extern "C" int trlx_t5_attention_bwd(const TrlxT5AttentionBwdArgs* a, void* stre
                      a->workspace_bytes >= need,
                  TRLX_ERR_ARG, "t5 attention bwd: workspace of %lld bytes, %lld needed (4-byte aligned)",
                  (long long)a->workspace_bytes, (long long)need);
+    const int64_t nib = (a->Tq + a->S - 1 + kWave - 1) / kWave;   // the finish: blocks of 64 table entries a head
+    if (ordered) {
+        const int64_t dneed = trlx_t5_attention_bwd_dbias_workspace_bytes(a->B, a->n_heads, a->d_kv, a->Tq, a->S);
+        TRLX_REQUIRE(dneed > 0 && dbias_workspace && (reinterpret_cast<uintptr_t>(dbias_workspace) & 3u) == 0 &&
+                         dbias_workspace_bytes >= dneed,
+                     TRLX_ERR_ARG, "t5 attention bwd: dbias workspace of %lld bytes, %lld needed (4-byte aligned)",
+                     (long long)dbias_workspace_bytes, (long long)dneed);
+        TRLX_REQUIRE(a->n_heads * nib <= 0x7fffffffLL, TRLX_ERR_ARG,
+                     "t5 attention bwd: heads * ceil((Tq + S - 1) / 64) = %lld * %lld exceeds the grid", (long long)a->n_heads,
+                     (long long)nib);
+    }
 
     TbArgs k = {};
     k.q = static_cast<const uint16_t*>(a->q);
@@ -738,7 +863,8 @@ extern "C" int trlx_t5_attention_bwd(const TrlxT5AttentionBwdArgs* a, void* stre
     k.Tq = int(a->Tq);
     k.S = int(a->S);
     hipStream_t st = (hipStream_t)stream;
-    if (a->dbias) {
+    if (ordered) k.dbias = static_cast<float*>(dbias_workspace);   // the dq kernel stores its partial rows there
+    if (a->dbias && !ordered) {
         const hipError_t e = hipMemsetAsync(a->dbias, 0, size_t(a->n_heads) * size_t(a->Tq + a->S - 1) * 4, st);
         TRLX_REQUIRE(e == hipSuccess, TRLX_ERR_LAUNCH,"t5 attention bwd: zeroing dbias: %s", hipGetErrorString(e));
     }
@@ -749,17 +875,26 @@ extern "C" int trlx_t5_attention_bwd(const TrlxT5AttentionBwdArgs* a, void* stre
         const int rc = check_launch("k_t5_attn_bwd_delta");
         if (rc != TRLX_OK) return rc;
     }
-    if (big) return tb_launch_d256(k, flags, unsigned(grid_k), unsigned(grid_q), stream);
-    {
+    if (big) {
+        const int rc = tb_launch_d256(k, flags, unsigned(grid_k), unsigned(grid_q), ordered, stream);
+        if (rc != TRLX_OK || !ordered) return rc;
+    } else {
         k.nblk = int(nkb);
         tb_kernel_t fn = a->d_kv == 64 ? tb_pick_dkv<64>(flags) : tb_pick_dkv<128>(flags);
         hipLaunchKernelGGL(fn, dim3(unsigned(grid_k)), dim3(kTbThreads), 0, st, k);
         const int rc = check_launch("k_t5_attn_bwd_dkv");
         if (rc != TRLX_OK) return rc;
     }
-    k.nblk = int(nqb);
-    tb_kernel_t fn = a->dbias ? (a->d_kv == 64 ? tb_pick_dq<64, true>(flags) : tb_pick_dq<128, true>(flags))
-                              : (a->d_kv == 64 ? tb_pick_dq<64, false>(flags) : tb_pick_dq<128, false>(flags));
-    hipLaunchKernelGGL(fn, dim3(unsigned(grid_q)), dim3(kTbThreads), 0, st, k);
-    return check_launch("k_t5_attn_bwd_dq");
+    if (!big) {
+        k.nblk = int(nqb);
+        tb_kernel_t fn = !a->dbias ? (a->d_kv == 64 ? tb_pick_dq<64, false>(flags) : tb_pick_dq<128, false>(flags))
+                         : ordered ? (a->d_kv == 64 ? tb_pick_dq<64, true, true>(flags) : tb_pick_dq<128, true, true>(flags))
+                                   : (a->d_kv == 64 ? tb_pick_dq<64, true>(flags) : tb_pick_dq<128, true>(flags));
+        hipLaunchKernelGGL(fn, dim3(unsigned(grid_q)), dim3(kTbThreads), 0, st, k);
+        const int rc = check_launch("k_t5_attn_bwd_dq");
+        if (rc != TRLX_OK || !ordered) return rc;
+    }
+    hipLaunchKernelGGL(k_t5_attn_bwd_dbias_finish, dim3(unsigned(a->n_heads * nib)), dim3(kTbThreads), 0, st,
+                       static_cast<const float*>(dbias_workspace), a->dbias, int(a->B), k.nH, k.Tq, k.S, int(nqb), int(nib));
+    return check_launch("k_t5_attn_bwd_dbias_finish");
 }

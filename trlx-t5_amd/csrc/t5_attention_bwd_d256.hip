@@ -14,6 +14,7 @@
 // k-steps the delta kernel takes, so a query with one live key has dS = 0 exactly.  dQ leaves through
 // the tiles' LDS in two passes of 128 columns.  DBIAS: the LDS ring of 256 offsets; a 128 x 32 tile
 // pair spans 160, the 32 that leave the window per step go out with global fp32 atomics.
+// ORD: the ordered form of t5_attention_bwd.hip (a ring per half-wave, partial rows, no global atomic).
 //
 // dk / dv.  k_t5_attn_bwd_dkv_d256: one workgroup = 4 waves = 64 keys of one (batch row, head), a wave
 // owns 16 keys, on v_mfma_f32_16x16x32_bf16: at 32 keys a wave dK^T and dV^T alone are 256
@@ -43,6 +44,7 @@ namespace trlx {
 constexpr int kT2Threads = 256;
 constexpr int kT2D = 256;
 constexpr int kT2Ring = 256;      // dbias ring in LDS (a power of two)
+constexpr int kT2Rings = 2 * kT2Threads / kWave;   // ordered dbias: a ring per (wave, half-wave)
 constexpr float kT2L2E = 1.4426950408889634f;
 
 typedef float tb_f32x4 __attribute__((ext_vector_type(4)));
@@ -276,8 +278,16 @@ __global__ __launch_bounds__(kT2Threads, 1) void k_t5_attn_bwd_dkv_d256(const Tb
 }
 
 // ------------------------------------------------------------------ dQ (and dbias)
-template <int FLAGS, bool DBIAS>
+// ORD (with DBIAS): the ordered bias gradient, as in k_t5_attn_bwd_dq.  The lane layout of the dS^T
+// tile is that kernel's at one 32-key block a tile: lane (c, hh) holds query qw0 + c and, per
+// register, key kl0 + 4 hh, so the 32 lanes of a half-wave meet 32 different offsets in one
+// instruction, and a ring per (wave, half-wave) is summed in program order.  The window is BW = 160
+// offsets and moves by 32; the hand-over sums the 8 rings in a fixed order into the workgroup's own
+// partial row (a.dbias = [B, nH, nblk, S + QT - 1]) and `fill` stores the zeros of what no window
+// reached: every entry of the row is stored exactly once.
+template <int FLAGS, bool DBIAS, bool ORD = false>
 __global__ __launch_bounds__(kT2Threads, 1) void k_t5_attn_bwd_dq_d256(const TbArgs a) {
+    static_assert(DBIAS || !ORD, "the ordered form is a dbias form");
     constexpr bool BIAS = FLAGS & kTaBias, MASK = FLAGS & kTaMask, CAUSAL = FLAGS & kTaCausal;
     constexpr int QT = kTb256DqQTile, KVT = kTb256DqKVTile;
     constexpr int CPR = kT2D / 8;                           // 16-byte chunks per row
@@ -296,7 +306,7 @@ __global__ __launch_bounds__(kT2Threads, 1) void k_t5_attn_bwd_dq_d256(const TbA
     static_assert(BW + KVT <= kT2Ring && (kT2Ring & (kT2Ring - 1)) == 0 && kT2Ring == kT2Threads && BW <= kT2Threads, "dbias ring");
     __shared__ __attribute__((aligned(16))) unsigned char smem[kBytes];
     __shared__ float s_bias[BW];
-    __shared__ float s_db[DBIAS ? kT2Ring : 1];
+    __shared__ float s_db[DBIAS ? (ORD ? kT2Rings : 1) * kT2Ring : 1];
     __shared__ int s_lohi[2];
     unsigned char* sK = smem;
     unsigned char* sV = smem + KVT * KS;
@@ -315,6 +325,10 @@ __global__ __launch_bounds__(kT2Threads, 1) void k_t5_attn_bwd_dq_d256(const TbA
     const bool wave_live = qw0 < a.Tq;
 
     if (DBIAS) s_db[tid] = 0.f;            // kT2Ring == kT2Threads; the first tile's barrier orders it
+    if (ORD) {
+#pragma unroll
+        for (int r = 1; r < kT2Rings; ++r) s_db[r * kT2Ring + tid] = 0.f;
+    }
 
     // Q^T and dO^T fragments: lane (c, hh) holds row qg, d = 16 kk + 8 hh + 0..7; rows past Tq are clamped
     ta_bf16x8 qf[KK], gf[KK];
@@ -334,7 +348,10 @@ __global__ __launch_bounds__(kT2Threads, 1) void k_t5_attn_bwd_dq_d256(const TbA
     const uint16_t* kbase = a.k + int64_t(b) * a.k_sb + int64_t(h) * a.k_sh;
     const uint16_t* vbase = a.v + int64_t(b) * a.v_sb + int64_t(h) * a.v_sh;
     const float* brow = BIAS ? a.bias + int64_t(h) * (a.Tq + a.S - 1) : nullptr;
-    float* dbrow = DBIAS ? a.dbias + int64_t(h) * (a.Tq + a.S - 1) : nullptr;
+    const int prl = a.S + QT - 1;          // ORD: entries of a partial row
+    float* dbrow = !DBIAS ? nullptr
+                   : ORD  ? a.dbias + ((int64_t(b) * a.nH + h) * a.nblk + qb) * prl
+                          : a.dbias + int64_t(h) * (a.Tq + a.S - 1);
     const int64_t* mrow = MASK ? a.mask + int64_t(b) * a.S : nullptr;
 
     // keys [0, kend) can matter to this workgroup; the tiles walked are [t_lo, t_hi)
@@ -396,15 +413,30 @@ __global__ __launch_bounds__(kT2Threads, 1) void k_t5_attn_bwd_dq_d256(const TbA
             br = idx >= 0 && idx < a.Tq + a.S - 1 ? brow[idx] : 0.f;
         }
     };
-    // dbias: ring slot of table index idx, and the hand-over of one index to the global buffer
-    int ring0 = 0;              // table index of the current tile's window entry 0
+    // dbias: ring slot of table index idx (ORD: of the row's local index), and the hand-over of one
+    // index to the global buffer
+    int ring0 = 0;              // table (ORD: local) index of the current tile's window entry 0
     bool ring_open = false;
     auto flush = [&](int idx) __attribute__((always_inline)) {
         float* slot = &s_db[idx & (kT2Ring - 1)];
+        if (ORD) {
+            float x = 0.f;
+#pragma unroll 1   // rolled: eight reads in flight here spill the bias form without a mask (512 registers in use)
+            for (int r = 0; r < kT2Rings; ++r) {
+                x += slot[r * kT2Ring];
+                slot[r * kT2Ring] = 0.f;
+            }
+            if (idx < prl) dbrow[idx] = x;   // idx >= 0: a window starts at its tile's first key
+            return;
+        }
         const float x = *slot;
         *slot = 0.f;
         if (!(x == 0.f) && idx >= 0 && idx < a.Tq + a.S - 1) atomicAdd(dbrow + idx, x);
     };
+    auto fill = [&](int from, int upto) __attribute__((always_inline)) {   // ORD: zeros for [from, upto)
+        for (int j = from + tid; j < upto; j += kT2Threads) dbrow[j] = 0.f;
+    };
+    const int ring = (2 * wave + hh) * kT2Ring;   // ORD: this half-wave's ring
 
     ta_f32x16 dQ[DB];
 #pragma unroll
@@ -413,6 +445,7 @@ __global__ __launch_bounds__(kT2Threads, 1) void k_t5_attn_bwd_dq_d256(const TbA
         for (int i = 0; i < 16; ++i) dQ[db][i] = 0.f;
 
     if (t_lo < t_hi) prefetch(t_lo);
+    if (ORD) fill(0, t_lo < t_hi ? t_lo * KVT : 0);   // below the first window: zeros
 #pragma unroll 1
     for (int t = t_lo; t < t_hi; ++t) {
         const unsigned long long lm = lmN;
@@ -425,12 +458,17 @@ __global__ __launch_bounds__(kT2Threads, 1) void k_t5_attn_bwd_dq_d256(const TbA
                 *reinterpret_cast<vec4u*>(sV + row * VS + c * 16) = vr[i];
             }
             if (BIAS && tid < BW) s_bias[tid] = br;
-            if (DBIAS) {   // the offsets below the new window are complete: hand them over
+            if (DBIAS && !ORD) {   // the offsets below the new window are complete: hand them over
                 const int nb = k0 - q0 - (QT - 1) + (a.Tq - 1);
                 if (ring_open && tid < BW && ring0 + tid < nb) flush(ring0 + tid);
                 ring0 = nb;
                 ring_open = true;
             }
+        }
+        if (ORD) {   // at every tile, a dead one too: the windows follow each other and leave no gap in the row
+            if (ring_open && tid < KVT) flush(ring0 + tid);
+            ring0 = k0;
+            ring_open = true;
         }
         __syncthreads();
         if (t + 1 < t_hi) prefetch(t + 1);   // in flight under the MFMAs below
@@ -467,7 +505,7 @@ __global__ __launch_bounds__(kT2Threads, 1) void k_t5_attn_bwd_dq_d256(const TbA
                 if (CAUSAL) dead = dead || k0 + kl > qg;
                 const float p = dead ? 0.f : exp2_fast((s - lse) * kT2L2E);
                 const float ds = dead ? 0.f : p * (dacc[i] - delta);
-                if (DBIAS) atomicAdd(&s_db[(ring0 + e) & (kT2Ring - 1)], ds);   // a dead pair adds its exact zero: no branch
+                if (DBIAS) atomicAdd(&s_db[(ORD ? ring : 0) + ((ring0 + e) & (kT2Ring - 1))], ds);   // a dead pair adds its exact zero: no branch
                 sacc[i] = ds;
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -490,6 +528,7 @@ __global__ __launch_bounds__(kT2Threads, 1) void k_t5_attn_bwd_dq_d256(const TbA
     }
     if (DBIAS) {
         if (ring_open && tid < BW) flush(ring0 + tid);
+        if (ORD) fill(ring_open ? ring0 + BW : 0, prl);   // past the last window, or a walk of no tile: zeros
     }
 
     // round once, stage the wave's 32 rows in LDS (OC columns a pass) and store whole rows
@@ -533,28 +572,29 @@ static tb2_kernel_t tb2_pick_dkv(int flags) {
         default: return k_t5_attn_bwd_dkv_d256<7>;
     }
 }
-template <bool DBIAS>
+template <bool DBIAS, bool ORD = false>
 static tb2_kernel_t tb2_pick_dq(int flags) {
     switch (flags) {
-        case 0: return k_t5_attn_bwd_dq_d256<0, DBIAS>;
-        case 1: return k_t5_attn_bwd_dq_d256<1, DBIAS>;
-        case 2: return k_t5_attn_bwd_dq_d256<2, DBIAS>;
-        case 3: return k_t5_attn_bwd_dq_d256<3, DBIAS>;
-        case 4: return k_t5_attn_bwd_dq_d256<4, DBIAS>;
-        case 5: return k_t5_attn_bwd_dq_d256<5, DBIAS>;
-        case 6: return k_t5_attn_bwd_dq_d256<6, DBIAS>;
-        default: return k_t5_attn_bwd_dq_d256<7, DBIAS>;
+        case 0: return k_t5_attn_bwd_dq_d256<0, DBIAS, ORD>;
+        case 1: return k_t5_attn_bwd_dq_d256<1, DBIAS, ORD>;
+        case 2: return k_t5_attn_bwd_dq_d256<2, DBIAS, ORD>;
+        case 3: return k_t5_attn_bwd_dq_d256<3, DBIAS, ORD>;
+        case 4: return k_t5_attn_bwd_dq_d256<4, DBIAS, ORD>;
+        case 5: return k_t5_attn_bwd_dq_d256<5, DBIAS, ORD>;
+        case 6: return k_t5_attn_bwd_dq_d256<6, DBIAS, ORD>;
+        default: return k_t5_attn_bwd_dq_d256<7, DBIAS, ORD>;
     }
 }
 
-int tb_launch_d256(TbArgs k, int flags, unsigned grid_k, unsigned grid_q, void* stream) {
+int tb_launch_d256(TbArgs k, int flags, unsigned grid_k, unsigned grid_q, bool ordered, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     k.nblk = (k.S + kTb256KvKTile - 1) / kTb256KvKTile;
     hipLaunchKernelGGL(tb2_pick_dkv(flags), dim3(grid_k), dim3(kT2Threads), 0, st, k);
     const int rc = check_launch("k_t5_attn_bwd_dkv_d256");
     if (rc != TRLX_OK) return rc;
     k.nblk = (k.Tq + kTb256DqQTile - 1) / kTb256DqQTile;
-    hipLaunchKernelGGL(k.dbias ? tb2_pick_dq<true>(flags) : tb2_pick_dq<false>(flags), dim3(grid_q), dim3(kT2Threads), 0, st, k);
+    const tb2_kernel_t fn = !k.dbias ? tb2_pick_dq<false>(flags) : ordered ? tb2_pick_dq<true, true>(flags) : tb2_pick_dq<true>(flags);
+    hipLaunchKernelGGL(fn, dim3(grid_q), dim3(kT2Threads), 0, st, k);
     return check_launch("k_t5_attn_bwd_dq_d256");
 }
 

@@ -9,7 +9,8 @@ with the relative-position bias, the key mask and the causal rule inside the ker
   t5_attention_train         the same under autograd: trlx_t5_attention_fwd_lse forward, saving
                              q, k, v, out and the fp32 row statistics, and trlx_t5_attention_bwd
                              (csrc/t5_attention_bwd.hip, at d_kv 256 csrc/t5_attention_bwd_d256.hip)
-                             for dq, dk, dv and the bias table's gradient
+                             for dq, dk, dv and the bias table's gradient (bias_grad="ordered":
+                             trlx_t5_attention_bwd_ordered, a bit-reproducible one without atomics)
 
 The three many-query attentions of a T5 PPO rollout:
   encoder self-attention                 bias = bidirectional table, key_mask = attention_mask
@@ -266,10 +267,11 @@ def _kernel_forward(q4, k4, v4, bias, key_mask, causal, with_lse):
 
 
 class _T5AttentionFn(torch.autograd.Function):
-    """trlx_t5_attention_fwd_lse / trlx_t5_attention_bwd on [B, T, nH, d] bf16 operands."""
+    """trlx_t5_attention_fwd_lse / trlx_t5_attention_bwd (ordered: trlx_t5_attention_bwd_ordered) on
+    [B, T, nH, d] bf16 operands."""
 
     @staticmethod
-    def forward(ctx, q4, k4, v4, bias, key_mask, causal):
+    def forward(ctx, q4, k4, v4, bias, key_mask, causal, ordered):
         q4, k4, v4 = _in_place(q4), _in_place(k4), _in_place(v4)
         if bias is not None:
             bias = bias.detach().contiguous()
@@ -278,6 +280,7 @@ class _T5AttentionFn(torch.autograd.Function):
         out, lse = _kernel_forward(q4.detach(), k4.detach(), v4.detach(), bias, key_mask, causal, True)
         ctx.save_for_backward(q4, k4, v4, out, lse, bias, key_mask)
         ctx.causal = bool(causal)
+        ctx.ordered = bool(ordered)
         return out
 
     @staticmethod
@@ -302,11 +305,17 @@ class _T5AttentionFn(torch.autograd.Function):
             lse=lse.data_ptr(), bias_by_offset=_lib.ptr(bias), key_mask=_lib.ptr(key_mask), dbias=_lib.ptr(dbias),
             workspace=ws.data_ptr(), workspace_bytes=ws_bytes, B=B, n_heads=nH, d_kv=d, Tq=Tq, S=S,
             dtype=_lib.dtype_code(q4), causal=1 if ctx.causal else 0)
-        _lib.call("trlx_t5_attention_bwd", ctypes.byref(args), _lib.stream_of(dq))
-        return dq, dk, dv, dbias, None, None
+        if want_dbias and ctx.ordered:   # the partial rows of the ordered bias gradient, summed by a last launch
+            pw_bytes = _lib.query("trlx_t5_attention_bwd_dbias_workspace_bytes", B, nH, d, Tq, S)
+            pw = torch.empty(pw_bytes, dtype=torch.uint8, device=q4.device)
+            _lib.call("trlx_t5_attention_bwd_ordered", ctypes.byref(args), pw.data_ptr(), pw_bytes, _lib.stream_of(dq))
+        else:
+            _lib.call("trlx_t5_attention_bwd", ctypes.byref(args), _lib.stream_of(dq))
+        return dq, dk, dv, dbias, None, None, None
 
 
-def t5_attention_train(q, k, v, *, bias=None, key_mask=None, causal=False, n_heads=None, layout="bhtd"):
+def t5_attention_train(q, k, v, *, bias=None, key_mask=None, causal=False, n_heads=None, layout="bhtd",
+                       bias_grad="atomic"):
     """`t5_attention` under autograd: the same operands, layouts and checks, the same result
     (bit for bit on the kernel's shapes), and gradients for q, k, v shaped like the tensors given and,
     when `bias.requires_grad`, the fp32 [nH, Tq + S - 1] gradient of the bias table.
@@ -320,11 +329,21 @@ def t5_attention_train(q, k, v, *, bias=None, key_mask=None, causal=False, n_hea
     Saved for the backward: q, k, v, out and the fp32 row statistics lse [B, nH, Tq] (and the bias and
     the mask) — nothing of size Tq x S; the backward recomputes the scores per tile
     (trlx_t5_attention_bwd: dq, dk, dv bit-reproducible, the bias gradient summed with fp32 atomics
-    and not).  The incoming gradient is read in place when it meets the stride rules, else copied
+    and not).
+    bias_grad: "atomic" (the default) or "ordered".  "ordered" takes trlx_t5_attention_bwd_ordered: the
+    bias gradient without a global atomic, summed in an order that (d_kv, B, Tq, S, the flags, the
+    mask rows) fix, so two runs of an update agree bit for bit; dq, dk, dv and the forward are the
+    same bits either way.  It costs a second workspace of B * nH * ceil(Tq / 128) * (S + 127) fp32
+    (1 / 64 of one bf16 score tensor, freed after the backward) and one more launch; README's
+    backward table says where it is also the faster route.  Any other value raises ValueError.  The
+    torch routes below ignore it: torch's autograd sums in a fixed order already.
+    The incoming gradient is read in place when it meets the stride rules, else copied
     once.  No double backward.  Under torch.no_grad(), or with nothing that requires grad, this is
     `t5_attention`.  For other dtypes, other d_kv (not 64, 128 or 256) or CPU tensors the same torch
     expressions as `t5_attention`'s run under autograd; float64 operands stay in float64 throughout, softmax
     included, and may come with a float64 bias table."""
+    if bias_grad not in ("atomic", "ordered"):
+        raise ValueError(f"bias_grad must be 'atomic' or 'ordered', got {bias_grad!r}")
     q4, k4, v4, (B, Tq, nH, d, S) = _checked(q, k, v, bias, key_mask, causal, n_heads, layout, f64_bias=True)
     needs = torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (q, k, v, bias))
     if not needs:   # exactly t5_attention, for every dtype (a float64 table goes in as the float32 it takes)
@@ -335,7 +354,7 @@ def t5_attention_train(q, k, v, *, bias=None, key_mask=None, causal=False, n_hea
         return _torch_attention(q4, k4, v4, bias, key_mask, bool(causal), softmax_dtype=torch.float64)
     if q4.dtype not in KERNEL_DTYPES or d not in TRAIN_KERNEL_D_KV or not q4.is_cuda:
         return _torch_attention(q4, k4, v4, bias, key_mask, bool(causal))
-    return _T5AttentionFn.apply(q4, k4, v4, bias, key_mask, bool(causal))
+    return _T5AttentionFn.apply(q4, k4, v4, bias, key_mask, bool(causal), bias_grad == "ordered")
 
 
 # the package exports the function under the module's name: keep the tiles reachable either way
