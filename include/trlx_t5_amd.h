@@ -1204,6 +1204,63 @@ int trlx_t5_decode_attn_group_mma(const TrlxT5DecodeAttnGroupArgs* a, void* stre
  * 32 * W keys); 0 for a d_kv the entry does not take.  Needs no device. */
 int trlx_t5_decode_attn_group_mma_waves(int64_t d_kv);
 
+/* ---------------------------------------------------------------- the MFMA tile at d_kv 256, keys split
+ * trlx_t5_decode_attn_group_mma for d_kv 256 (the UL2 head size), bf16, with the encoder keys cut
+ * into ranges that workgroups of the same kernel walk side by side.  The argument block and its
+ * meaning are trlx_t5_decode_attn_group's; d_kv must be 256.
+ *   splits    : 1 ... 8 (trlx_t5_decode_attn_group_d256_plan gives the default for a shape).
+ *   workspace : for splits > 1 device memory, 16-byte aligned, at least
+ *               trlx_t5_decode_attn_group_d256_workspace_bytes(P * G, n_heads, S, splits) bytes: fp32
+ *               states [P * G, n_heads, ranges, 258].  Scratch: it needs no initialisation and
+ *               nothing is kept in it between calls; two calls in flight on different streams
+ *               need a workspace each.  Not read at splits 1 (NULL is fine).
+ * k_t5_decode_attn_group_d256, grid (P * n_heads, ceil(G / 16), ranges), 4 waves, one a SIMD: a
+ *   workgroup takes a (prompt, head, tile of 16 queries, range of the keys).  The keys are cut into
+ *   nblk = ceil(S / 32) blocks; with cb = ceil(nblk / splits) range x holds blocks [x cb, min(nblk,
+ *   (x + 1) cb)), ranges = ceil(nblk / cb) of them are not empty and only those are launched; wave w
+ *   walks blocks x cb + w, + 4, ...  Per block the arithmetic is trlx_t5_decode_attn_group_mma's
+ *   (K·Q^T and V^T·P^T on v_mfma_f32_16x16x32_bf16, fp32 online softmax, P rounded to bf16
+ *   un-normalised); the four waves' states are merged in wave order against their maximum.
+ *   splits 1: the merged state is divided, rounded once and stored: ONE launch, no workspace.
+ *   splits > 1: the undivided (M, L, o[256]) of every live query goes to workspace[((row * n_heads
+ *   + h) * ranges + x) * 258], M = -inf and L = 0 when the range held no live key; a dead query and a
+ *   dead tile write nothing.
+ * k_t5_decode_attn_group_d256_merge (splits > 1 only), one thread per (row, head, 8 columns): the
+ *   row's records in range order against their maximum, divided, rounded once, stored; a dead row
+ *   gets zeros and its records are not read.
+ * Masked keys, a fully masked prompt, dead rows and dead tiles behave as in
+ * trlx_t5_decode_attn_group (not read; zeros).  No atomics; bit-reproducible; a row's bits depend
+ * only on its own q, the prompt's keys, values and mask, S and splits: not on G, the row's place
+ * in its tile, P, the strides, the other rows' live words or the workspace's earlier contents.  The
+ * launches take the same arguments at every token: the call captures as it is.
+ * Refused with TRLX_ERR_ARG before any launch: everything trlx_t5_decode_attn_group refuses with
+ * "d_kv other than 256" in the place of its d_kv rule, TRLX_F32, a P * G * n_heads past 2^31 - 1,
+ * splits outside 1 ... 8, and for splits > 1 a workspace that is NULL, not 16-byte aligned or too
+ * small. */
+int trlx_t5_decode_attn_group_d256(const TrlxT5DecodeAttnGroupArgs* a, int64_t splits, void* workspace,
+                                   int64_t workspace_bytes, void* stream);
+
+/* Bytes of workspace for `rows` = P * G rows: rows * n_heads * ranges * 258 * 4 with the ranges of
+ * (S, splits); 0 at splits 1, and for rows, n_heads or S < 1 or splits outside 1 ... 8. */
+int64_t trlx_t5_decode_attn_group_d256_workspace_bytes(int64_t rows, int64_t n_heads, int64_t S, int64_t splits);
+
+/* The geometry of trlx_t5_decode_attn_group_d256 for S keys at `splits` (1 ... 8).  A host function,
+ * no device needed.  TRLX_ERR_ARG (and a zeroed *g) for a NULL g, S < 1, splits outside 1 ... 8. */
+typedef struct TrlxT5DecodeAttnGroupD256Geometry {
+    int64_t waves;       /* waves of a workgroup: 4 */
+    int64_t block_keys;  /* keys a block: 32 */
+    int64_t tile;        /* queries a tile: 16 */
+    int64_t cb;          /* blocks a range: ceil(ceil(S / 32) / splits) */
+    int64_t ranges;      /* non-empty ranges = ceil(ceil(S / 32) / cb) <= splits: the grid's z */
+    int64_t max_splits;  /* 8 */
+} TrlxT5DecodeAttnGroupD256Geometry;
+int trlx_t5_decode_attn_group_d256_geometry(int64_t S, int64_t splits, TrlxT5DecodeAttnGroupD256Geometry* g);
+
+/* The default splits of a shape: a pure function of these arguments (it looks neither at live nor
+ * at the device), in 1 ... 8, set from measurements (DESIGN.md,
+ * profiles/t5_cross_group_d256_bench.json).  1 for arguments the entry would refuse. */
+int trlx_t5_decode_attn_group_d256_plan(int64_t P, int64_t G, int64_t n_heads, int64_t S);
+
 /* ---------------------------------------------------------------- encoder keys split across workgroups
  * trlx_t5_decode_attn_group with the S keys of a (row, head) cut into X ranges, each walked by a
  * workgroup of its own: for the shapes where P * n_heads * tiles workgroups leave the chip

@@ -59,6 +59,10 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
   t5_decode_cross_attention_grouped_mma — opt-in: the grouped call with 16 of a prompt's samples as the
       columns of an MFMA tile, for groups of 8 to 64: K / V read once per 16 samples, arithmetic per
       key independent of G; not bit-equal to the grouped call, a row's bits are its own
+  t5_decode_cross_attention_grouped_mma_d256 (+ _d256_plan, _d256_geometry, _d256_workspace_bytes) —
+      the MFMA tile at d_kv 256 (the UL2 head size): a kernel of its own with one wave a SIMD and the
+      encoder keys split across workgroups of the same kernel; t5_decode_cross_attention_grouped_mma
+      takes it at bf16 d_kv 256
   t5_decode_cross_attention_split (+ _split_plan, _split_geometry) — opt-in: the same call with the
       encoder keys of a (row, head) cut into ranges walked by workgroups of their own and merged by
       a second launch, for few rows, few live rows or long prompts; the plan is set from measurements
@@ -109,6 +113,10 @@ from .value_head import make_head as make_value_head
 from .sampling import PPOLogitsProcessors, ppo_sample_step
 from .t5_decode import (T5CrossKV8, T5DecodeClock, T5DecodeKVCache, t5_decode_cross_attention,
                         t5_decode_cross_attention_grouped, t5_decode_cross_attention_grouped_mma,
+                        t5_decode_cross_attention_grouped_mma_d256,
+                        t5_decode_cross_attention_grouped_mma_d256_geometry,
+                        t5_decode_cross_attention_grouped_mma_d256_plan,
+                        t5_decode_cross_attention_grouped_mma_d256_workspace_bytes,
                         t5_decode_cross_attention_kv8,
                         t5_decode_cross_attention_split, t5_decode_cross_attention_split_geometry,
                         t5_decode_cross_attention_split_plan, t5_decode_embed,
@@ -138,6 +146,8 @@ __all__ = [
     "t5_decode_embed", "T5CrossKV8", "t5_quantize_cross_kv", "t5_decode_cross_attention_kv8",
     "t5_decode_cross_attention_grouped", "t5_decode_cross_attention_grouped_mma", "t5_decode_cross_attention_split",
     "t5_decode_cross_attention_split_plan", "t5_decode_cross_attention_split_geometry",
+    "t5_decode_cross_attention_grouped_mma_d256", "t5_decode_cross_attention_grouped_mma_d256_geometry",
+    "t5_decode_cross_attention_grouped_mma_d256_plan", "t5_decode_cross_attention_grouped_mma_d256_workspace_bytes",
     "t5_attention", "t5_relative_bias_offsets", "t5_attention_train", "t5_relative_bias_buckets",
     "t5_ff_act", "t5_ff_act_packed", "T5FeedForward",
     "t5_rmsnorm", "t5_add_rmsnorm", "T5LayerNorm",

@@ -128,6 +128,12 @@ class T5DecodeAttnSplitGeometry(ctypes.Structure):
     _fields_ = [("NG", _c_i64), ("C", _c_i64), ("ranges", _c_i64), ("tile", _c_i64), ("max_splits", _c_i64)]
 
 
+class T5DecodeAttnGroupD256Geometry(ctypes.Structure):
+    """Mirror of TrlxT5DecodeAttnGroupD256Geometry (include/trlx_t5_amd.h)."""
+    _fields_ = [("waves", _c_i64), ("block_keys", _c_i64), ("tile", _c_i64), ("cb", _c_i64), ("ranges", _c_i64),
+                ("max_splits", _c_i64)]
+
+
 class T5DecodeEmbedArgs(ctypes.Structure):
     """Mirror of TrlxT5DecodeEmbedArgs (include/trlx_t5_amd.h)."""
     _fields_ = [
@@ -416,6 +422,10 @@ SIGNATURES = {
     "trlx_t5_decode_attn_group_tile": (_c_int, [_c_i64]),
     "trlx_t5_decode_attn_group_mma": (_c_int, [ctypes.POINTER(T5DecodeAttnGroupArgs), _c_vp]),
     "trlx_t5_decode_attn_group_mma_waves": (_c_int, [_c_i64]),
+    "trlx_t5_decode_attn_group_d256": (_c_int, [ctypes.POINTER(T5DecodeAttnGroupArgs), _c_i64, _c_vp, _c_i64, _c_vp]),
+    "trlx_t5_decode_attn_group_d256_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    "trlx_t5_decode_attn_group_d256_geometry": (_c_int, [_c_i64, _c_i64, ctypes.POINTER(T5DecodeAttnGroupD256Geometry)]),
+    "trlx_t5_decode_attn_group_d256_plan": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64]),
     "trlx_t5_decode_attn_split": (_c_int, [ctypes.POINTER(T5DecodeAttnGroupArgs), _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_t5_decode_attn_split_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
     "trlx_t5_decode_attn_split_geometry": (_c_int, [_c_int, _c_i64, _c_i64, _c_i64,

@@ -40,11 +40,14 @@ int t5_group_tile(int64_t G) {
 }
 
 int t5_group_check(const TrlxT5DecodeAttnGroupArgs* a, const char* who, bool f32_ok, bool rows_by_heads, int tile,
-                   T5GroupChecked* c) {
+                   T5GroupChecked* c, int64_t d_only) {
     TRLX_REQUIRE(a, TRLX_ERR_ARG, "%s: NULL arguments", who);
     TRLX_REQUIRE(a->dtype == TRLX_BF16 || (f32_ok && a->dtype == TRLX_F32), TRLX_ERR_ARG, "%s: dtype %d (%s only)", who,
                  a->dtype, f32_ok ? "bf16 and fp32" : "bf16");
-    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128, TRLX_ERR_ARG, "%s: d_kv %lld (64 and 128 only)", who, (long long)a->d_kv);
+    if (d_only)
+        TRLX_REQUIRE(a->d_kv == d_only, TRLX_ERR_ARG, "%s: d_kv %lld (%lld only)", who, (long long)a->d_kv, (long long)d_only);
+    else
+        TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128, TRLX_ERR_ARG, "%s: d_kv %lld (64 and 128 only)", who, (long long)a->d_kv);
     TRLX_REQUIRE(a->P >= 1 && a->G >= 1 && a->n_heads >= 1 && a->S >= 1, TRLX_ERR_ARG,
                  "%s: P %lld, G %lld, heads %lld, S %lld (all >= 1)", who, (long long)a->P, (long long)a->G,
                  (long long)a->n_heads, (long long)a->S);

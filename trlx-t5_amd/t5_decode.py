@@ -31,7 +31,8 @@ Forward only: generation runs under no_grad.
 
 Kernel shapes: bfloat16 / float32 with d_kv 64 / 128 / 256 (256, the UL2 head size: 32 lanes a
 bf16 key row, a whole wave an fp32 one) for the self- and the cross-attention, host t, t=clock and
-live= alike; the kv8, grouped and split calls take d_kv 64 / 128.  For any other dtype or d_kv the
+live= alike; the grouped MFMA call takes bf16 d_kv 256 too (a kernel of its own, keys split across
+workgroups); the kv8, the scalar grouped and the scalar split calls take d_kv 64 / 128.  For any other dtype or d_kv the
 two functions evaluate the same step as torch expressions (`_torch_self_attention`,
 `_torch_cross_attention`, HF's op order).
 """
@@ -47,7 +48,7 @@ __all__ = ["t5_relative_bias_table", "T5DecodeKVCache", "T5DecodeClock", "t5_dec
            "t5_decode_cross_attention_kv8", "t5_decode_cross_attention_grouped"]
 
 KERNEL_DTYPES = (torch.bfloat16, torch.float32)
-KERNEL_D_KV = (64, 128)            # the kv8, grouped, grouped-MMA and split calls
+KERNEL_D_KV = (64, 128)            # the kv8, grouped, grouped-MMA and split calls (bf16 256: ..._grouped_mma_d256)
 BASE_KERNEL_D_KV = (64, 128, 256)  # t5_decode_self_attention / t5_decode_cross_attention (t=clock and live= included)
 
 
@@ -526,8 +527,9 @@ def _group_strides(x):
     return x, st
 
 
-def _group_launch(entry, q, k, v, key_mask, live, dims):
-    """One launch of a grouped entry (trlx_t5_decode_attn_group or _group_mma) on checked operands."""
+def _group_launch(entry, q, k, v, key_mask, live, dims, extra=()):
+    """One call of a grouped entry (trlx_t5_decode_attn_group, _group_mma or _group_d256) on checked
+    operands; `extra`: the entry's arguments between the block and the stream."""
     P, nH, S, d, B, G = dims
     _lib.require_cuda(k, q)
     if key_mask is not None and not key_mask.is_contiguous():
@@ -539,7 +541,7 @@ def _group_launch(entry, q, k, v, key_mask, live, dims):
         q=q2.data_ptr(), ldq=ldq, k=k.data_ptr(), k_stride_p=k_st[0], k_stride_h=k_st[1], k_stride_s=k_st[2],
         v=v.data_ptr(), v_stride_p=v_st[0], v_stride_h=v_st[1], v_stride_s=v_st[2], key_mask=_lib.ptr(key_mask),
         live=_lib.ptr(live), out=out.data_ptr(), P=P, G=G, n_heads=nH, d_kv=d, S=S, dtype=_lib.dtype_code(k))
-    _lib.call(entry, ctypes.byref(args), _lib.stream_of(out))
+    _lib.call(entry, ctypes.byref(args), *extra, _lib.stream_of(out))
     return out
 
 
@@ -613,10 +615,14 @@ def t5_decode_cross_attention_grouped_mma(q, k_enc, v_enc, key_mask=None, live=N
     2 * torch's eager bf16 error + one bf16 ulp.  It is bit-reproducible, and a row's bits depend only on
     its own q, the prompt's keys, values and mask, and S: not on G, the row's place in the group,
     the other rows' `live`, P or the strides, so a rollout stays reproducible as rows finish.
-    bf16 with d_kv 64 or 128 on a ROCm device; anything else (fp32, another d_kv, CPU tensors) goes
-    to t5_decode_cross_attention_grouped.  One launch, same arguments at every token: capturable.
+    bf16 with d_kv 64 or 128 on a ROCm device; bf16 d_kv 256 is
+    t5_decode_cross_attention_grouped_mma_d256 at its plan's splits; anything else (fp32, another
+    d_kv, CPU tensors) goes to t5_decode_cross_attention_grouped.  One launch, same arguments at
+    every token: capturable.
     Runs on the current stream, no host sync; only the output is allocated."""
     k, v, dims = _group_checked(q, k_enc, v_enc, key_mask, live, n_heads)
+    if k.is_cuda and k.dtype == torch.bfloat16 and dims[3] == D256:
+        return t5_decode_cross_attention_grouped_mma_d256(q, k_enc, v_enc, key_mask, live, n_heads)
     if not k.is_cuda or k.dtype != torch.bfloat16 or not _group_kernel_takes(k.dtype, dims[3]):
         return t5_decode_cross_attention_grouped(q, k_enc, v_enc, key_mask, live, n_heads)
     return _group_launch("trlx_t5_decode_attn_group_mma", q, k, v, key_mask, live, dims)
@@ -626,6 +632,73 @@ def t5_decode_cross_attention_grouped_mma_waves(d_kv):
     """W, the waves per workgroup of t5_decode_cross_attention_grouped_mma at this d_kv: a round of all
     waves covers 32 * W keys.  0 for a d_kv the kernel does not take.  Needs no device."""
     return int(_lib.query("trlx_t5_decode_attn_group_mma_waves", int(d_kv)))
+
+
+# ------------------------------------------------------------------ the MFMA tile at d_kv 256
+D256 = 256               # the head size of trlx_t5_decode_attn_group_d256
+D256_MAX_SPLITS = 8      # the largest `splits` it takes
+_D256_WORKSPACES = {}    # (device, bytes) -> uint8 tensor, allocated on first use and reused
+
+
+def t5_decode_cross_attention_grouped_mma_d256_geometry(S, splits):
+    """trlx_t5_decode_attn_group_d256_geometry as a dict (needs no device): waves of a workgroup,
+    block_keys a block, `tile` queries a workgroup, cb = ceil(ceil(S / 32) / splits) blocks a range,
+    `ranges` = the non-empty ranges (the grid's z) and max_splits."""
+    g = _lib.T5DecodeAttnGroupD256Geometry()
+    _lib.call("trlx_t5_decode_attn_group_d256_geometry", int(S), int(splits), ctypes.byref(g))
+    return {k: int(getattr(g, k)) for k, _ in g._fields_}
+
+
+def t5_decode_cross_attention_grouped_mma_d256_plan(P, G, n_heads, S):
+    """The `splits` t5_decode_cross_attention_grouped_mma_d256 takes by default
+    (trlx_t5_decode_attn_group_d256_plan): a pure function of the shape, in 1 ... 8, set from
+    measurements.  Needs no device."""
+    return int(_lib.query("trlx_t5_decode_attn_group_d256_plan", int(P), int(G), int(n_heads), int(S)))
+
+
+def t5_decode_cross_attention_grouped_mma_d256_workspace_bytes(rows, n_heads, S, splits):
+    """trlx_t5_decode_attn_group_d256_workspace_bytes: rows * n_heads * ranges * 258 * 4, 0 at one split."""
+    return int(_lib.query("trlx_t5_decode_attn_group_d256_workspace_bytes", int(rows), int(n_heads), int(S), int(splits)))
+
+
+def t5_decode_cross_attention_grouped_mma_d256(q, k_enc, v_enc, key_mask=None, live=None, n_heads=None, splits=None,
+                                               workspace=None):
+    """t5_decode_cross_attention_grouped_mma at d_kv 256, the UL2 head size
+    (trlx_t5_decode_attn_group_d256): a kernel of its own, four waves with one a SIMD, 16 of a
+    prompt's samples as the columns of an MFMA tile, and the encoder keys cut into `splits` ranges of
+    whole 32-key blocks that workgroups of the same kernel walk side by side.  Returns [P*G, nH*256].
+
+    q, k_enc, v_enc, key_mask, live, n_heads: as in t5_decode_cross_attention_grouped, with the same
+    checks and the same in-place reading through strides.  splits: None =
+    t5_decode_cross_attention_grouped_mma_d256_plan for the shape, or 1 ... 8.  1 is one launch and
+    touches no workspace; above 1 a second launch merges the ranges' fp32 states.  The result is
+    bit-reproducible, and a row's bits depend only on its own q, the prompt's keys, values and mask,
+    S and `splits`: not on G, the row's place in the group, P, the strides, the other rows' `live`
+    or what the workspace held.  workspace: None, or a contiguous tensor on the device of at least
+    t5_decode_cross_attention_grouped_mma_d256_workspace_bytes(P*G, nH, S, splits) bytes, 16-byte
+    aligned.  With None one is allocated on first use per (device, size) and reused, so the call
+    captures after one eager call; calls that may run concurrently on different streams must pass
+    workspaces of their own.  Anything but bf16 d_kv 256 on a ROCm device:
+    t5_decode_cross_attention_grouped_mma.  Runs on the current stream, no host sync."""
+    k, v, dims = _group_checked(q, k_enc, v_enc, key_mask, live, n_heads)
+    if splits is not None and not 1 <= int(splits) <= D256_MAX_SPLITS:
+        raise ValueError(f"splits = {splits}: None (the plan) or 1 ... {D256_MAX_SPLITS}")
+    P, nH, S, d, B, G = dims
+    if not k.is_cuda or k.dtype != torch.bfloat16 or d != D256:
+        return t5_decode_cross_attention_grouped_mma(q, k_enc, v_enc, key_mask, live, n_heads)
+    X = int(splits) if splits is not None else t5_decode_cross_attention_grouped_mma_d256_plan(P, G, nH, S)
+    need = t5_decode_cross_attention_grouped_mma_d256_workspace_bytes(B, nH, S, X)
+    if X == 1:
+        return _group_launch("trlx_t5_decode_attn_group_d256", q, k, v, key_mask, live, dims, (1, None, 0))
+    if workspace is None:
+        workspace = _D256_WORKSPACES.get((k.device, need))
+        if workspace is None:
+            workspace = _D256_WORKSPACES[k.device, need] = torch.empty(need, dtype=torch.uint8, device=k.device)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != k.device or not workspace.is_contiguous() \
+            or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {k.device}")
+    return _group_launch("trlx_t5_decode_attn_group_d256", q, k, v, key_mask, live, dims,
+                         (X, workspace.data_ptr(), workspace.numel() * workspace.element_size()))
 
 
 def t5_decode_cross_attention_group_tile(tile=0):
