@@ -1090,7 +1090,7 @@ int trlx_t5_decode_attn_live(const TrlxT5DecodeAttnArgs* a, const int64_t* live,
  * A live Inf or NaN in a (b, h) block of K (of V): that block's scale is NaN and each of its live
  * bytes is 0x7f, the e4m3fn NaN; the attention then gives NaN for that (b, h) and no other.
  * Refused with TRLX_ERR_ARG before any launch: NULL a / k / v / k8 / v8 / k_scale / v_scale, a
- * d_kv other than 64 / 128, B, n_heads or S < 1, k / v / k8 / v8 not 16-byte aligned, a scale not
+ * d_kv other than 64 / 128 / 256, B, n_heads or S < 1, k / v / k8 / v8 not 16-byte aligned, a scale not
  * 4-byte or key_mask not 8-byte aligned, a stride that is negative or not a whole number of
  * 16-byte vectors, a head or key stride below d_kv. */
 typedef struct TrlxT5CrossKvQuantArgs {
@@ -1106,7 +1106,7 @@ typedef struct TrlxT5CrossKvQuantArgs {
     int64_t B;
     int64_t n_heads;
     int64_t S;
-    int64_t d_kv;                     /* 64 or 128 */
+    int64_t d_kv;                     /* 64, 128 or 256 */
 } TrlxT5CrossKvQuantArgs;
 int trlx_t5_cross_kv_quantize(const TrlxT5CrossKvQuantArgs* a, void* stream);
 
@@ -1123,9 +1123,50 @@ int trlx_t5_cross_kv_quantize(const TrlxT5CrossKvQuantArgs* a, void* stream);
  * token: it captures as it is.
  * Refused with TRLX_ERR_ARG before any launch: everything the cross mode of trlx_t5_decode_attn
  * refuses (k and v not 16-byte aligned among it), mode TRLX_T5_ATTN_SELF, a dtype other than
- * TRLX_BF16, a NULL scale or one not 4-byte aligned, a live not 8-byte aligned. */
+ * TRLX_BF16, a NULL scale or one not 4-byte aligned, a live not 8-byte aligned.  d_kv 64 / 128; 256
+ * is refused here and taken by trlx_t5_decode_attn_kv8_d256, below. */
 int trlx_t5_decode_attn_kv8(const TrlxT5DecodeAttnArgs* a, const float* k_scale, const float* v_scale,
                             const int64_t* live, void* stream);
+
+/* trlx_t5_decode_attn_kv8 at d_kv 256, the UL2 head size, in a kernel of its own
+ * (k_t5_decode_attn_kv8_d256, csrc/t5_cross_kv8_d256.hip), with the encoder keys optionally cut
+ * across workgroups.  Arguments, formula and live as in trlx_t5_decode_attn_kv8; a->d_kv is 256.
+ * A key row is 256 bytes = 16 lanes x 16 B, a wave-wide load covers 4 rows, the 4-wave workgroup is
+ * 16 lane groups with 4 keys in flight each: a trip of the loop is 64 keys.  A group handles its 4
+ * keys in flight as one block: the partial dots reduced together inside the 16-lane row, one
+ * running-max update and one rescale of the accumulator per block, V unpacked after the block's
+ * probabilities are known.  fp32 arithmetic; v_scale is applied once, before the division and the
+ * one rounding.
+ *   splits == 1 : ONE launch, grid B * n_heads, the workspace is not touched (NULL is fine).
+ *   splits  > 1 : grid (B * n_heads, ranges).  Range x holds the whole trips
+ *                 [x * T, (x + 1) * T), T = ceil(ceil(max_len / 64) / splits); only the non-empty
+ *                 ranges are launched.  Each workgroup writes its unnormalised fp32 state
+ *                 (M, L, o[256]) to workspace[x][b * n_heads + h][258]; a second launch merges the
+ *                 ranges in split order against the common maximum, applies v_scale, divides and
+ *                 rounds.  A range with no live key contributes nothing; a row with none gives zeros;
+ *                 a NaN scale reaches the output of its (row, head) only.  No atomics.
+ * A row with live[b] == 0 reads none of q, K, V, the mask or the scales and is written as zeros
+ * once: by its workgroup at splits == 1, by the merge above that (the part kernel writes nothing).
+ * A row's bits depend only on its own q, bytes, scales, mask, max_len and splits: not on B, ldq,
+ * live, the other rows or what the workspace held.  They differ between values of splits.
+ * Refused with TRLX_ERR_ARG before any launch: everything trlx_t5_decode_attn_kv8 refuses, a d_kv
+ * other than 256, splits outside 1 ... 16, and for splits > 1 a workspace that is NULL, not 16-byte
+ * aligned or smaller than trlx_t5_decode_attn_kv8_d256_workspace_bytes(B, n_heads, splits). */
+int trlx_t5_decode_attn_kv8_d256(const TrlxT5DecodeAttnArgs* a, const float* k_scale, const float* v_scale,
+                                 const int64_t* live, int splits, void* workspace, int64_t workspace_bytes,
+                                 void* stream);
+/* splits * B * n_heads * 258 * 4; 0 for arguments the entry refuses.  Needs no device. */
+int64_t trlx_t5_decode_attn_kv8_d256_workspace_bytes(int64_t B, int64_t n_heads, int64_t splits);
+typedef struct TrlxT5DecodeAttnKv8D256Geometry {
+    int64_t rows_per_wave_load;       /* 4 */
+    int64_t lane_groups;              /* 16 */
+    int64_t keys_per_trip;            /* 64 */
+    int64_t keys_per_range;           /* ceil(ceil(S / 64) / splits) * 64 */
+    int64_t ranges;                   /* ceil(S / keys_per_range): the ranges launched, <= splits */
+    int64_t max_splits;               /* 16 */
+} TrlxT5DecodeAttnKv8D256Geometry;
+/* The geometry of trlx_t5_decode_attn_kv8_d256 for S keys and `splits`.  Needs no device. */
+int trlx_t5_decode_attn_kv8_d256_geometry(int64_t S, int64_t splits, TrlxT5DecodeAttnKv8D256Geometry* g);
 
 /* ---------------------------------------------------------------- encoder keys shared by a prompt's samples
  * trlx_t5_decode_attn, mode TRLX_T5_ATTN_CROSS, for a rollout that draws G samples per prompt

@@ -51,7 +51,9 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
   t5_quantize_cross_kv, T5CrossKV8, t5_decode_cross_attention_kv8 — opt-in: the encoder's keys and
       values as e4m3fn bytes with a power-of-two scale per (row, head), quantised once per rollout
       in one launch, and the decode cross-attention over them: half the K / V bytes per token,
-      fp32 arithmetic; lossy against the bf16 keys, exact against its own dequantised values
+      fp32 arithmetic; lossy against the bf16 keys, exact against its own dequantised values.  d_kv
+      64 / 128 / 256; at 256 (UL2) a kernel of its own, `splits=` cuts the keys across workgroups
+      (+ t5_decode_cross_attention_kv8_d256_geometry, _d256_workspace_bytes)
   t5_decode_cross_attention_grouped — the decode cross-attention of a rollout that draws G samples
       per prompt (num_return_sequences, RLOO / GRPO groups) over one copy of each prompt's keys and
       values: K / V bytes per token and K / V memory divided by G, every row bit-identical to
@@ -117,7 +119,8 @@ from .t5_decode import (T5CrossKV8, T5DecodeClock, T5DecodeKVCache, t5_decode_cr
                         t5_decode_cross_attention_grouped_mma_d256_geometry,
                         t5_decode_cross_attention_grouped_mma_d256_plan,
                         t5_decode_cross_attention_grouped_mma_d256_workspace_bytes,
-                        t5_decode_cross_attention_kv8,
+                        t5_decode_cross_attention_kv8, t5_decode_cross_attention_kv8_d256_geometry,
+                        t5_decode_cross_attention_kv8_d256_workspace_bytes,
                         t5_decode_cross_attention_split, t5_decode_cross_attention_split_geometry,
                         t5_decode_cross_attention_split_plan, t5_decode_embed,
                         t5_decode_self_attention, t5_quantize_cross_kv, t5_relative_bias_table)
@@ -144,6 +147,7 @@ __all__ = [
     "FusedAdamW", "adamw_step", "clip_grad_norm_", "schedule_table",
     "T5DecodeKVCache", "T5DecodeClock", "t5_decode_self_attention", "t5_decode_cross_attention", "t5_relative_bias_table",
     "t5_decode_embed", "T5CrossKV8", "t5_quantize_cross_kv", "t5_decode_cross_attention_kv8",
+    "t5_decode_cross_attention_kv8_d256_geometry", "t5_decode_cross_attention_kv8_d256_workspace_bytes",
     "t5_decode_cross_attention_grouped", "t5_decode_cross_attention_grouped_mma", "t5_decode_cross_attention_split",
     "t5_decode_cross_attention_split_plan", "t5_decode_cross_attention_split_geometry",
     "t5_decode_cross_attention_grouped_mma_d256", "t5_decode_cross_attention_grouped_mma_d256_geometry",

@@ -134,6 +134,12 @@ class T5DecodeAttnGroupD256Geometry(ctypes.Structure):
                 ("max_splits", _c_i64)]
 
 
+class T5DecodeAttnKv8D256Geometry(ctypes.Structure):
+    """Mirror of TrlxT5DecodeAttnKv8D256Geometry (include/trlx_t5_amd.h)."""
+    _fields_ = [("rows_per_wave_load", _c_i64), ("lane_groups", _c_i64), ("keys_per_trip", _c_i64),
+                ("keys_per_range", _c_i64), ("ranges", _c_i64), ("max_splits", _c_i64)]
+
+
 class T5DecodeEmbedArgs(ctypes.Structure):
     """Mirror of TrlxT5DecodeEmbedArgs (include/trlx_t5_amd.h)."""
     _fields_ = [
@@ -422,6 +428,10 @@ SIGNATURES = {
     "trlx_t5_decode_attn_group_tile": (_c_int, [_c_i64]),
     "trlx_t5_decode_attn_group_mma": (_c_int, [ctypes.POINTER(T5DecodeAttnGroupArgs), _c_vp]),
     "trlx_t5_decode_attn_group_mma_waves": (_c_int, [_c_i64]),
+    "trlx_t5_decode_attn_kv8_d256": (_c_int, [ctypes.POINTER(T5DecodeAttnArgs), _c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_i64,
+                                              _c_vp]),
+    "trlx_t5_decode_attn_kv8_d256_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64]),
+    "trlx_t5_decode_attn_kv8_d256_geometry": (_c_int, [_c_i64, _c_i64, ctypes.POINTER(T5DecodeAttnKv8D256Geometry)]),
     "trlx_t5_decode_attn_group_d256": (_c_int, [ctypes.POINTER(T5DecodeAttnGroupArgs), _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_t5_decode_attn_group_d256_workspace_bytes": (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
     "trlx_t5_decode_attn_group_d256_geometry": (_c_int, [_c_i64, _c_i64, ctypes.POINTER(T5DecodeAttnGroupD256Geometry)]),

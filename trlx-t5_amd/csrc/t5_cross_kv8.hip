@@ -141,8 +141,8 @@ using namespace trlx;
 
 extern "C" int trlx_t5_cross_kv_quantize(const TrlxT5CrossKvQuantArgs* a, void* stream) {
     TRLX_REQUIRE(a, TRLX_ERR_ARG, "t5 cross kv quantize: NULL arguments");
-    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128, TRLX_ERR_ARG, "t5 cross kv quantize: d_kv %lld (64 and 128 only)",
-                 (long long)a->d_kv);
+    TRLX_REQUIRE(a->d_kv == 64 || a->d_kv == 128 || a->d_kv == 256, TRLX_ERR_ARG,
+                 "t5 cross kv quantize: d_kv %lld (64, 128 and 256 only)", (long long)a->d_kv);
     TRLX_REQUIRE(a->B >= 1 && a->n_heads >= 1 && a->S >= 1 && a->B * a->n_heads <= 0x7fffffffLL &&
                      a->S <= 0x7fffffffLL / 128 && a->n_heads <= 0x7fffffffLL / 128,
                  TRLX_ERR_ARG, "t5 cross kv quantize: B %lld, heads %lld, S %lld", (long long)a->B,
@@ -174,7 +174,7 @@ extern "C" int trlx_t5_cross_kv_quantize(const TrlxT5CrossKvQuantArgs* a, void* 
     q.v_sb = st[3], q.v_sh = st[4], q.v_ss = st[5];
     q.nH = int(a->n_heads);
     q.S = int(a->S);
-    hipLaunchKernelGGL(a->d_kv == 64 ? k_t5_cross_kv_quantize<64> : k_t5_cross_kv_quantize<128>,
+    hipLaunchKernelGGL(a->d_kv == 64 ? k_t5_cross_kv_quantize<64> : a->d_kv == 128 ? k_t5_cross_kv_quantize<128> : k_t5_cross_kv_quantize<256>,
                        dim3(unsigned(a->B * a->n_heads)), dim3(kQ8Threads), 0, (hipStream_t)stream, q);
     return check_launch("k_t5_cross_kv_quantize");
 }

@@ -4,7 +4,8 @@
 // separate; the geometry, the per-key step, the merge of the lane groups and the stores are written
 // here once, so the bits one kernel produces for a query are the bits of the others: grouped ==
 // plain on the expanded tensors, split with one live range == grouped.  k_t5_decode_attn_kv8
-// (t5_cross_kv8.hip) takes the geometry and the stores and keeps a step and a merge of its own.
+// (t5_cross_kv8.hip) takes the geometry and the stores and keeps a step and a merge of its own, and so
+// does k_t5_decode_attn_kv8_d256 (t5_cross_kv8_d256.hip), whose step takes four keys at a time.
 #pragma once
 
 #include "common.h"

@@ -16,7 +16,8 @@
   t5_quantize_cross_kv       the encoder's keys / values to e4m3fn bytes with one power-of-two scale
                              per (row, head), once per rollout: one launch, a T5CrossKV8
   t5_decode_cross_attention_kv8   the cross-attention over those bytes: half the K / V traffic per
-                             token, fp32 arithmetic; opt-in and lossy (3 mantissa bits)
+                             token, fp32 arithmetic; opt-in and lossy (3 mantissa bits).  At d_kv 256
+                             a kernel of its own, splits= cuts the keys across workgroups
   t5_decode_cross_attention_grouped   the cross-attention of a rollout that draws G samples per
                              prompt over ONE copy of each prompt's keys / values: K / V bytes per
                              token and K / V memory divided by G, every row bit-identical to
@@ -32,8 +33,10 @@ Forward only: generation runs under no_grad.
 Kernel shapes: bfloat16 / float32 with d_kv 64 / 128 / 256 (256, the UL2 head size: 32 lanes a
 bf16 key row, a whole wave an fp32 one) for the self- and the cross-attention, host t, t=clock and
 live= alike; the grouped MFMA call takes bf16 d_kv 256 too (a kernel of its own, keys split across
-workgroups); the kv8, the scalar grouped and the scalar split calls take d_kv 64 / 128.  For any other dtype or d_kv the
-two functions evaluate the same step as torch expressions (`_torch_self_attention`,
+workgroups); the quantiser and the kv8 call take d_kv 64 / 128 / 256 (256:
+k_t5_decode_attn_kv8_d256, 16 lanes a key row, a block of 4 keys a step, splits=); the scalar
+grouped and the scalar split calls take d_kv 64 / 128.  For any other dtype or d_kv the two
+functions evaluate the same step as torch expressions (`_torch_self_attention`,
 `_torch_cross_attention`, HF's op order).
 """
 import ctypes
@@ -48,7 +51,8 @@ __all__ = ["t5_relative_bias_table", "T5DecodeKVCache", "T5DecodeClock", "t5_dec
            "t5_decode_cross_attention_kv8", "t5_decode_cross_attention_grouped"]
 
 KERNEL_DTYPES = (torch.bfloat16, torch.float32)
-KERNEL_D_KV = (64, 128)            # the kv8, grouped, grouped-MMA and split calls (bf16 256: ..._grouped_mma_d256)
+KERNEL_D_KV = (64, 128)            # the grouped, grouped-MMA and split calls (bf16 256: ..._grouped_mma_d256)
+KV8_KERNEL_D_KV = (64, 128, 256)   # t5_quantize_cross_kv / T5CrossKV8 / t5_decode_cross_attention_kv8
 BASE_KERNEL_D_KV = (64, 128, 256)  # t5_decode_self_attention / t5_decode_cross_attention (t=clock and live= included)
 
 
@@ -347,8 +351,8 @@ class T5CrossKV8:
     """
 
     def __init__(self, B, n_heads, S, d_kv, device):
-        if min(B, n_heads, S) < 1 or d_kv not in KERNEL_D_KV:
-            raise ValueError(f"B, n_heads, S = {B}, {n_heads}, {S} (>= 1), d_kv = {d_kv} (in {KERNEL_D_KV})")
+        if min(B, n_heads, S) < 1 or d_kv not in KV8_KERNEL_D_KV:
+            raise ValueError(f"B, n_heads, S = {B}, {n_heads}, {S} (>= 1), d_kv = {d_kv} (in {KV8_KERNEL_D_KV})")
         self.B, self.n_heads, self.S, self.d_kv = int(B), int(n_heads), int(S), int(d_kv)
         self.k8 = torch.zeros(B, n_heads, S, d_kv, dtype=torch.float8_e4m3fn, device=device)
         self.v8 = torch.zeros(B, n_heads, S, d_kv, dtype=torch.float8_e4m3fn, device=device)
@@ -403,8 +407,8 @@ def _kv_strides(x, name, n_heads):
     B, nH, S, d = x.shape
     if n_heads is not None and int(n_heads) != nH:
         raise ValueError(f"{name} has {nH} heads, n_heads = {n_heads}")
-    if min(B, nH, S) < 1 or d not in KERNEL_D_KV:
-        raise ValueError(f"{name}: B, nH, S = {B}, {nH}, {S} (>= 1), d_kv = {d} (in {KERNEL_D_KV})")
+    if min(B, nH, S) < 1 or d not in KV8_KERNEL_D_KV:
+        raise ValueError(f"{name}: B, nH, S = {B}, {nH}, {S} (>= 1), d_kv = {d} (in {KV8_KERNEL_D_KV})")
     st = [x.stride(i) if x.shape[i] > 1 else 0 for i in range(3)]
     if x.stride(3) != 1 or x.data_ptr() % 16 or any(s < 0 or s % 8 for s in st) or \
             (nH > 1 and st[1] < d) or (S > 1 and st[2] < d):
@@ -418,7 +422,7 @@ def t5_quantize_cross_kv(k_enc, v_enc, key_mask=None, out=None, n_heads=None):
     One launch for K and V (trlx_t5_cross_kv_quantize).
 
     k_enc, v_enc: bfloat16, [B, nH, S, d_kv] -- contiguous or HF's transposed view of the
-    projection -- or the projection output [B, S, nH*d_kv] with n_heads=; d_kv 64 or 128.  Both are
+    projection -- or the projection output [B, S, nH*d_kv] with n_heads=; d_kv 64, 128 or 256.  Both are
     read in place: the .contiguous() that t5_decode_cross_attention asks for is not needed here.
     key_mask: int64 [B, S], 0 = masked, or None: a masked row is not read, is stored as zero bytes
     and does not enter the scale.  Per (b, h) and tensor: scale = 2^e with e the smallest integer
@@ -456,20 +460,52 @@ def t5_quantize_cross_kv(k_enc, v_enc, key_mask=None, out=None, n_heads=None):
     return out
 
 
-def t5_decode_cross_attention_kv8(q, kv8, key_mask=None, live=None):
-    """t5_decode_cross_attention over fp8 keys and values (trlx_t5_decode_attn_kv8): half the K / V
-    bytes per token, the same fp32 arithmetic.  Returns bfloat16 [B, nH*d_kv].
+KV8_D256 = 256             # the d_kv of trlx_t5_decode_attn_kv8_d256
+KV8_D256_MAX_SPLITS = 16   # the largest `splits` it takes
+
+
+def t5_decode_cross_attention_kv8_d256_geometry(S, splits):
+    """trlx_t5_decode_attn_kv8_d256_geometry as a dict (needs no device): rows_per_wave_load (4),
+    lane_groups (16), keys_per_trip (64), keys_per_range = ceil(ceil(S / 64) / splits) * 64, `ranges`
+    = the non-empty ranges (the grid's y, <= splits) and max_splits."""
+    g = _lib.T5DecodeAttnKv8D256Geometry()
+    _lib.call("trlx_t5_decode_attn_kv8_d256_geometry", int(S), int(splits), ctypes.byref(g))
+    return {k: int(getattr(g, k)) for k, _ in g._fields_}
+
+
+def t5_decode_cross_attention_kv8_d256_workspace_bytes(B, n_heads, splits):
+    """trlx_t5_decode_attn_kv8_d256_workspace_bytes: splits * B * n_heads * 258 * 4 (needs no device)."""
+    return int(_lib.query("trlx_t5_decode_attn_kv8_d256_workspace_bytes", int(B), int(n_heads), int(splits)))
+
+
+def t5_decode_cross_attention_kv8(q, kv8, key_mask=None, live=None, splits=None, workspace=None):
+    """t5_decode_cross_attention over fp8 keys and values (trlx_t5_decode_attn_kv8, at d_kv 256
+    trlx_t5_decode_attn_kv8_d256): half the K / V bytes per token, the same fp32 arithmetic.
+    Returns bfloat16 [B, nH*d_kv].
 
     q: bfloat16, the shapes and strides of t5_decode_cross_attention.  kv8: a T5CrossKV8.
     key_mask, live: as in t5_decode_cross_attention.  score_j = (q · k8_j) * k_scale[b, h]; the
     output is (P · v8) * v_scale[b, h] / sum P, rounded once.  The result differs from the bf16
     route by the quantisation of K and V and by nothing else: t5_decode_cross_attention on
     kv8.dequantize() computes on the same values.  The launch takes the same arguments at every
-    token and can be captured.  On a CPU device: the torch expressions on dequantize()."""
+    token and can be captured.  On a CPU device: the torch expressions on dequantize().
+    splits, d_kv 256 only: None or 1 = one launch, one workgroup per (row, head); 2 ... 16 cut the
+    keys of every (row, head) into that many ranges of whole 64-key trips, a workgroup each, and a
+    second launch merges their fp32 states in split order -- for a batch too small to fill the chip.
+    Bit-reproducible; a row's bits depend on `splits` and on nothing outside the row.  At d_kv 64 /
+    128 anything but None / 1 raises ValueError; the CPU route ignores it.  workspace: None, or a
+    contiguous tensor on the device of at least t5_decode_cross_attention_kv8_d256_workspace_bytes(B,
+    nH, splits) bytes, 16-byte aligned.  With None one is allocated on first use per (device, size)
+    and reused, so at splits > 1 the call captures after one eager call; calls that may run
+    concurrently on different streams must pass workspaces of their own."""
     if not isinstance(kv8, T5CrossKV8):
         raise TypeError("kv8 must be a T5CrossKV8")
     B, nH, S, d = kv8.B, kv8.n_heads, kv8.S, kv8.d_kv
     dev = kv8.device
+    X = 1 if splits is None else int(splits)
+    if not 1 <= X <= (KV8_D256_MAX_SPLITS if d == KV8_D256 else 1):
+        raise ValueError(f"splits = {splits}: None or 1" + (f" ... {KV8_D256_MAX_SPLITS}" if d == KV8_D256 else
+                                                             f" at d_kv {d} (the key split is d_kv {KV8_D256}'s)"))
     _check_q(q, B, nH, d, torch.bfloat16, dev)
     if key_mask is not None:
         if tuple(key_mask.shape) != (B, S) or key_mask.dtype != torch.int64 or key_mask.device != dev:
@@ -492,8 +528,21 @@ def t5_decode_cross_attention_kv8(q, kv8, key_mask=None, live=None):
         q=q2.data_ptr(), ldq=ldq, k_new=None, ldk=0, v_new=None, ldv=0, k=kv8.k8.data_ptr(), v=kv8.v8.data_ptr(),
         bias_by_distance=None, key_mask=_lib.ptr(key_mask), out=out.data_ptr(), B=B, n_heads=nH, d_kv=d,
         max_len=S, t=0, dtype=_lib.BF16, mode=_lib.T5_ATTN_CROSS)
-    _lib.call("trlx_t5_decode_attn_kv8", ctypes.byref(args), kv8.k_scale.data_ptr(), kv8.v_scale.data_ptr(),
-              _lib.ptr(live), _lib.stream_of(out))
+    if d != KV8_D256:
+        _lib.call("trlx_t5_decode_attn_kv8", ctypes.byref(args), kv8.k_scale.data_ptr(), kv8.v_scale.data_ptr(),
+                  _lib.ptr(live), _lib.stream_of(out))
+        return out
+    ws_ptr, ws_bytes = None, 0
+    if X > 1:
+        need = t5_decode_cross_attention_kv8_d256_workspace_bytes(B, nH, X)
+        if workspace is None:
+            workspace = _split_workspace(dev, need)
+        elif not isinstance(workspace, torch.Tensor) or workspace.device != dev or not workspace.is_contiguous() \
+                or workspace.numel() * workspace.element_size() < need:
+            raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {dev}")
+        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    _lib.call("trlx_t5_decode_attn_kv8_d256", ctypes.byref(args), kv8.k_scale.data_ptr(), kv8.v_scale.data_ptr(),
+              _lib.ptr(live), X, ws_ptr, ws_bytes, _lib.stream_of(out))
     return out
 
 
