@@ -1838,6 +1838,73 @@ typedef struct TrlxT5DecodeLinearRowsGeometry {
 int trlx_t5_decode_linear_rows(const trlx_t5_decode_linear_rows_args* a, void* stream);
 int trlx_t5_decode_linear_rows_geometry(TrlxT5DecodeLinearRowsGeometry* g);
 
+/* fp8 weights for the decode-step projections (opt-in, lossy against the bf16 weights;
+ * csrc/t5_decode_linear_w8.hip): the weight-side counterpart of trlx_t5_cross_kv_quantize.
+ *
+ * trlx_t5_linear_w8_quantize: w [N, K] bf16 in nn.Linear.weight's layout, rows ld_w >= K elements
+ * apart (a slice of a packed weight is read in place), to w8 [N, K] e4m3fn bytes, contiguous, and
+ * scale [N] fp32.  One launch, one wave per row, two passes.  Per row: scale = 2^e with e the
+ * smallest integer such that max|w| * 2^-e <= 448 (0 for an all-zero row, clamped to [-100, 119]),
+ * byte = (w * 2^-e) cast to e4m3fn as torch casts it, bit for bit, ties and subnormals included.  A
+ * row holding an Inf / NaN gets a NaN scale and 0x7f in every byte (the rule of
+ * trlx_t5_cross_kv_quantize, per row).  K a multiple of 8, 8 to 16384; w, w8 and scale 16-byte
+ * aligned; ld_w a multiple of 8.
+ *
+ * trlx_t5_decode_linear_w8: out = epilogue( prologue(x) . (scale (.) weight8)^T ), the expression,
+ * the RMSNorm prologue and the four epilogue forms of trlx_t5_decode_linear with the weight given as
+ * those bytes and scales (weight8 [2N, K] and scale [2N] when gated).  The bytes become bf16 in
+ * registers (exact), the products are bf16 MFMA with fp32 accumulation, and the row's scale
+ * multiplies the merged fp32 sum once, before the epilogue: up to the order of one fp32 sum the
+ * result is what a bf16 kernel gives on the dequantised weight.  A workgroup is `waves` waves (4, 8
+ * or 16; 0 takes the default, a pure function of (N, K, gated) that
+ * trlx_t5_decode_linear_w8_geometry reports) and owns 16 output columns and every row; K is split
+ * across those waves only, turn j (256 k) to wave j % waves, and the partial sums are added in wave
+ * order: no atomics, no workspace, one launch, two calls give the same bits.  A row's bits depend on
+ * its x row, the weight row, K and waves, not on M, N or the row's position.
+ * TRLX_BF16 x / out only.  M >= 1; K a multiple of 64, 64 to 16384 (8192 with a norm weight); N a
+ * multiple of 16.  Every pointer is 16-byte aligned; the row strides of x, residual and out are
+ * multiples of 8 elements, ld_w (in bytes) a multiple of 16.
+ * Refused before any launch, out untouched: what trlx_t5_decode_linear refuses, with its statuses;
+ * a NULL scale; waves other than 0, 4, 8, 16 (TRLX_ERR_ARG).
+ * Not built: fp8 activations / an fp8 MFMA, per-group scales, a K split across workgroups, a
+ * rows-split or live form, fp32, a backward. */
+typedef struct trlx_t5_decode_linear_w8_args {
+    const void* x;
+    int64_t ld_x;
+    const void* weight8;              /* e4m3fn bytes, [N, K] ([2N, K] gated) */
+    int64_t ld_w;                     /* bytes between weight rows */
+    const float* scale;               /* [N] ([2N] gated), powers of two */
+    const void* norm_weight;          /* [K] or NULL */
+    const void* residual;             /* [M, N] or NULL */
+    int64_t ld_residual;
+    void* out;
+    int64_t ld_out;
+    int64_t M;
+    int64_t K;
+    int64_t N;                        /* output columns */
+    float eps;
+    int dtype;                        /* TRLX_BF16 */
+    int act;                          /* trlx_t5_act or TRLX_T5_ACT_NONE */
+    int gated;                        /* weight8 is [2N, K] */
+    int waves;                        /* 0 (the default), 4, 8 or 16 */
+    int reserved;                     /* 0 */
+} trlx_t5_decode_linear_w8_args;
+typedef struct TrlxT5DecodeLinearW8Geometry {
+    int waves;                        /* the default for (N, K, gated) */
+    int turns;                        /* ceil(K / 256): turn j belongs to wave j % waves */
+    int cols_per_block;               /* output columns a workgroup owns */
+    int rows_per_tile;
+    int k_per_chunk;                  /* one 16-byte weight load per lane, two MFMAs */
+    int chunks_per_wave_turn;
+    int max_row_tiles;                /* accumulator tiles of a wave: row tiles per pass x weight slabs */
+    int max_k;
+    int norm_max_k;                   /* the largest K taken with a norm weight */
+    int norm_wave_row_max_k;          /* up to here the norm's sum takes one wave per row */
+} TrlxT5DecodeLinearW8Geometry;
+int trlx_t5_linear_w8_quantize(const void* w, int64_t ld_w, void* w8, float* scale, int64_t N, int64_t K, void* stream);
+int trlx_t5_decode_linear_w8(const trlx_t5_decode_linear_w8_args* a, void* stream);
+int trlx_t5_decode_linear_w8_geometry(int64_t N, int64_t K, int gated, TrlxT5DecodeLinearW8Geometry* g);
+
 /* ---------------------------------------------------------------- §8f: device-resident rollout store
  * Row copy between padded columnar [rows, W] buffers — replaces the reference's
  * `.cpu()` of the experience tensors, per-sample PPORLElement lists and the pad_sequence

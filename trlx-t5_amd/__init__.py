@@ -88,6 +88,10 @@ Drop-in names (reference file:line in danyang-rainbow/trlx-t5):
       instead of 12 (HF T5Block under generate; every other projection stays hipBLASLt);
       split_rows=True spreads the rows over workgroups and live=recorder.unfinished skips the
       projections of finished rows on the device (trlx_t5_decode_linear_rows)
+  T5LinearW8, t5_quantize_linear_weight, t5_decode_linear_w8, T5DecodeBlockWeights8 — opt-in and lossy:
+      the decode-step projections over e4m3fn weights with a power-of-two scale per output row, on a
+      streaming MFMA kernel of their own (K split over 4 / 8 / 16 waves of a workgroup, next turn's
+      weight loads in flight under the current one's MFMAs); t5_decode_layer_fused takes the fp8 block
   PPORolloutStorage, PPORLElement, PPORLBatch
       trlx/pipeline/ppo_pipeline.py, trlx/data/ppo_types.py (device-resident store)
   ILQLRolloutStorage (.from_samples = make_experience, .collate, .create_loader), ILQLElement
@@ -128,6 +132,7 @@ from .t5_attention import t5_attention, t5_attention_train, t5_relative_bias_buc
 from .t5_ff import T5FeedForward, t5_ff_act, t5_ff_act_packed
 from .t5_norm import T5LayerNorm, t5_add_rmsnorm, t5_rmsnorm
 from .t5_decode_linear import T5DecodeBlockWeights, t5_decode_layer_fused, t5_decode_linear
+from .t5_linear_w8 import T5DecodeBlockWeights8, T5LinearW8, t5_decode_linear_w8, t5_quantize_linear_weight
 from .control import PPOControlState
 from .step import PPOHotPath
 from .comm import RcclComm
@@ -156,6 +161,7 @@ __all__ = [
     "t5_ff_act", "t5_ff_act_packed", "T5FeedForward",
     "t5_rmsnorm", "t5_add_rmsnorm", "T5LayerNorm",
     "t5_decode_linear", "T5DecodeBlockWeights", "t5_decode_layer_fused",
+    "T5LinearW8", "t5_quantize_linear_weight", "t5_decode_linear_w8", "T5DecodeBlockWeights8",
 ]
 
 

@@ -236,6 +236,22 @@ class T5DecodeLinearRowsArgs(ctypes.Structure):
     _fields_ = T5DecodeLinearArgs._fields_ + [("live", _c_vp), ("reserved", _c_i64)]
 
 
+class T5DecodeLinearW8Args(ctypes.Structure):
+    """Mirror of trlx_t5_decode_linear_w8_args (include/trlx_t5_amd.h)."""
+    _fields_ = [
+        ("x", _c_vp), ("ld_x", _c_i64), ("weight8", _c_vp), ("ld_w", _c_i64), ("scale", _c_vp), ("norm_weight", _c_vp),
+        ("residual", _c_vp), ("ld_residual", _c_i64), ("out", _c_vp), ("ld_out", _c_i64),
+        ("M", _c_i64), ("K", _c_i64), ("N", _c_i64), ("eps", ctypes.c_float), ("dtype", _c_int), ("act", _c_int),
+        ("gated", _c_int), ("waves", _c_int), ("reserved", _c_int),
+    ]
+
+
+class T5DecodeLinearW8Geometry(ctypes.Structure):
+    """Mirror of TrlxT5DecodeLinearW8Geometry (include/trlx_t5_amd.h)."""
+    _fields_ = [(n, _c_int) for n in ("waves", "turns", "cols_per_block", "rows_per_tile", "k_per_chunk", "chunks_per_wave_turn",
+                                      "max_row_tiles", "max_k", "norm_max_k", "norm_wave_row_max_k")]
+
+
 class T5DecodeLinearRowsGeometry(ctypes.Structure):
     """Mirror of TrlxT5DecodeLinearRowsGeometry (include/trlx_t5_amd.h)."""
     _fields_ = [(n, _c_int) for n in ("threads", "cols_per_block", "rows_per_tile", "rows_per_block", "max_m_live", "reserved")]
@@ -462,6 +478,9 @@ SIGNATURES = {
     "trlx_t5_decode_linear_geometry": (_c_int, [ctypes.POINTER(T5DecodeLinearGeometry)]),
     "trlx_t5_decode_linear_rows": (_c_int, [ctypes.POINTER(T5DecodeLinearRowsArgs), _c_vp]),
     "trlx_t5_decode_linear_rows_geometry": (_c_int, [ctypes.POINTER(T5DecodeLinearRowsGeometry)]),
+    "trlx_t5_linear_w8_quantize": (_c_int, [_c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i64, _c_vp]),
+    "trlx_t5_decode_linear_w8": (_c_int, [ctypes.POINTER(T5DecodeLinearW8Args), _c_vp]),
+    "trlx_t5_decode_linear_w8_geometry": (_c_int, [_c_i64, _c_i64, _c_int, ctypes.POINTER(T5DecodeLinearW8Geometry)]),
     "trlx_rows_copy": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp,
                                 _c_i64, _c_vp, _c_i64, _c_vp]),
     "trlx_shift_tokens_right": (_c_int, [_c_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_vp, _c_i64, _c_vp]),

@@ -270,7 +270,9 @@ def t5_decode_layer_fused(h, w, self_attention, cross_attention, act="gelu_new",
                           split_rows=False):
     """One decoder layer's decode step on the residual stream h [B, D], updated in place, in 8 launches.
 
-    w: T5DecodeBlockWeights.  self_attention(q, k_new, v_new) and cross_attention(q) are the caller's
+    w: T5DecodeBlockWeights, or a T5DecodeBlockWeights8 (fp8 weights, t5_linear_w8): the same 8 launches
+    with the six projections on t5_decode_linear_w8, which has no `live` / `split_rows` form.
+    self_attention(q, k_new, v_new) and cross_attention(q) are the caller's
     attention launches (t5_decode_self_attention with its cache, clock, bias table and live rows;
     t5_decode_cross_attention or its kv8 form) and return [B, inner].  bufs: None, or a dict with
     preallocated "qkv" [B, 3 inner], "cq" [B, inner] and "ff" [B, F] so that a captured step allocates
@@ -282,13 +284,20 @@ def t5_decode_layer_fused(h, w, self_attention, cross_attention, act="gelu_new",
     Returns h."""
     bufs = bufs or {}
     i = w.inner
-    kw = dict(live=live, split_rows=split_rows)
-    qkv = t5_decode_linear(h, w.qkv, norm_weight=w.ln[0], eps=eps, out=bufs.get("qkv"), **kw)
+    linear, kw = t5_decode_linear, dict(live=live, split_rows=split_rows)
+    if not isinstance(w, T5DecodeBlockWeights):
+        from .t5_linear_w8 import T5DecodeBlockWeights8, t5_decode_linear_w8
+        if not isinstance(w, T5DecodeBlockWeights8):
+            raise TypeError("t5_decode_layer_fused: w must be a T5DecodeBlockWeights or a T5DecodeBlockWeights8")
+        if live is not None or split_rows:
+            raise ValueError("t5_decode_layer_fused: live / split_rows with fp8 weights (t5_decode_linear_w8 has no rows form)")
+        linear, kw = t5_decode_linear_w8, {}
+    qkv = linear(h, w.qkv, norm_weight=w.ln[0], eps=eps, out=bufs.get("qkv"), **kw)
     a = self_attention(qkv[:, :i], qkv[:, i:2 * i], qkv[:, 2 * i:])
-    t5_decode_linear(a, w.o, residual=h, out=h, **kw)
-    q = t5_decode_linear(h, w.cq, norm_weight=w.ln[1], eps=eps, out=bufs.get("cq"), **kw)
+    linear(a, w.o, residual=h, out=h, **kw)
+    q = linear(h, w.cq, norm_weight=w.ln[1], eps=eps, out=bufs.get("cq"), **kw)
     c = cross_attention(q)
-    t5_decode_linear(c, w.co, residual=h, out=h, **kw)
-    f = t5_decode_linear(h, w.wi, norm_weight=w.ln[2], eps=eps, act=act, gated=w.gated, out=bufs.get("ff"), **kw)
-    t5_decode_linear(f, w.wo, residual=h, out=h, **kw)
+    linear(c, w.co, residual=h, out=h, **kw)
+    f = linear(h, w.wi, norm_weight=w.ln[2], eps=eps, act=act, gated=w.gated, out=bufs.get("ff"), **kw)
+    linear(f, w.wo, residual=h, out=h, **kw)
     return h
